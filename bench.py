@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """MIRROR pre-training step benchmark on MI355X (BASELINE.json metric: SSL samples/s, slide+RNA pairs).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds what takes runs or legs of its
+own: the per-kernel roofline leg (one HIP-event-timed warm-up step, an eager re-run of min(K, 5) steps after the timed region,
+the PMC evidence files under profiles/) and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed
+(see dump_outputs).
 
 N > 1: one rank per GPU over RCCL.  Under an external launcher (`python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N`, the reference's scripts/run_train_mirror.sh:62-71) the ranks read RANK / LOCAL_RANK / WORLD_SIZE from
@@ -78,6 +83,27 @@ def self_launch(n: int) -> int:
     return subprocess.run(cmd, env=dict(os.environ, MASTER_ADDR="127.0.0.1")).returncode
 
 
+DUMP_SAMPLE = 1 << 22       # elements kept of each parameter-sized output: 16 MB of f32, two such files + the losses < 64 MB
+
+
+def dump_outputs(d: str, losses, model) -> None:
+    """What a caller of the timed step holds after its last call, as f32 .npy files under d: losses.npy (the six values
+    TrainEngine.step returned), params.npy (the parameters its Adam update left) and grads.npy (that step's gradients, which stay
+    in p.grad until the next step), both over the parameters concatenated in named_parameters() order — a fixed seeded
+    sample of DUMP_SAMPLE elements when there are more, so two builds of the same model are compared element for element."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "losses.npy"), torch.stack([x.reshape(()).float() for x in losses]).cpu().numpy())
+    ps = [p for _, p in model.named_parameters()]
+    n = sum(p.numel() for p in ps)
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values.to(ps[0].device)
+    for name, ts in (("params", [p.detach() for p in ps]), ("grads", [p.grad for p in ps])):
+        flat = torch.cat([t.reshape(-1).float() for t in ts])
+        np.save(os.path.join(d, f"{name}.npy"), (flat if idx is None else flat[idx]).cpu().numpy())
+
+
 CONFIGS = {
     # BASELINE.json configs[1] (the metric's config) and configs[0]; "template" = the reference's own operating point,
     # configs/pretrain/mirror.template.yaml:16-46 (2048 Phikon tokens x 768-d, 10234 genes, D = 768 -> dh = 96, m = 384,
@@ -99,14 +125,19 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (weak scaling); default 16 (the reference template's batch_size), 8 for --config c4")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "bf16_pinv32", "fp32", "fp8"])
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline leg")
     ap.add_argument("--no-gather", action="store_true", help="rank-local InfoNCE even when N>1 (reference behaviour)")
     ap.add_argument("--grad-dtype", default="f32", choices=["f32", "bf16"], help="wire format of the gradient buckets at N > 1 (config 5: bf16)")
     ap.add_argument("--feed", default="resident", choices=["resident", "host", "host-bf16"],
                     help="resident (default, the metric): the batch is in HBM when the timed region starts; host / host-bf16: every "
                          "step's batch comes from pinned host memory (f32 / bf16 patch features) through mirror_amd.data.HostFeeder, "
                          "copied on a side stream under the previous step — the PCIe-inclusive rate, reported as a separate line")
+    ap.add_argument("--full", action="store_true", help="also the roofline leg and the CPU baseline (off: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's losses, parameters and gradients to DIR/<name>.npy (f32)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # a timing tool must not be one environment variable away from a fake number: the MH_EXP_* switches make entry points
     # return without launching (results garbage) and only exist in `make EXP=1` builds of the library
@@ -176,15 +207,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- warm-up; one warm-up step (the second when there is one) times every MFMA kernel launch (all GEMM template
-    #      instances + the fused pinv chains) with HIP events to find the dominant kernel
+    # ---- warm-up; with --full one warm-up step (the second when there is one) times every MFMA kernel launch (all GEMM
+    #      template instances + the fused pinv chains) with HIP events to find the dominant kernel
     # The engine records its HIP graphs during its third step (the whole step at N = 1, the RNA branch at N > 1) after two
     # eager ones: at least three untimed steps run before the timed region whatever --warmup says, so that no capture
     # (~0.3 s, once) is ever timed; `warmup` in the JSON line is the flag, `config.untimed_steps` what actually ran.
     nwarm = max(3, a.warmup)
     summ = {}
     for i in range(nwarm):
-        if i == min(1, nwarm - 1):
+        if a.full and i == min(1, nwarm - 1):
             torch.cuda.synchronize()
             K.gemm_profiler = K.GemmProfiler()
             eng.step(wsi, rna, **kw)
@@ -193,7 +224,6 @@ def main():
             K.gemm_profiler = None
         else:
             eng.step(wsi, rna, **kw)
-    dominant = max(summ, key=lambda v: summ[v]["total_ms"])
 
     # ---- timed region: exactly K steps, barrier + synchronize on both sides.  On one GPU every step is ONE HIP-graph
     #      launch (TrainEngine captures the step after two eager ones), so no host code runs between its kernels.
@@ -224,17 +254,21 @@ def main():
     if os.environ.get("MIRROR_BENCH_HOSTTIME") and rank == 0 and host_us:
         print("host us per step() call: " + " ".join(f"{u:.0f}" for u in host_us), file=sys.stderr)
     loss_vals = [float(x) for x in losses]
-    # ---- roofline leg: the dominant kernel's launches carry HIP event pairs on their launch stream.  Events cannot be
-    #      recorded inside a graph replay, so the same steps are run once more eagerly right here (same process, same
-    #      inputs, min(K, 5) steps); profiles/ holds the rocprofv3 per-kernel averages of the graph run for comparison.
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, losses, model)
     graphed = getattr(eng, "_graph", None) is not None
-    eng._use_graph = False
-    K.gemm_profiler = K.GemmProfiler(only=dominant)
-    for _ in range(min(a.steps, 5)):
-        eng.step(wsi, rna, **kw)
-    torch.cuda.synchronize()
-    prof = K.gemm_profiler.summary().get(dominant, {"launches": 0, "total_ms": 0.0, "flops": 0.0})
-    K.gemm_profiler = None
+    if a.full:
+        # ---- roofline leg: the dominant kernel's launches carry HIP event pairs on their launch stream.  Events cannot be
+        #      recorded inside a graph replay, so the same steps are run once more eagerly right here (same process, same
+        #      inputs, min(K, 5) steps); profiles/ holds the rocprofv3 per-kernel averages of the graph run for comparison.
+        dominant = max(summ, key=lambda v: summ[v]["total_ms"])
+        eng._use_graph = False
+        K.gemm_profiler = K.GemmProfiler(only=dominant)
+        for _ in range(min(a.steps, 5)):
+            eng.step(wsi, rna, **kw)
+        torch.cuda.synchronize()
+        prof = K.gemm_profiler.summary().get(dominant, {"launches": 0, "total_ms": 0.0, "flops": 0.0})
+        K.gemm_profiler = None
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -245,49 +279,6 @@ def main():
         value = samples / dt
         fl_fwd = model_flops_fwd(shp["N"], shp["F"], shp["D"], shp["G"], shp["L"], mlp_ratio=shp["mlp"])
         step_tflops = 3 * fl_fwd * a.batch * world * a.steps / dt / 1e12
-        is_f32 = dominant.startswith("gemm_kernel<0")
-        peak = PEAK_F32_TFLOPS if is_f32 else PEAK_BF16_TFLOPS
-        avg_ms = prof["total_ms"] / max(prof["launches"], 1)
-        # HBM-side bytes per launch of the dominant kernel: PMC passes (FETCH_SIZE, WRITE_SIZE in separate runs, gfx950
-        # correction applied) summarised by tools/pmc_summary.py into profiles/pmc_traffic.json; null when not collected
-        # the file records the digest of the kernel sources it was measured on: an entry from other code is refused (null)
-        traffic, traffic_note = None, "no profiles/pmc_traffic.json entry for this kernel"
-        try:
-            with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as fh:
-                pm = json.load(fh)
-            ent = pm["kernels"].get(dominant.replace(" ", ""))
-            if ent and pm.get("csrc_sha256") == csrc_digest() and pm.get("config", "c2") == a.config:
-                traffic, traffic_note = ent["bytes_per_launch"], f"PMC passes on csrc {pm['csrc_sha256']} (tools/collect_profiles.sh)"
-            elif ent:
-                traffic_note = (f"stale: profiles/pmc_traffic.json was measured on csrc {pm.get('csrc_sha256')}, "
-                                f"this run is {csrc_digest()} / config {a.config}")
-        except (OSError, ValueError, KeyError):
-            pass
-        # step-level HBM traffic (sum over every kernel of the same PMC passes) and the dominant kernel's MFMA-pipe utilisation
-        # (profiles/pmc_mfma_busy.json, its own PMC pass): both only when measured on exactly these kernel sources
-        step_bytes, mfma_busy, mfma_note = None, None, "no profiles/pmc_mfma_busy.json entry for this kernel"
-        step_launches = None
-        try:
-            if pm.get("csrc_sha256") == csrc_digest() and pm.get("config", "c2") == a.config:
-                steps_prof = float(pm.get("steps", 9))
-                step_bytes = sum(v["bytes_per_launch"] * v["launches"] for v in pm["kernels"].values()) / steps_prof
-                if pm.get("replayed_step"):          # the replayed step alone (what is timed), not the 9-step average
-                    step_bytes = float(pm["replayed_step"]["hbm_bytes"])
-                    step_launches = int(pm["replayed_step"]["launches"])
-        except (NameError, KeyError, TypeError):
-            pass
-        try:
-            with open(os.path.join(ROOT, "profiles", "pmc_mfma_busy.json")) as fh:
-                mb = json.load(fh)
-            key = {k.replace(" ", "").replace("unsignedshort", "bf16"): v for k, v in mb["kernels"].items()}
-            ent = key.get(dominant.replace(" ", ""))
-            if ent and mb.get("csrc_sha256") == csrc_digest():
-                mfma_busy, mfma_note = ent["mfma_pipe_utilisation_of_chip"], f"SQ_VALU_MFMA_BUSY_CYCLES pass on csrc {mb['csrc_sha256']} (tools/pmc_mfma.sh)"
-            elif ent:
-                mfma_note = f"stale: measured on csrc {mb.get('csrc_sha256')}, this run is {csrc_digest()}"
-        except (OSError, ValueError, KeyError):
-            pass
-        ach = (prof["flops"] / max(prof["launches"], 1)) / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
         out = {
             "metric": "SSL samples/sec (slide+RNA pairs)", "value": round(value, 3), "unit": "samples/s",
             "n_gpus": world, "world_size_reported": (dist.get_world_size() if world > 1 else 1), "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
@@ -304,25 +295,69 @@ def main():
             "model_tflops_per_s": round(step_tflops, 2),
             "model_flops_frac_of_bf16_peak": round(step_tflops / world / PEAK_BF16_TFLOPS, 4),
             "losses": [round(x, 5) for x in loss_vals],
-            "roofline": {"bound": "mfma", "kernel": dominant, "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(ach / peak, 4), "traffic": traffic, "traffic_source": traffic_note,
-                         "bound_note": ("`bound` names what limits the DOMINANT KERNEL (a chain of dependent 256^3 products on half of the "
-                                        "CUs: MFMA latency, not throughput); the STEP as a whole moves step_hbm_bytes through HBM and "
-                                        "is closer to the HBM roof than to the MFMA roof, see step_hbm_frac_of_6.3TBps"),
-                         "mfma_busy_frac": mfma_busy, "mfma_busy_source": mfma_note,
-                         "step_hbm_bytes": None if step_bytes is None else int(step_bytes),
-                         "step_launches": step_launches,      # dispatches of one replayed step in the same PMC passes
-                         "step_hbm_frac_of_6.3TBps": None if step_bytes is None else round(step_bytes / (dt / a.steps) / 6.3e12, 4),
-                         "launches_timed": prof["launches"],
-                         "timed_in": ("eager re-run of min(K,5) steps right after the timed region (the timed region "
-                                      "replays one HIP graph per step)") if graphed else "the timed region",
-                         "avg_launch_ms": round(avg_ms, 5),
-                         "share_of_mfma_kernel_time_in_profiled_step": round(summ[dominant]["total_ms"] / max(sum(s["total_ms"] for s in summ.values()), 1e-9), 3),
-                         "flops_per_launch": round(prof["flops"] / max(prof["launches"], 1) / 1e9, 3),
-                         "flops_unit": "GFLOP (algorithmic: 2*M*N*K*batch per GEMM; 2*m^3 per chain product)",
-                         "runner_up": sorted(((round(v["total_ms"], 3), k) for k, v in summ.items()), reverse=True)[1:4]},
         }
-        if world == 1 and not a.no_cpu_baseline and not shp.get("mask"):      # (the CPU leg times the unmasked path; c4 is reported without it)
+        if a.full:
+            is_f32 = dominant.startswith("gemm_kernel<0")
+            peak = PEAK_F32_TFLOPS if is_f32 else PEAK_BF16_TFLOPS
+            avg_ms = prof["total_ms"] / max(prof["launches"], 1)
+            # HBM-side bytes per launch of the dominant kernel: PMC passes (FETCH_SIZE, WRITE_SIZE in separate runs, gfx950
+            # correction applied) summarised by tools/pmc_summary.py into profiles/pmc_traffic.json; null when not collected
+            # the file records the digest of the kernel sources it was measured on: an entry from other code is refused (null)
+            traffic, traffic_note = None, "no profiles/pmc_traffic.json entry for this kernel"
+            try:
+                with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as fh:
+                    pm = json.load(fh)
+                ent = pm["kernels"].get(dominant.replace(" ", ""))
+                if ent and pm.get("csrc_sha256") == csrc_digest() and pm.get("config", "c2") == a.config:
+                    traffic, traffic_note = ent["bytes_per_launch"], f"PMC passes on csrc {pm['csrc_sha256']} (tools/collect_profiles.sh)"
+                elif ent:
+                    traffic_note = (f"stale: profiles/pmc_traffic.json was measured on csrc {pm.get('csrc_sha256')}, "
+                                    f"this run is {csrc_digest()} / config {a.config}")
+            except (OSError, ValueError, KeyError):
+                pass
+            # step-level HBM traffic (sum over every kernel of the same PMC passes) and the dominant kernel's MFMA-pipe utilisation
+            # (profiles/pmc_mfma_busy.json, its own PMC pass): both only when measured on exactly these kernel sources
+            step_bytes, mfma_busy, mfma_note = None, None, "no profiles/pmc_mfma_busy.json entry for this kernel"
+            step_launches = None
+            try:
+                if pm.get("csrc_sha256") == csrc_digest() and pm.get("config", "c2") == a.config:
+                    steps_prof = float(pm.get("steps", 9))
+                    step_bytes = sum(v["bytes_per_launch"] * v["launches"] for v in pm["kernels"].values()) / steps_prof
+                    if pm.get("replayed_step"):          # the replayed step alone (what is timed), not the 9-step average
+                        step_bytes = float(pm["replayed_step"]["hbm_bytes"])
+                        step_launches = int(pm["replayed_step"]["launches"])
+            except (NameError, KeyError, TypeError):
+                pass
+            try:
+                with open(os.path.join(ROOT, "profiles", "pmc_mfma_busy.json")) as fh:
+                    mb = json.load(fh)
+                key = {k.replace(" ", "").replace("unsignedshort", "bf16"): v for k, v in mb["kernels"].items()}
+                ent = key.get(dominant.replace(" ", ""))
+                if ent and mb.get("csrc_sha256") == csrc_digest():
+                    mfma_busy, mfma_note = ent["mfma_pipe_utilisation_of_chip"], f"SQ_VALU_MFMA_BUSY_CYCLES pass on csrc {mb['csrc_sha256']} (tools/pmc_mfma.sh)"
+                elif ent:
+                    mfma_note = f"stale: measured on csrc {mb.get('csrc_sha256')}, this run is {csrc_digest()}"
+            except (OSError, ValueError, KeyError):
+                pass
+            ach = (prof["flops"] / max(prof["launches"], 1)) / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
+            out["roofline"] = {"bound": "mfma", "kernel": dominant, "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s",
+                               "frac": round(ach / peak, 4), "traffic": traffic, "traffic_source": traffic_note,
+                               "bound_note": ("`bound` names what limits the DOMINANT KERNEL (a chain of dependent 256^3 products on half of the "
+                                              "CUs: MFMA latency, not throughput); the STEP as a whole moves step_hbm_bytes through HBM and "
+                                              "is closer to the HBM roof than to the MFMA roof, see step_hbm_frac_of_6.3TBps"),
+                               "mfma_busy_frac": mfma_busy, "mfma_busy_source": mfma_note,
+                               "step_hbm_bytes": None if step_bytes is None else int(step_bytes),
+                               "step_launches": step_launches,      # dispatches of one replayed step in the same PMC passes
+                               "step_hbm_frac_of_6.3TBps": None if step_bytes is None else round(step_bytes / (dt / a.steps) / 6.3e12, 4),
+                               "launches_timed": prof["launches"],
+                               "timed_in": ("eager re-run of min(K,5) steps right after the timed region (the timed region "
+                                            "replays one HIP graph per step)") if graphed else "the timed region",
+                               "avg_launch_ms": round(avg_ms, 5),
+                               "share_of_mfma_kernel_time_in_profiled_step": round(summ[dominant]["total_ms"] / max(sum(s["total_ms"] for s in summ.values()), 1e-9), 3),
+                               "flops_per_launch": round(prof["flops"] / max(prof["launches"], 1) / 1e9, 3),
+                               "flops_unit": "GFLOP (algorithmic: 2*M*N*K*batch per GEMM; 2*m^3 per chain product)",
+                               "runner_up": sorted(((round(v["total_ms"], 3), k) for k, v in summ.items()), reverse=True)[1:4]}
+        if a.full and world == 1 and not a.no_cpu_baseline and not shp.get("mask"):      # (the CPU leg times the unmasked path; c4 is reported without it)
             from oracle import mirror_oracle as O
             from oracle.cpu_step import time_cpu_steps
             cfg = O.Cfg(wsi_embed_dim=shp["F"], rna_embed_dim=shp["G"], embed_dim=shp["D"], wsi_num_tokens=shp["N"],

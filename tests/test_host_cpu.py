@@ -243,6 +243,35 @@ def test_bench_gpus_n_without_launcher_refuses_when_devices_are_missing():
     assert '"n_gpus"' not in r.stdout
 
 
+def test_bench_dump_outputs_writes_a_fixed_f32_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: losses, parameters and gradients as f32 .npy; above DUMP_SAMPLE elements the same seeded
+    sample in every run (two builds are compared element for element), and the three files stay under 64 MB at any size."""
+    import numpy as np
+    import bench
+    assert (2 * bench.DUMP_SAMPLE + 6) * 4 < 64 << 20
+    model = torch.nn.Sequential(torch.nn.Linear(40, 30), torch.nn.Linear(30, 5))
+    model(torch.randn(3, 40)).square().sum().backward()
+    losses = tuple(torch.arange(6, dtype=torch.float32).unbind(0))
+    flat = {"params": torch.cat([p.detach().reshape(-1) for p in model.parameters()]),
+            "grads": torch.cat([p.grad.reshape(-1) for p in model.parameters()])}
+    bench.dump_outputs(str(tmp_path / "all"), losses, model)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    bench.dump_outputs(str(tmp_path / "a"), losses, model)
+    bench.dump_outputs(str(tmp_path / "b"), losses, model)
+    assert sorted(os.listdir(tmp_path / "a")) == ["grads.npy", "losses.npy", "params.npy"]
+    for d in ("all", "a", "b"):
+        got = {f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)}
+        assert all(v.dtype == np.float32 for v in got.values())
+        assert got["losses"].tolist() == [0.0, 1.0, 2.0, 3.0, 4.0, 5.0]
+        for k, v in flat.items():
+            assert v.numel() > 100 and got[k].shape == ((v.numel(),) if d == "all" else (100,))
+            if d == "all":
+                assert np.array_equal(got[k], v.numpy())
+            else:
+                assert np.array_equal(got[k], np.load(tmp_path / "a" / f"{k}.npy"))
+                assert np.isin(got[k], v.numpy()).all()
+
+
 def test_rna_block_ok_mirrors_the_kernel_limits():
     """mh_rna_block_fwd rejects D > 2048 and operand images above 158 KiB (csrc/rna_block.hip): the host-side admission test
     must say no to the same shapes so that Block.forward falls back to the composed ops instead of raising."""

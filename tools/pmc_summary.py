@@ -64,4 +64,4 @@ if per_step:
     replayed = {"launches": lo, "hbm_bytes": int(sum(p["hbm_bytes"] for p in rp) / len(rp)), "steps_averaged": len(rp)}
 
 json.dump({"csrc_sha256": csrc_digest(), "config": "c2", "steps": 9, "per_step": per_step, "replayed_step": replayed, "note": "bytes_per_launch = (2 x FETCH_SIZE + WRITE_SIZE) KiB, averaged over the launches of each kernel in a "
-                   "`bench.py --steps 3 --warmup 1` run = 9 steps (3 untimed, 3 timed, 3 eager re-run); see tools/pmc_summary.py", "kernels": out}, sys.stdout, indent=1)
+                   "`bench.py --full --steps 3 --warmup 1` run = 9 steps (3 untimed, 3 timed, 3 eager re-run); see tools/pmc_summary.py", "kernels": out}, sys.stdout, indent=1)
