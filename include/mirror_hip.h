@@ -688,6 +688,41 @@ int mh_adam(float* p, const float* g, float* m, float* v, void* shadow_bf16, int
  * min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0); scratch1 = one device float. */
 int mh_grad_clip(const float* g, int64_t n, float grad_scale, float max_norm, float* scratch1, float* dev_state, mh_stream s);
 
+/* ---------------------------------------------------------------- downstream survival step (train_survival.py, v119)
+ * logits [N x M] f32, row stride ld; event_times [N] int32 / int64 (dt_t = MH_SV_I32 / MH_SV_I64: the dataset's disc_label is
+ * torch.int, datasets/dataset_survival.py:307); censoring [N] read through dt_c (bool / uint8, int32, int64 or f32), compared as
+ * the reference does (`censoring == 1`, `== 0`).  lo / hi: the hazard clamp bounds eps, 1 - eps rounded to f32 as torch rounds a
+ * clamp scalar; lo is also the CE clamp of p_sum and of the chosen probability.  One lane per row, the M bins in the reference's
+ * order; every entry point is deterministic (no float atomics) and graph capturable. */
+#define MH_SV_U8 0
+#define MH_SV_I32 1
+#define MH_SV_I64 2
+#define MH_SV_F32 3
+#define MH_SURV_NLL 0   /* losses/nll_surv.py:17-94 (NLLSurvLoss.forward) */
+#define MH_SURV_CE 1    /* losses/cross_entropy_surv.py:25-105 (CrossEntropySurvLoss.forward) */
+/* per-row losses into loss_rows [N] (nullable) and out[0] = coef * sum_r loss_r (nullable; STORED, not accumulated; the rows are
+ * summed in a fixed order by one block).  NLL: loss_r = w_all * nll_r + w_unc * [censoring_r == 1] * nll_r with w_all = 1 - alpha,
+ * w_unc = alpha (losses/nll_surv.py:84-87); rows with censoring outside {0, 1} are 0; T >= M and T < 0 follow the reference's masks.
+ * CE: the target is T when censoring == 1, else class M; an uncensored T outside [0, M] (where the reference's gather raises) gives
+ * NaN in that row.  w_all / w_unc are ignored for CE. */
+int mh_surv_loss_fwd(const float* logits, int64_t ld, const void* event_times, int dt_t, const void* censoring, int dt_c, int N, int M,
+                     int kind, float lo, float hi, float w_all, float w_unc, float coef, float* loss_rows, float* out, mh_stream s);
+/* dlogits [N x M] contiguous = d(sum_r gcoef * g[0 or r] * loss_r) / d logits, recomputed from logits (nothing saved by the forward):
+ * the derivative of the reference's expression as written (zero where the sigmoid clamp is active; CE through p / clamp(p_sum) and
+ * the clamp of the chosen probability).  A NaN CE row (see above) gives a NaN dlogits row. */
+int mh_surv_loss_bwd(const float* logits, int64_t ld, const void* event_times, int dt_t, const void* censoring, int dt_c, int N, int M,
+                     int kind, float lo, float hi, float w_all, float w_unc, const float* g, int g_per_row, float gcoef, float* dlogits,
+                     mh_stream s);
+/* risk[r] = -sum_j prod_{i <= j} (1 - sigmoid(logits[r, i]))   (train_survival.py:1431-1433; no clamp) */
+int mh_surv_risk(const float* logits, int64_t ld, int N, int M, float* risk, mh_stream s);
+/* pair counts of the censored concordance index (sksurv.metrics.concordance_index_censored, train_survival.py:1460-1465):
+ * counts[5] int64 = {concordant, discordant, tied_risk, tied_time, comparable}, zeroed on s by this call.  Pair (i, j) is comparable
+ * when event[i] and (time[j] > time[i] or (time[j] == time[i] and !event[j])); tied when |est[j] - est[i]| <= tied_tol in f32,
+ * concordant when not tied and est[j] < est[i], discordant otherwise; tied_time counts the comparable pairs at equal time.
+ * O(n^2) pairs through LDS, integer atomics (deterministic); n <= 2^26. */
+int mh_cindex_counts(const uint8_t* event, const double* time, const float* estimate, int64_t n, float tied_tol, int64_t* counts,
+                     mh_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2847,3 +2847,41 @@ class MatmulNTFn(Function):
         a, b = ctx.saved_tensors
         dG = dG.contiguous()
         return K.gemm(dG, b, mma=MH_F32), K.gemm(dG.t(), a, mma=MH_F32)
+
+
+def _f32(x: float) -> float:
+    """A Python float rounded to f32 the way torch rounds a scalar operand of an f32 tensor op."""
+    import struct
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+class SurvLossFn(Function):
+    """Discrete-time survival loss of f32 logits [N, M] (losses/nll_surv.py, losses/cross_entropy_surv.py), one HIP launch per
+    direction.  kind: K.SURV_NLL / K.SURV_CE.  Returns a 0-d tensor for "mean" / "sum", else the per-row losses ([N] for NLL,
+    [N, 1] for CE, as the reference's gather keeps the dim).  Gradients flow to the logits only; the backward recomputes from the
+    logits (nothing but the inputs is saved)."""
+
+    @staticmethod
+    def forward(ctx, logits, event_times, censoring, kind, eps, alpha, reduction):
+        N = logits.shape[0]
+        # clamp bounds and the alpha weights as f32 scalars (hazards.clamp(min=eps, max=1.0 - eps), (1 - alpha) * neg_l)
+        cfg = (kind, _f32(eps), _f32(1.0 - eps), _f32(1.0 - alpha), _f32(alpha))
+        per_row = reduction not in ("mean", "sum")
+        coef = 1.0 / N if reduction == "mean" else 1.0
+        if per_row:
+            rows = torch.empty((N, 1) if kind == K.SURV_CE else (N,), device=logits.device, dtype=f32)
+            K.surv_loss_fwd(logits, event_times, censoring, *cfg, coef, None, rows)
+            res = rows
+        else:
+            out = torch.empty((1,), device=logits.device, dtype=f32)
+            K.surv_loss_fwd(logits, event_times, censoring, *cfg, coef, out, None)
+            res = out.reshape(())
+        ctx.save_for_backward(logits, event_times, censoring)
+        ctx.cfg, ctx.gcoef = cfg, (1.0 if per_row else coef)
+        return res
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, event_times, censoring = ctx.saved_tensors
+        dx = K.surv_loss_bwd(logits, event_times, censoring, *ctx.cfg, g, ctx.gcoef)
+        return dx, None, None, None, None, None, None

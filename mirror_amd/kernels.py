@@ -1817,3 +1817,85 @@ def adam(p, g, m, v, shadow, lr, b1, b2, eps, bc1, bc2, grad_scale=1.0, dev_stat
     _lib.call("mh_adam", _p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), lr, b1, b2, eps, bc1, bc2, grad_scale,
               _p(dev_state), ci, clo, chi, _p(counter), int(counter_add), 2 if tick == "early" else int(bool(tick)), *((0, 0) if hole is None else (int(hole[0]), int(hole[1]))),
               stream=_stream())
+
+
+# ----------------------------------------------------------------------------- survival step (train_survival.py)
+SURV_NLL, SURV_CE = 0, 1
+_SV_T = {torch.int32: 1, torch.int64: 2}
+_SV_C = {torch.bool: 0, torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3}
+
+
+def _surv_inputs(logits: torch.Tensor, event_times: torch.Tensor, censoring: torch.Tensor):
+    """(logits, event_times, censoring, dt_t, dt_c) checked for mh_surv_loss_*: logits [N, M] f32 with unit column stride,
+    event_times / censoring contiguous [N] of a supported dtype."""
+    _chk(logits, event_times, censoring)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise MirrorHipError(f"survival logits must be f32 [N, M], got {logits.dtype} {tuple(logits.shape)}")
+    if logits.stride(1) != 1 and logits.shape[1] > 1:
+        logits = logits.contiguous()
+    N = logits.shape[0]
+    if event_times.numel() != N or censoring.numel() != N:
+        raise MirrorHipError(f"event_times / censoring need {N} elements, got {event_times.numel()} / {censoring.numel()}")
+    if event_times.dtype not in _SV_T:
+        raise MirrorHipError(f"event_times must be int32 or int64, got {event_times.dtype}")
+    if censoring.dtype not in _SV_C:
+        raise MirrorHipError(f"censoring must be bool, uint8, int32, int64 or f32, got {censoring.dtype}")
+    t, c = event_times.reshape(-1).contiguous(), censoring.reshape(-1).contiguous()
+    return logits, t, c, _SV_T[t.dtype], _SV_C[c.dtype]
+
+
+def _ld(logits: torch.Tensor) -> int:
+    return logits.stride(0) if logits.shape[0] > 1 else logits.shape[1]
+
+
+def surv_loss_fwd(logits, event_times, censoring, kind: int, lo: float, hi: float, w_all: float, w_unc: float, coef: float,
+                  out: Optional[torch.Tensor], rows: Optional[torch.Tensor]) -> None:
+    """out [1] = coef * sum of the per-row losses (stored); rows [N] (optional) = the per-row losses."""
+    logits, t, c, dt_t, dt_c = _surv_inputs(logits, event_times, censoring)
+    N, M = logits.shape
+    _chk(out, rows)
+    assert out is None or (out.dtype == torch.float32 and out.numel() >= 1)
+    assert rows is None or (rows.dtype == torch.float32 and rows.is_contiguous() and rows.numel() == N)
+    _lib.call("mh_surv_loss_fwd", _p(logits), _ld(logits), _p(t), dt_t, _p(c), dt_c, N, M, kind, lo, hi, w_all, w_unc, coef,
+              _p(rows), _p(out), stream=_stream())
+
+
+def surv_loss_bwd(logits, event_times, censoring, kind: int, lo: float, hi: float, w_all: float, w_unc: float, g: torch.Tensor,
+                  gcoef: float) -> torch.Tensor:
+    """dlogits [N, M] f32 for the upstream gcoef * g (g: one element, or one per row)."""
+    logits, t, c, dt_t, dt_c = _surv_inputs(logits, event_times, censoring)
+    N, M = logits.shape
+    _chk(g)
+    g = g.reshape(-1).contiguous().float()
+    if g.numel() not in (1, N):
+        raise MirrorHipError(f"survival loss upstream gradient must have 1 or {N} elements, got {g.numel()}")
+    dx = torch.empty((N, M), device=logits.device, dtype=torch.float32)
+    _lib.call("mh_surv_loss_bwd", _p(logits), _ld(logits), _p(t), dt_t, _p(c), dt_c, N, M, kind, lo, hi, w_all, w_unc, _p(g),
+              int(g.numel() == N and N > 1), gcoef, _p(dx), stream=_stream())
+    return dx
+
+
+def surv_risk(logits: torch.Tensor) -> torch.Tensor:
+    """-sum_j cumprod(1 - sigmoid(logits), 1)[:, j] as f32 [N]."""
+    _chk(logits)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise MirrorHipError(f"risk_scores needs f32 [N, M] logits, got {logits.dtype} {tuple(logits.shape)}")
+    if logits.stride(1) != 1 and logits.shape[1] > 1:
+        logits = logits.contiguous()
+    N, M = logits.shape
+    risk = torch.empty((N,), device=logits.device, dtype=torch.float32)
+    _lib.call("mh_surv_risk", _p(logits), _ld(logits), N, M, _p(risk), stream=_stream())
+    return risk
+
+
+def cindex_counts(event_u8: torch.Tensor, time_f64: torch.Tensor, est_f32: torch.Tensor, tied_tol: float) -> torch.Tensor:
+    """int64 [5] {concordant, discordant, tied_risk, tied_time, comparable} on the device (no sync)."""
+    _chk(event_u8, time_f64, est_f32)
+    n = event_u8.numel()
+    assert event_u8.dtype == torch.uint8 and time_f64.dtype == torch.float64 and est_f32.dtype == torch.float32
+    assert event_u8.is_contiguous() and time_f64.is_contiguous() and est_f32.is_contiguous()
+    if time_f64.numel() != n or est_f32.numel() != n:
+        raise MirrorHipError(f"concordance inputs differ in length: {n}, {time_f64.numel()}, {est_f32.numel()}")
+    counts = torch.empty((5,), device=event_u8.device, dtype=torch.int64)
+    _lib.call("mh_cindex_counts", _p(event_u8), _p(time_f64), _p(est_f32), n, float(tied_tol), _p(counts), stream=_stream())
+    return counts

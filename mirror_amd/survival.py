@@ -1,0 +1,46 @@
+"""Survival validation metrics of train_survival.py on HIP kernels: the risk score of :1431-1433 and the censored concordance
+index of :1460-1465 (`sksurv.metrics.concordance_index_censored`, restated from its documented definition; sksurv is not a
+dependency).  Both take device tensors."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import kernels as K
+
+__all__ = ["concordance_index_censored", "risk_scores"]
+
+
+def risk_scores(logits: torch.Tensor) -> torch.Tensor:
+    """-sum(cumprod(1 - sigmoid(logits), dim=1), dim=1) of f32 logits [N, M] as f32 [N] (train_survival.py:1431-1433)."""
+    return K.surv_risk(logits)
+
+
+def concordance_index_censored(event_indicator: torch.Tensor, event_time: torch.Tensor, estimate: torch.Tensor, tied_tol: float = 1e-8):
+    """Harrell's concordance index for right-censored data, sksurv's 5-tuple (cindex, concordant, discordant, tied_risk, tied_time).
+
+    Pair (i, j) is comparable when sample i has an event and j outlives it (time[j] > time[i], or the same time with j censored);
+    it is tied when |estimate[j] - estimate[i]| <= tied_tol (in f32), concordant when not tied and estimate[i] > estimate[j],
+    discordant otherwise.  cindex = (concordant + 0.5 * tied_risk) / comparable.  The counts are computed on the device (one
+    launch, integer atomics) and read back with one sync; `event_time` is converted to f64 and `estimate` to f32 on the device.
+    Raises ValueError when every sample is censored or when no pair is comparable (where sksurv raises, and also where it would
+    return 0 / 0)."""
+    n = event_indicator.numel()
+    if event_time.numel() != n or estimate.numel() != n:
+        raise ValueError(f"event_indicator, event_time and estimate differ in length: {n}, {event_time.numel()}, {estimate.numel()}")
+    if n == 0:
+        raise ValueError("concordance_index_censored: empty input")
+    if estimate.is_complex() or not (estimate.is_floating_point() or estimate.dtype in (torch.int32, torch.int64)):
+        raise ValueError(f"estimate must be real-valued, got {estimate.dtype}")
+    K._chk(event_indicator, event_time, estimate)
+    ev = event_indicator.reshape(-1)
+    ev = (ev if ev.dtype == torch.bool else ev != 0).contiguous().view(torch.uint8)
+    counts = K.cindex_counts(ev, event_time.reshape(-1).to(torch.float64).contiguous(),
+                             estimate.reshape(-1).to(torch.float32).contiguous(), tied_tol)
+    con, dis, tie, ttime, comp = (np.int64(v) for v in counts.cpu().numpy())
+    if comp == 0:
+        if not bool(ev.any()):
+            raise ValueError("All samples are censored")
+        raise ValueError("Data has no comparable pairs, cannot estimate concordance index.")
+    cindex = np.float64((con + 0.5 * tie) / comp)
+    return cindex, con, dis, tie, ttime
