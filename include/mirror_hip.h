@@ -723,6 +723,39 @@ int mh_surv_risk(const float* logits, int64_t ld, int N, int M, float* risk, mh_
 int mh_cindex_counts(const uint8_t* event, const double* time, const float* estimate, int64_t n, float tied_tol, int64_t* counts,
                      mh_stream s);
 
+/* ---------------------------------------------------------------- downstream subtyping step (train_subtyping.py, v120)
+ * logits / scores [N x C] f32, row stride ld (the f32 output of mirror_classifier, models/mirror.py:667-707); labels [N] int32 /
+ * int64 read through dt_l (MH_SV_I32 / MH_SV_I64 of the survival block).  Every entry point is deterministic (no float atomics:
+ * fixed-order sums in one block, integer atomics for counts) and graph capturable; nothing is allocated. */
+#define MH_CLS_RED_NONE 0   /* torch's Reduction enum: "none" */
+#define MH_CLS_RED_MEAN 1   /* "mean" */
+#define MH_CLS_RED_SUM 2    /* "sum" */
+/* Cross-entropy with label smoothing s, per row: loss_r = (1 - s) (lse_r - x[r, y_r]) + s (lse_r - mean_c x[r, c]), lse_r =
+ * logsumexp(x[r, :]) (timm's LabelSmoothingCrossEntropy, train_subtyping.py:984; nn.CrossEntropyLoss(label_smoothing=s,
+ * ignore_index, reduction), :986 / :990).  A row whose label equals ignore_index has loss 0 and is not counted; a row whose label
+ * is otherwise outside [0, C) has loss NaN (torch raises / device-asserts there).  row_loss [N]: the per-row losses (nullable
+ * unless mode = MH_CLS_RED_NONE); out[0] (mean / sum; STORED, not accumulated) = the sum of the rows in a fixed order, divided
+ * by the number of non-ignored rows for MH_CLS_RED_MEAN (NaN when every row is ignored, as torch).  One block, one launch. */
+int mh_cls_ce_fwd(const float* logits, int64_t ld, const void* labels, int dt_l, int N, int C, float smoothing, int64_t ignore_index,
+                  float* row_loss, float* out, int mode, mh_stream s);
+/* dlogits [N x C] contiguous: dx[r, c] = w_r (softmax(x_r)[c] - (1 - s) [c == y_r] - s / C), recomputed from the logits; w_r =
+ * g[r] (MH_CLS_RED_NONE), g[0] (SUM) or g[0] / #non-ignored rows (MEAN); 0 for ignored rows, NaN for out-of-range labels. */
+int mh_cls_ce_bwd(const float* logits, int64_t ld, const void* labels, int dt_l, int N, int C, float smoothing, int64_t ignore_index,
+                  const float* g, int mode, float* dlogits, mh_stream s);
+/* Confusion counts behind top-1 accuracy (timm.utils.accuracy, train_subtyping.py:1390) and MulticlassF1Score (:1358-1360, :1392):
+ * conf [C x C] int64, indexed [label, prediction], ACCUMULATED (the caller zeroes it).  input: f32 scores [N x C] with row stride
+ * ld (dt_in = MH_SV_F32; the prediction is the first maximum of the row, or its first NaN, as torch.argmax) or predicted labels
+ * [N] (dt_in = MH_SV_I32 / MH_SV_I64; ld ignored).  A row whose label or prediction lies outside [0, C) leaves conf alone and adds
+ * 1 to bad[0] (int64, accumulated).  An int32 LDS copy of conf per block when C * C <= 4096, integer atomics. */
+int mh_cls_confusion(const void* input, int64_t ld, int dt_in, const void* labels, int dt_l, int N, int C, int64_t* conf, int64_t* bad,
+                     mh_stream s);
+/* One-vs-rest AUROC of torcheval's MulticlassAUROC (train_subtyping.py:1355-1357, :1391, :1419-1422) as exact integer pair counts:
+ * counts [C x 4] int64 = {U2_c, P_c, Q_c, NaN_c}, zeroed on s by this call.  For class c the positives are the rows with
+ * labels == c, the negatives all others (out-of-range labels included) and the score is the raw column scores[:, c];
+ * U2_c = 2 #{(i pos, j neg): s_i > s_j} + #{s_i == s_j}, so AUROC_c = U2_c / (2 P_c Q_c); NaN_c = the NaN scores in column c
+ * (their pairs add nothing).  labels int64 [N].  O(N^2 C) pairs through LDS; 1 <= N <= 2^20, 2 <= C <= 1024. */
+int mh_auroc_counts(const float* scores, int64_t ld, const int64_t* labels, int N, int C, int64_t* counts, mh_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,10 @@ _SIGS = {
     "mh_surv_loss_bwd": [P, L, P, I, P, I, I, I, I, F, F, F, F, P, I, F, P],
     "mh_surv_risk": [P, L, I, I, P],
     "mh_cindex_counts": [P, P, P, L, F, P],
+    "mh_cls_ce_fwd": [P, L, P, I, I, I, F, L, P, P, I],
+    "mh_cls_ce_bwd": [P, L, P, I, I, I, F, L, P, I, P],
+    "mh_cls_confusion": [P, L, I, P, I, I, I, P, P],
+    "mh_auroc_counts": [P, L, P, I, I, P],
 }
 EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "mh_gemm_select_pp", "mh_gemm_variant_name", "mh_device_ok", "mh_nys_attn3_ws_floats", "mh_rna_block_workspace_bytes",
                                  "mh_gemm_workspace_bytes", "mh_layernorm_bwd_workspace_bytes", "mh_nys_attn3_workspace_bytes",
@@ -201,7 +205,7 @@ _lib = None
 # The ABI generation this binding was written against (mh_version() of csrc/errors.cpp).  _SIGS above restates the argument lists of
 # include/mirror_hip.h by hand: a library built from another generation would be called with shifted arguments (a stream where a
 # counter belongs) and corrupt device memory silently, so load() refuses anything but this exact number.
-ABI_VERSION = 119
+ABI_VERSION = 120
 
 
 class MirrorHipError(RuntimeError):

@@ -2885,3 +2885,33 @@ class SurvLossFn(Function):
         logits, event_times, censoring = ctx.saved_tensors
         dx = K.surv_loss_bwd(logits, event_times, censoring, *ctx.cfg, g, ctx.gcoef)
         return dx, None, None, None, None, None, None
+
+
+class ClsCELossFn(Function):
+    """Cross-entropy with label smoothing of f32 logits [N, C] against integer labels [N] (timm's LabelSmoothingCrossEntropy,
+    nn.CrossEntropyLoss(ignore_index, reduction, label_smoothing)), one HIP launch per direction.  Returns a 0-d tensor for
+    "mean" / "sum", else the per-row losses [N].  Gradients flow to the logits only; the backward recomputes from the logits and
+    the labels, which is all that is saved."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, smoothing, ignore_index, reduction):
+        N = logits.shape[0]
+        mode = K.CLS_RED[reduction]
+        labels = K.cls_labels(labels, logits.device, N)
+        cfg = (_f32(smoothing), int(ignore_index), mode)
+        if mode == K.CLS_RED["none"]:
+            res = torch.empty((N,), device=logits.device, dtype=f32)
+            K.cls_ce_fwd(logits, labels, cfg[0], cfg[1], mode, res, None)
+        else:
+            out = torch.empty((1,), device=logits.device, dtype=f32)
+            K.cls_ce_fwd(logits, labels, cfg[0], cfg[1], mode, None, out)
+            res = out.reshape(())
+        ctx.save_for_backward(logits, labels)
+        ctx.cfg = cfg
+        return res
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels = ctx.saved_tensors
+        s, ignore_index, mode = ctx.cfg
+        return K.cls_ce_bwd(logits, labels, s, ignore_index, g, mode), None, None, None, None

@@ -1899,3 +1899,97 @@ def cindex_counts(event_u8: torch.Tensor, time_f64: torch.Tensor, est_f32: torch
     counts = torch.empty((5,), device=event_u8.device, dtype=torch.int64)
     _lib.call("mh_cindex_counts", _p(event_u8), _p(time_f64), _p(est_f32), n, float(tied_tol), _p(counts), stream=_stream())
     return counts
+
+
+# ----------------------------------------------------------------------------- subtyping step (train_subtyping.py)
+CLS_RED = {"none": 0, "mean": 1, "sum": 2}
+NO_IGNORE = -(1 << 63)          # ignore_index that no int32 label can equal (timm's loss has none)
+
+
+def cls_labels(labels: torch.Tensor, device: torch.device, N: int) -> torch.Tensor:
+    """Integer labels [N] as a contiguous int32 / int64 tensor on `device` (host labels are copied without blocking)."""
+    if labels.dtype not in _SV_T:
+        raise MirrorHipError(f"labels must be int32 or int64, got {labels.dtype}")
+    if labels.numel() != N or labels.dim() > 1:
+        raise MirrorHipError(f"labels must be [{N}], got {tuple(labels.shape)}")
+    if not labels.is_cuda:
+        labels = labels.to(device, non_blocking=True)
+    return labels.reshape(-1).contiguous()
+
+
+def _cls_logits(logits: torch.Tensor) -> torch.Tensor:
+    _chk(logits)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise MirrorHipError(f"classification logits must be f32 [N, C], got {logits.dtype} {tuple(logits.shape)}")
+    if logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise MirrorHipError(f"classification logits must be non-empty, got {tuple(logits.shape)}")
+    if logits.stride(1) != 1 and logits.shape[1] > 1:
+        logits = logits.contiguous()
+    return logits
+
+
+def cls_ce_fwd(logits, labels, smoothing: float, ignore_index: int, mode: int, rows: Optional[torch.Tensor],
+               out: Optional[torch.Tensor]) -> None:
+    """rows [N] (optional unless mode is "none") = per-row losses; out [1] = their sum, or mean over the non-ignored rows."""
+    logits = _cls_logits(logits)
+    N, C = logits.shape
+    t = cls_labels(labels, logits.device, N)
+    _chk(out, rows)
+    assert out is None or (out.dtype == torch.float32 and out.numel() >= 1)
+    assert rows is None or (rows.dtype == torch.float32 and rows.is_contiguous() and rows.numel() == N)
+    _lib.call("mh_cls_ce_fwd", _p(logits), _ld(logits), _p(t), _SV_T[t.dtype], N, C, smoothing, ignore_index, _p(rows), _p(out), mode,
+              stream=_stream())
+
+
+def cls_ce_bwd(logits, labels, smoothing: float, ignore_index: int, g: torch.Tensor, mode: int) -> torch.Tensor:
+    """dlogits [N, C] f32 for the upstream g (one element, or one per row for mode "none")."""
+    logits = _cls_logits(logits)
+    N, C = logits.shape
+    t = cls_labels(labels, logits.device, N)
+    _chk(g)
+    g = g.reshape(-1).contiguous().float()
+    if g.numel() != (N if mode == CLS_RED["none"] else 1):
+        raise MirrorHipError(f"cross-entropy upstream gradient has {g.numel()} elements for N = {N}, mode {mode}")
+    dx = torch.empty((N, C), device=logits.device, dtype=torch.float32)
+    _lib.call("mh_cls_ce_bwd", _p(logits), _ld(logits), _p(t), _SV_T[t.dtype], N, C, smoothing, ignore_index, _p(g), mode, _p(dx),
+              stream=_stream())
+    return dx
+
+
+def cls_confusion(inp: torch.Tensor, labels: torch.Tensor, conf: torch.Tensor, bad: torch.Tensor) -> None:
+    """conf [C, C] int64 += counts of (label, prediction) pairs; bad [1] int64 += rows with a label or prediction outside [0, C).
+    inp: f32 scores [N, C] (prediction = first argmax) or int32 / int64 predicted labels [N]."""
+    _chk(inp, conf, bad)
+    C = conf.shape[0]
+    assert conf.dtype == torch.int64 and conf.is_contiguous() and tuple(conf.shape) == (C, C)
+    assert bad.dtype == torch.int64 and bad.numel() >= 1
+    if inp.dim() == 2:
+        if inp.dtype != torch.float32 or inp.shape[1] != C:
+            raise MirrorHipError(f"scores must be f32 [N, {C}], got {inp.dtype} {tuple(inp.shape)}")
+        if inp.stride(1) != 1 and C > 1:
+            inp = inp.contiguous()
+        dt_in, ld = 3, _ld(inp)
+    elif inp.dim() == 1 and inp.dtype in _SV_T:
+        inp, dt_in, ld = inp.contiguous(), _SV_T[inp.dtype], 0
+    else:
+        raise MirrorHipError(f"input must be f32 scores [N, C] or integer predictions [N], got {inp.dtype} {tuple(inp.shape)}")
+    N = inp.shape[0]
+    if N == 0:
+        return
+    t = cls_labels(labels, inp.device, N)
+    _lib.call("mh_cls_confusion", _p(inp), ld, dt_in, _p(t), _SV_T[t.dtype], N, C, _p(conf), _p(bad), stream=_stream())
+
+
+def auroc_counts(scores: torch.Tensor, labels_i64: torch.Tensor) -> torch.Tensor:
+    """int64 [C, 4] {U2, P, Q, NaN count} per class on the device (no sync); scores f32 [N, C], labels int64 [N] on the device."""
+    _chk(scores, labels_i64)
+    assert scores.dim() == 2 and scores.dtype == torch.float32 and labels_i64.dtype == torch.int64
+    if scores.stride(1) != 1:
+        scores = scores.contiguous()
+    labels_i64 = labels_i64.contiguous()
+    N, C = scores.shape
+    if not (1 <= N <= (1 << 20)) or not (2 <= C <= 1024) or labels_i64.numel() != N:
+        raise MirrorHipError(f"auroc_counts: N = {N} (1..2^20), C = {C} (2..1024), {labels_i64.numel()} labels")
+    counts = torch.empty((C, 4), device=scores.device, dtype=torch.int64)
+    _lib.call("mh_auroc_counts", _p(scores), _ld(scores), _p(labels_i64), N, C, _p(counts), stream=_stream())
+    return counts
