@@ -684,6 +684,32 @@ int mh_adam(float* p, const float* g, float* m, float* v, void* shadow_bf16, int
             float clamp_lo, float clamp_hi, int64_t* counter, int64_t counter_add, int tick, int64_t hole_lo, int64_t hole_hi,
             mh_stream s);
 
+/* ---------------------------------------------------------------- model EMA (timm ModelEmaV3; added to v120)
+ * train_mirror.py:787-799 (ModelEmaV3(model, decay, use_warmup)), :1283-1284 (model_ema.update(model, step=num_updates)); the same in
+ * train_subtyping.py:867-879, :1293 and train_survival.py:879-891, :1322.  The decay of step t is timm's get_decay(t), computed on the
+ * device in double: s = max(0, t - update_after_step - 1); s == 0 -> 0 (the update copies); use_warmup -> max(min(1 - (1 + s /
+ * warmup_gamma)^-warmup_power, decay), min_decay); else decay.  The lerp weight 1 - decay is rounded to f32 once and applied in
+ * torch.lerp's form (w < 0.5 ? e + w (p - e) : p - (p - e)(1 - w)); w = 1 is an exact copy.
+ * mh_adam_ema: mh_adam (every argument keeps its meaning) plus ema (f32, laid out like p, 16-B aligned): each updated element's
+ * final value (after the clamp) is lerped into ema in the same pass (+8 B per parameter), with t = dev_state[0] after the tick
+ * (dev_state is required).  Both launches of a two-launch step run as `adam_ema_kernel`.
+ * The settings travel as a host struct, read at launch (kernel arguments: a captured graph keeps them). */
+typedef struct {
+    double decay, min_decay, warmup_gamma, warmup_power;   /* timm's ModelEmaV3 settings (warmup_gamma > 0) */
+    int64_t update_after_step;
+    int use_warmup;
+} mh_ema_cfg;
+int mh_adam_ema(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, float beta1, float beta2,
+                float eps, float bias_c1, float bias_c2, float grad_scale, float* dev_state, int64_t clamp_index, float clamp_lo,
+                float clamp_hi, int64_t* counter, int64_t counter_add, int tick, int64_t hole_lo, int64_t hole_hi, float* ema,
+                const mh_ema_cfg* cfg, mh_stream s);
+/* ema[off_i + j] = lerp(ema[off_i + j], src_i[j], w) for j < n_i, for the nseg rows {off_i, (int64) src_i, n_i} of the device
+ * table (int64 [nseg, 3]; src_i: f32 device pointers; the ranges must not overlap).  One workgroup per row: split long tensors
+ * into rows of a few 10^4 elements (a multiple of 4) for balance.  w = weight (in [0, 1]) when dev_state is NULL (cfg unused,
+ * may be NULL), else the decay rule of cfg applied to t = dev_state[0] (graph-capturable). */
+int mh_ema_update_many(float* ema, const int64_t* table, int nseg, float weight, const float* dev_state, const mh_ema_cfg* cfg,
+                       mh_stream s);
+
 /* clip-grad "norm" mode (train_mirror.py:1206-1230): dev_state[5] = ||grad_scale * g||_2, dev_state[4] =
  * min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0); scratch1 = one device float. */
 int mh_grad_clip(const float* g, int64_t n, float grad_scale, float max_norm, float* scratch1, float* dev_state, mh_stream s);

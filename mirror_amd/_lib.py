@@ -59,6 +59,12 @@ class GemmDesc(C.Structure):
 P, I, L, F, U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
 
 
+class EmaCfg(C.Structure):
+    """mh_ema_cfg of include/mirror_hip.h (field order = the header's)."""
+    _fields_ = [("decay", C.c_double), ("min_decay", C.c_double), ("warmup_gamma", C.c_double), ("warmup_power", C.c_double),
+                ("update_after_step", C.c_int64), ("use_warmup", C.c_int32)]
+
+
 class LossTermsDesc(C.Structure):
     """mh_loss_terms of include/mirror_hip.h (field order = the header's)."""
     _fields_ = [
@@ -182,6 +188,8 @@ _SIGS = {
     "mh_rownorm_": [P, P, I, I, F],
     "mh_clamp_": [P, L, F, F],
     "mh_adam": [P, P, P, P, P, L, F, F, F, F, F, F, F, P, L, F, F, P, L, I, L, L],
+    "mh_adam_ema": [P, P, P, P, P, L, F, F, F, F, F, F, F, P, L, F, F, P, L, I, L, L, P, P],
+    "mh_ema_update_many": [P, P, I, F, P, P],
     "mh_grad_clip": [P, L, F, F, P, P],
     "mh_rna_block_fwd": [C.POINTER(RnaBlockDesc)],
     "mh_rna_block_bwd": [C.POINTER(RnaBlockDesc)],
@@ -254,7 +262,9 @@ def load() -> C.CDLL:
     lib.mh_rna_block_workspace_bytes.restype = C.c_int64
     lib.mh_rna_block_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     for name, sig in _SIGS.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:      # entry points added within a generation (no argument list changed): an older build lacks them
+            raise MirrorHipError(f"{LIB_PATH} lacks {name}: rebuild the library (`make -C mirror_amd/csrc`, or __graft_entry__.build())")
         fn.argtypes = list(sig) + [C.c_void_p]
         fn.restype = C.c_int
     _lib = lib

@@ -4,6 +4,8 @@ Mirrors what train_mirror.py does after every epoch (:1053-1062): `saver.save_ch
 timm's CheckpointSaver built at :920-930 (`decreasing=True` for a loss metric, `max_history=args.checkpoint_hist`): the latest
 state always goes to `last.pth.tar`, the `max_history` best epochs are kept as `checkpoint-<epoch>.pth.tar`, the best one
 is also copied to `model_best.pth.tar`, and (best_metric, best_epoch) comes back.  Host logic only — no kernels.
+With --model-ema (:920-930 hands `model_ema` to the saver) the files also hold `state_dict_ema`; `load_checkpoint` is timm's, as
+train_mirror.py:797 calls it to reload the EMA weights (`use_ema=True`).
 """
 from __future__ import annotations
 
@@ -17,8 +19,9 @@ import torch
 
 class CheckpointSaver:
     def __init__(self, model: torch.nn.Module, engine=None, *, args=None, checkpoint_dir: str = "", decreasing: bool = True,
-                 max_history: int = 10, checkpoint_prefix: str = "checkpoint", extension: str = ".pth.tar"):
-        self.model, self.engine, self.args = model, engine, args
+                 max_history: int = 10, checkpoint_prefix: str = "checkpoint", extension: str = ".pth.tar", model_ema=None):
+        """model_ema: a mirror_amd.ema.ModelEmaV3 whose weights go to `state_dict_ema` (keys `module.<name>`, as timm writes them)."""
+        self.model, self.engine, self.args, self.model_ema = model, engine, args, model_ema
         self.checkpoint_dir, self.prefix, self.ext = checkpoint_dir, checkpoint_prefix, extension
         self.decreasing, self.max_history = decreasing, max_history
         self.files: List[Tuple[str, float]] = []          # (path, metric), best first
@@ -33,6 +36,8 @@ class CheckpointSaver:
                  "version": 2}
         if self.engine is not None:
             state["optimizer"] = self.engine.state_dict()
+        if self.model_ema is not None:
+            state["state_dict_ema"] = {k: v.detach().cpu().clone() for k, v in self.model_ema.state_dict().items()}
         if self.args is not None:
             # timm pickles the argparse.Namespace itself (train_mirror.py:920-930); a plain dict holds the same information and
             # opens under torch.load's default weights_only=True
@@ -99,3 +104,30 @@ def resume_checkpoint(model: torch.nn.Module, path: str, engine=None, trusted: b
     if engine is not None:
         engine.sync_shadows()
     return None
+
+
+def _clean_state_dict(sd: dict) -> dict:
+    return {k[7:] if k.startswith("module.") else k: v for k, v in sd.items()}
+
+
+def select_state_dict(ckpt, use_ema: bool = False) -> dict:
+    """timm.models.load_state_dict's choice of weights inside a checkpoint: with use_ema `state_dict_ema`, then `model_ema`, then
+    `state_dict`, then `model`; a bare state dict as it is.  The `module.` prefix of DDP / EMA-wrapped keys is stripped."""
+    key = ""
+    if isinstance(ckpt, dict):
+        if use_ema and ckpt.get("state_dict_ema") is not None:
+            key = "state_dict_ema"
+        elif use_ema and ckpt.get("model_ema") is not None:
+            key = "model_ema"
+        elif "state_dict" in ckpt:
+            key = "state_dict"
+        elif "model" in ckpt:
+            key = "model"
+    return _clean_state_dict(ckpt[key] if key else ckpt)
+
+
+def load_checkpoint(model: torch.nn.Module, path: str, use_ema: bool = False, strict: bool = True, trusted: bool = False):
+    """timm.models.load_checkpoint (train_mirror.py:797: `load_checkpoint(model_ema.module, args.resume, use_ema=True)`): the
+    weights of `path` (files of this package's saver or of timm's) into `model`; returns load_state_dict's incompatible keys.  A
+    TrainEngine's model needs `engine.sync_shadows()` afterwards; a ModelEmaV3's `.module` refreshes its bf16 copies itself."""
+    return model.load_state_dict(select_state_dict(load_checkpoint_file(path, trusted), use_ema), strict=strict)

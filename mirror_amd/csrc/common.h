@@ -152,3 +152,20 @@ static inline int mh_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 #define MH_DISPATCH_DT(dt, T, ...)                              \
     if ((dt) == MH_F32) { using T = float; __VA_ARGS__; }       \
     else { using T = bf16_t; __VA_ARGS__; }
+
+// ---- model EMA (timm ModelEmaV3, train_mirror.py:787-799, :1284): the decay schedule and the lerp, shared by mh_adam_ema and
+// mh_ema_update_many.  ema_weight restates ModelEmaV3.get_decay(step) in double and returns the lerp weight 1 - decay rounded to
+// f32 once, as torch rounds the Python scalar that timm hands to _foreach_lerp_.
+__device__ inline float ema_weight(const mh_ema_cfg& c, double t) {
+    const double step = fmax(0.0, t - (double)c.update_after_step - 1.0);
+    if (step <= 0.0) return 1.f;                              // the first update copies the model
+    double d = c.decay;
+    if (c.use_warmup) d = fmax(fmin(1.0 - pow(1.0 + step / c.warmup_gamma, -c.warmup_power), c.decay), c.min_decay);
+    return (float)(1.0 - d);
+}
+// torch.lerp(e, p, w) in torch's two-sided form; w = 1 (the first update) is an exact copy
+__device__ __forceinline__ float ema_lerp(float e, float p, float w) {
+    if (w >= 1.f) return p;
+    const float d = p - e;
+    return w < 0.5f ? e + w * d : p - d * (1.f - w);
+}

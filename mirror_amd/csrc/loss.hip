@@ -471,12 +471,14 @@ extern "C" int mh_clamp_(float* x, int64_t n, float lo, float hi, mh_stream s) {
     return MH_OK;
 }
 
-// torch.optim.Adam semantics (no weight decay, no amsgrad): 4 floats per thread, 16-B accesses (HBM-bound: 28 B/param)
+// torch.optim.Adam semantics (no weight decay, no amsgrad): 4 floats per thread, 16-B accesses (HBM-bound: 28 B/param).
+// EMA = true: the final parameter value (after the clamp) is also lerped into `ema` with weight `ew` (+8 B/param: mh_adam_ema)
+template <bool EMA = false>
 __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, bf16_t* __restrict__ shadow, long n, float lr, float b1,
                                                    float b2, float eps, float bc1, float bc2, float gscale,
                                                    const float* __restrict__ state, long clamp_i, float clamp_lo, float clamp_hi,
-                                                   long hole_lo4, long hole_hi4) {
+                                                   long hole_lo4, long hole_hi4, float* __restrict__ ema = nullptr, float ew = 0.f) {
     // quads [hole_lo4, hole_hi4) are left alone: a range another launch of the same step has already updated (the RNA encoder's
     // parameters, whose gradients are complete 2 ms before the step's last one: TrainEngine's early update)
     if (state) {   // device-resident step state {t, 1 - b1^t, 1 - b2^t, lr, clip}: nothing step-dependent is a launch argument
@@ -508,6 +510,14 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __
         reinterpret_cast<float4*>(p)[q] = pp;
         reinterpret_cast<float4*>(m)[q] = mm;
         reinterpret_cast<float4*>(v)[q] = vv;
+        if constexpr (EMA) {
+            float4 ee = reinterpret_cast<float4*>(ema)[q];
+            ee.x = ema_lerp(ee.x, pp.x, ew);
+            ee.y = ema_lerp(ee.y, pp.y, ew);
+            ee.z = ema_lerp(ee.z, pp.z, ew);
+            ee.w = ema_lerp(ee.w, pp.w, ew);
+            reinterpret_cast<float4*>(ema)[q] = ee;
+        }
         if (shadow) {
             uint2 sh;
             sh.x = pack_bf2(pa[0], pa[1]);
@@ -524,6 +534,7 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __
         if (i == clamp_i) pn = fminf(fmaxf(pn, clamp_lo), clamp_hi);
         p[i] = pn;
         if (shadow) shadow[i] = f2bf(pn);
+        if constexpr (EMA) ema[i] = ema_lerp(ema[i], pn, ew);
     }
 }
 
@@ -537,6 +548,17 @@ __global__ __launch_bounds__(256) void adam_kernel(ADAM_ARGS_) {
 // the early launch of a two-launch step (a sub-range, beside the backward): same arithmetic under another name
 __global__ __launch_bounds__(256) void adam_range_kernel(ADAM_ARGS_) {
     adam_body(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2, gscale, state, clamp_i, clamp_lo, clamp_hi, hole_lo4, hole_hi4);
+}
+// Adam + model EMA in one pass (timm ModelEmaV3.update right behind optimizer.step, train_mirror.py:1254-1284): the EMA weight
+// 1 - decay(t) comes from the device step t = state[0] that the tick has just advanced, once per workgroup — nothing
+// step-dependent is a launch argument.  Launched under one name for both launches of a two-launch step (profiling tools that cut
+// traces at `adam_kernel` see no EMA step, which is never on the benched path)
+__global__ __launch_bounds__(256) void adam_ema_kernel(ADAM_ARGS_, float* __restrict__ ema, mh_ema_cfg cfg) {
+    __shared__ float ew_s;
+    if (threadIdx.x == 0) ew_s = ema_weight(cfg, (double)state[0]);
+    __syncthreads();
+    adam_body<true>(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2, gscale, state, clamp_i, clamp_lo, clamp_hi, hole_lo4, hole_hi4,
+                    ema, ew_s);
 }
 #undef ADAM_ARGS_
 
@@ -581,24 +603,44 @@ extern "C" int mh_grad_clip(const float* g, int64_t n, float grad_scale, float m
     return MH_OK;
 }
 
-extern "C" int mh_adam(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, float lr, float b1, float b2,
+static int adam_launch(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, float lr, float b1, float b2,
                        float eps, float bc1, float bc2, float gscale, float* dev_state, int64_t clamp_index, float clamp_lo,
-                       float clamp_hi, int64_t* counter, int64_t counter_add, int tick, int64_t hole_lo, int64_t hole_hi, mh_stream s) {
+                       float clamp_hi, int64_t* counter, int64_t counter_add, int tick, int64_t hole_lo, int64_t hole_hi, float* ema,
+                       const mh_ema_cfg* cfg, mh_stream s, const char* name) {
     if (n == 0) return MH_OK;
     MH_REQUIRE(((uintptr_t)p & 15) == 0 && ((uintptr_t)g & 15) == 0 && ((uintptr_t)m & 15) == 0 && ((uintptr_t)v & 15) == 0 &&
-                   ((uintptr_t)shadow & 7) == 0, "mh_adam: buffers must be 16-byte aligned");
-    MH_REQUIRE(clamp_index < n, "mh_adam: clamp_index %ld outside the %ld parameters", (long)clamp_index, (long)n);
+                   ((uintptr_t)shadow & 7) == 0, "%s: buffers must be 16-byte aligned", name);
+    MH_REQUIRE(clamp_index < n, "%s: clamp_index %ld outside the %ld parameters", name, (long)clamp_index, (long)n);
     MH_REQUIRE(hole_lo >= 0 && hole_lo <= hole_hi && hole_hi <= n && hole_lo % 4 == 0 && (hole_hi % 4 == 0 || hole_hi == hole_lo) &&
                    (clamp_index < hole_lo || clamp_index >= hole_hi || hole_lo == hole_hi),
-               "mh_adam: hole [%ld, %ld) must be quad-aligned, inside the %ld parameters and not hold the clamped one", (long)hole_lo, (long)hole_hi, (long)n);
+               "%s: hole [%ld, %ld) must be quad-aligned, inside the %ld parameters and not hold the clamped one", name, (long)hole_lo, (long)hole_hi, (long)n);
     if ((dev_state && tick) || counter)
         hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, tick ? dev_state : nullptr, b1, b2, (long long*)counter, (long long)counter_add);
     const long live = n - (hole_hi - hole_lo);
     if (live == 0) return MH_OK;
-#define ADAM_LAUNCH_(KERN) hipLaunchKernelGGL(KERN, dim3((unsigned)min((long)mh_cdiv(mh_cdiv(live, 4), 256), 8192L)), dim3(256), 0, (hipStream_t)s, p, g, m, v, (bf16_t*)shadow, (long)n, lr, b1, b2, eps, bc1, bc2, gscale, (const float*)dev_state, \
-                       clamp_index < 0 ? -1L : (long)clamp_index, clamp_lo, clamp_hi, (long)(hole_lo / 4), (long)(hole_hi / 4))
-    if (tick == 2) ADAM_LAUNCH_(adam_range_kernel); else ADAM_LAUNCH_(adam_kernel);
+#define ADAM_LAUNCH_(KERN, ...) hipLaunchKernelGGL(KERN, dim3((unsigned)min((long)mh_cdiv(mh_cdiv(live, 4), 256), 8192L)), dim3(256), 0, (hipStream_t)s, p, g, m, v, (bf16_t*)shadow, (long)n, lr, b1, b2, eps, bc1, bc2, gscale, (const float*)dev_state, \
+                       clamp_index < 0 ? -1L : (long)clamp_index, clamp_lo, clamp_hi, (long)(hole_lo / 4), (long)(hole_hi / 4) __VA_ARGS__)
+    if (ema) ADAM_LAUNCH_(adam_ema_kernel, , ema, *cfg);
+    else if (tick == 2) ADAM_LAUNCH_(adam_range_kernel); else ADAM_LAUNCH_(adam_kernel);
 #undef ADAM_LAUNCH_
-    MH_LAUNCH_CHECK("mh_adam");
+    MH_LAUNCH_CHECK(name);
     return MH_OK;
+}
+
+extern "C" int mh_adam(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, float lr, float b1, float b2,
+                       float eps, float bc1, float bc2, float gscale, float* dev_state, int64_t clamp_index, float clamp_lo,
+                       float clamp_hi, int64_t* counter, int64_t counter_add, int tick, int64_t hole_lo, int64_t hole_hi, mh_stream s) {
+    return adam_launch(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2, gscale, dev_state, clamp_index, clamp_lo, clamp_hi, counter,
+                       counter_add, tick, hole_lo, hole_hi, nullptr, nullptr, s, "mh_adam");
+}
+
+extern "C" int mh_adam_ema(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, float lr, float b1, float b2,
+                           float eps, float bc1, float bc2, float gscale, float* dev_state, int64_t clamp_index, float clamp_lo,
+                           float clamp_hi, int64_t* counter, int64_t counter_add, int tick, int64_t hole_lo, int64_t hole_hi, float* ema,
+                           const mh_ema_cfg* cfg, mh_stream s) {
+    MH_REQUIRE(ema && ((uintptr_t)ema & 15) == 0, "mh_adam_ema: the EMA buffer must be 16-byte aligned");
+    MH_REQUIRE(dev_state, "mh_adam_ema: the EMA decay follows the device step: dev_state is required");
+    MH_REQUIRE(cfg && cfg->warmup_gamma > 0.0, "mh_adam_ema: no settings, or warmup_gamma <= 0");
+    return adam_launch(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2, gscale, dev_state, clamp_index, clamp_lo, clamp_hi, counter,
+                       counter_add, tick, hole_lo, hole_hi, ema, cfg, s, "mh_adam_ema");
 }

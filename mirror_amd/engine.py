@@ -59,14 +59,18 @@ class TrainEngine:
                  precision: str = "bf16", wsi_mask_ratio: float = 0.75, rna_mask_ratio: float = 0.75,
                  bucket_mb: float = 25.0, process_group=None, graph: Optional[bool] = None,
                  clip_grad: Optional[float] = None, clip_mode: str = "norm", accum_steps: int = 1, seed: Optional[int] = None,
-                 snapshot_grads: bool = False, grad_reduce_dtype: str = "f32"):
+                 snapshot_grads: bool = False, grad_reduce_dtype: str = "f32", model_ema=None):
         """grad_reduce_dtype: "f32" (default: the f32 arena slices are all-reduced in place) or "bf16" (BASELINE config 5 /
         SURVEY.md §8e "bf16 grads optional": each bucket is rounded to bf16 for the wire — half the xGMI bytes — summed by
         RCCL in bf16 and widened back into the f32 arena; Adam still reads f32).
         seed: dropout (Philox) seed of this process; rank is added to it, as the reference's
         `utils.random_seed(args.seed, args.rank)` does (train_mirror.py:682).  Without it, a multi-rank engine folds its rank
         into whatever seed `Fn.manual_seed` last set, so that ranks never draw identical dropout masks.
-        snapshot_grads: keep a copy of the (reduced) gradient arena of the last update in `self.grad_snap` (tests)."""
+        snapshot_grads: keep a copy of the (reduced) gradient arena of the last update in `self.grad_snap` (tests).
+        model_ema: a mirror_amd.ema.ModelEmaV3 of `model` (train_mirror.py:787-799, :1283-1284).  Its arena takes the master arena's
+        layout and every update step lerps it inside the Adam launches (mh_adam_ema, decay from the device step t = the reference's
+        num_updates); parameters outside the arena (frozen ones) and f32 buffers follow in one mh_ema_update_many launch.  Its
+        `update(model, step=num_updates)` is then a checked no-op.  Not under the fp8 policy."""
         if precision not in POLICIES:
             raise ValueError(f"unknown precision {precision!r}")
         # timm's dispatch_clip_grad modes (train_mirror.py:1219-1229, --clip-mode): "norm" (the template's default: one fused
@@ -189,6 +193,33 @@ class TrainEngine:
             dist.broadcast(self.master, src=0, group=self.pg)  # DDP's parameter broadcast at wrap time
             self.sync_shadows()
             self._build_buckets(bucket_mb)
+        self.model_ema = None
+        if model_ema is not None:
+            self._attach_ema(model_ema)
+
+    def _attach_ema(self, ema) -> None:
+        if POLICIES[self.precision].fp8_fwd:
+            # the fp8 amax site tables are per engine and an EMA forward must not touch them
+            raise NotImplementedError("model EMA under the fp8 policy is not built")
+        from .ema import _unwrap
+        if _unwrap(self.model) is not self.model:
+            raise ValueError("TrainEngine drives the bare model: pass it, not a DDP wrapper")
+        self._ema_arena, self._ema_table, self._ema_rows = ema._attach(self)
+        self._ema_cfg = ema._cfg()
+        if self.world > 1:
+            # rank-identical, as the master is: rank 0's EMA (a fresh EMA is rank 0's model, which is what the master broadcast above held)
+            dist.broadcast(self._ema_arena, src=0, group=self.pg)
+        ema.module.precision = self.precision
+        self.model_ema = ema
+
+    def _ema_step(self) -> None:
+        """The EMA of everything mh_adam_ema did not cover (frozen parameters, f32 buffers, integer buffers), right behind it."""
+        ema = self.model_ema
+        if self._ema_rows:
+            K.ema_update_many(self._ema_arena, self._ema_table, self._ema_rows, dev_state=self._state, ema_cfg=self._ema_cfg)
+        for e, src in ema._engine_copies:
+            e.detach().copy_(src)
+        ema._touch()
 
     # ------------------------------------------------------------------ shadows
     def sync_shadows(self) -> None:
@@ -387,6 +418,8 @@ class TrainEngine:
                     self._g_src[k], self._g_ver[k] = t, t._version
             self._graph.replay()
             self.step_count += 1
+            if self.model_ema is not None:
+                self.model_ema._touch()          # the replay updated the EMA arena: its bf16 copies are stale
             # the replay ran Adam: the transposed copies trail it and the arena holds this step's gradients until the next
             # step's start — the Python flags of _step_body have to say so after a replay too (out-of-step backward)
             self._t_stale = self.shadow_t is not None and _TRANSPOSE_AT_START
@@ -501,7 +534,8 @@ class TrainEngine:
                         lo, hi = early
                         K.adam(self.master[lo:hi], self.grad[lo:hi], self.m[lo:hi], self.v[lo:hi],
                                None if self.shadow is None else self.shadow[lo:hi], self.lr, b1, b2, self.eps, 1.0, 1.0,
-                               grad_scale=1.0, dev_state=self._state, tick="early")
+                               grad_scale=1.0, dev_state=self._state, tick="early",
+                               **({} if self.model_ema is None else {"ema": self._ema_arena[lo:hi], "ema_cfg": self._ema_cfg}))
         finally:
             Fn._wgrad_queue = None
             Fn.set_grad_sink(None)
@@ -544,7 +578,8 @@ class TrainEngine:
                grad_scale=gs,                  # the DDP / accumulation average is folded into Adam
                dev_state=self._state,          # t, bias corrections, lr and the clip factor live on the device
                clamp=clamp, counter=base, counter_add=used,
-               tick=early is None, hole=early)     # the RNA encoder's range was updated (and t advanced) beside the WSI backward
+               tick=early is None, hole=early,     # the RNA encoder's range was updated (and t advanced) beside the WSI backward
+               **({} if self.model_ema is None else {"ema": self._ema_arena[:self.numel], "ema_cfg": self._ema_cfg}))
         if _TRANSPOSE_AT_START:
             self._t_stale = self.shadow_t is not None
         else:
@@ -553,6 +588,8 @@ class TrainEngine:
             K.clamp_(self._logit.data.reshape(1), 0.0, math.log(100.0))
             if self.shadow is not None:
                 K.cast(self._logit.data.reshape(1), bf16, out=Fn.shadow(self._logit, POLICIES[self.precision]).reshape(1))
+        if self.model_ema is not None:
+            self._ema_step()          # behind the clamp, as model_ema.update (:1284) follows it (:1255)
         if _TRANSPOSE_AT_START:
             self._zero_pending = True        # cleared by the next step, beside its forward (nobody reads the arena in between)
         else:
@@ -574,14 +611,18 @@ class TrainEngine:
     # ------------------------------------------------------------------ validation (train_mirror.py:1382-1526)
     LOSS_NAMES = ("loss", "alignment_loss", "wsi_retention_loss", "rna_retention_loss", "style_loss", "cluster_loss")
 
-    def validate(self, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], noise: Optional[Sequence[dict]] = None) -> "OrderedDict[str, float]":
+    def validate(self, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], noise: Optional[Sequence[dict]] = None,
+                 model: Optional[torch.nn.Module] = None) -> "OrderedDict[str, float]":
         """The reference's `validate()`: eval mode (dropout off, masking still on), no autograd, the six losses averaged
         over the loader weighted by batch size (utils.AverageMeter.update(loss, B)) and, under DDP, averaged over ranks
         (utils.reduce_tensor).  The running sums stay on the device: ONE host sync at the end instead of six `.item()`s
         per batch.  `noise[i]` optionally pins the random draws of batch i (parity tests).  The module's train / eval
-        mode is restored on return (the reference leaves it in eval and flips it back in train_one_epoch)."""
-        was_training = self.model.training
-        self.model.eval()
+        mode is restored on return (the reference leaves it in eval and flips it back in train_one_epoch).
+        model: another module to validate with this engine's loss and masking, e.g. `model_ema.module` (the EMA weights,
+        train_mirror.py:1022-1037); the engine's model by default."""
+        net = self.model if model is None else model
+        was_training = net.training
+        net.eval()
         acc = torch.zeros(7, device=self.device, dtype=torch.float64)        # 6 weighted sums + the sample count
         sites_before = Fn._fp8_state["sites"]
         if POLICIES[self.precision].fp8_fwd:
@@ -591,18 +632,18 @@ class TrainEngine:
                 for i, (wsi, rna) in enumerate(loader):
                     wsi = wsi.to(self.device, non_blocking=True)
                     rna = rna.to(self.device, non_blocking=True)
-                    self.model._align_gather = self._align_gather
+                    net._align_gather = self._align_gather
                     try:
-                        outs = self.model(wsi, rna, wsi_mask_ratio=self.wsi_mask_ratio, rna_mask_ratio=self.rna_mask_ratio,
-                                          noise=None if noise is None else noise[i])
+                        outs = net(wsi, rna, wsi_mask_ratio=self.wsi_mask_ratio, rna_mask_ratio=self.rna_mask_ratio,
+                                   noise=None if noise is None else noise[i])
                     finally:
-                        self.model._align_gather = None
+                        net._align_gather = None
                     losses = self.loss_fn(*outs)
                     b = float(wsi.shape[0])
                     acc[:6] += torch.stack([x.detach().reshape(()) for x in losses]).double() * b
                     acc[6] += b
         finally:
-            self.model.train(was_training)
+            net.train(was_training)
             Fn._fp8_state["sites"] = sites_before
         if self.world > 1:      # mean over ranks of every batch's loss == summed weighted sums / summed counts for equal batch sizes
             dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=self.pg)

@@ -1800,13 +1800,15 @@ def grad_clip(g: torch.Tensor, grad_scale: float, max_norm: float, dev_state: to
 
 def adam(p, g, m, v, shadow, lr, b1, b2, eps, bc1, bc2, grad_scale=1.0, dev_state: Optional[torch.Tensor] = None,
          clamp: Optional[tuple] = None, counter: Optional[torch.Tensor] = None, counter_add: int = 0, tick: bool = True,
-         hole: Optional[tuple] = None) -> None:
+         hole: Optional[tuple] = None, ema: Optional[torch.Tensor] = None, ema_cfg=None) -> None:
     """dev_state: optional f32[6] device tensor {t, 1-b1^t, 1-b2^t, lr, clip, |g|}; when given the step count / bias
     corrections / lr live on the device (advanced by the launch itself), lr, bc1, bc2 are ignored and the gradient is
     also scaled by dev_state[4] (the factor grad_clip left there, else 1).  clamp = (index, lo, hi): that one parameter is clamped
     behind its update (master and shadow); counter (int64[1]) += counter_add in the same launches.  tick=False: dev_state is read,
-    not advanced (tick="early": advanced, by the first launch of a two-launch step); hole = (lo, hi): those elements are left alone (the other launch of a two-launch step updates them)."""
-    _chk(p, g, m, v, shadow, dev_state, counter)
+    not advanced (tick="early": advanced, by the first launch of a two-launch step); hole = (lo, hi): those elements are left alone (the other launch of a two-launch step updates them).
+    ema (f32, p's size) + ema_cfg (_lib.EmaCfg, needs dev_state): mh_adam_ema — every updated element's final value is also lerped
+    into `ema` with timm's ModelEmaV3 decay of the device step, in the same pass."""
+    _chk(p, g, m, v, shadow, dev_state, counter, ema)
     assert counter is None or (counter.dtype == torch.int64 and counter.numel() == 1)
     ci, clo, chi = (-1, 0.0, 0.0) if clamp is None else (int(clamp[0]), float(clamp[1]), float(clamp[2]))
     if ci >= p.numel():
@@ -1814,9 +1816,30 @@ def adam(p, g, m, v, shadow, lr, b1, b2, eps, bc1, bc2, grad_scale=1.0, dev_stat
     for t in (p, g, m, v):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel()
     assert dev_state is None or (dev_state.dtype == torch.float32 and dev_state.numel() == 6 and dev_state.is_contiguous())
-    _lib.call("mh_adam", _p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), lr, b1, b2, eps, bc1, bc2, grad_scale,
-              _p(dev_state), ci, clo, chi, _p(counter), int(counter_add), 2 if tick == "early" else int(bool(tick)), *((0, 0) if hole is None else (int(hole[0]), int(hole[1]))),
-              stream=_stream())
+    args = (_p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), lr, b1, b2, eps, bc1, bc2, grad_scale,
+            _p(dev_state), ci, clo, chi, _p(counter), int(counter_add), 2 if tick == "early" else int(bool(tick)),
+            *((0, 0) if hole is None else (int(hole[0]), int(hole[1]))))
+    if ema is None:
+        _lib.call("mh_adam", *args, stream=_stream())
+        return
+    if not (ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() == p.numel()) or ema_cfg is None or dev_state is None:
+        raise MirrorHipError("adam: the EMA buffer must be a contiguous f32 tensor of p's size, with ema_cfg and dev_state")
+    _lib.call("mh_adam_ema", *args, _p(ema), C.addressof(ema_cfg), stream=_stream())
+
+
+def ema_update_many(ema: torch.Tensor, table: torch.Tensor, nseg: int, weight: float = 1.0, dev_state: Optional[torch.Tensor] = None,
+                    ema_cfg=None) -> None:
+    """ema[o_i : o_i + n_i] = lerp(ema[o_i : o_i + n_i], src_i, w) for the rows {o_i, src_i address, n_i} of `table` (int64 [nseg, 3]
+    on ema's device; the caller guarantees that every row lies inside `ema` and its f32 source).  w = weight, or timm's decay rule
+    of ema_cfg (_lib.EmaCfg) at the device step dev_state[0] (graph-capturable)."""
+    _chk(ema, table, dev_state)
+    if not (ema.dtype == torch.float32 and ema.is_contiguous() and table.dtype == torch.int64 and table.is_contiguous()
+            and table.numel() == 3 * nseg):
+        raise MirrorHipError("ema_update_many: f32 contiguous ema, int64 [nseg, 3] table")
+    if dev_state is not None and ema_cfg is None:
+        raise MirrorHipError("ema_update_many: dev_state needs ema_cfg")
+    _lib.call("mh_ema_update_many", _p(ema), _p(table), int(nseg), float(weight), _p(dev_state),
+              None if ema_cfg is None else C.addressof(ema_cfg), stream=_stream())
 
 
 # ----------------------------------------------------------------------------- survival step (train_survival.py)
