@@ -46,12 +46,7 @@ def plan_buckets(sizes: Sequence[int], cap_elems: int, align: int = _ALIGN):
     return buckets, owner
 
 
-# A/B switch: 1 (default) = the transposed weight copies are rebuilt at the start of a step on the RNA stream, 0 = behind Adam
-_ASYNC_GATHER = True      # alignment all-gather issued behind the heads
-_DEFER_SKINNY = True      # one multi-tensor launch for the skinny weight gradients
-_TRANSPOSE_AT_START = True      # (test hook)
 _EARLY_ADAM = True      # (test hook, round 5) the RNA encoder's share of the optimizer step on its branch's stream, beside the WSI backward
-_KERNEL_D2D = True      # (test hook, round 5) the static-input refresh of a replayed step as a kernel, not a copy-engine transfer
 
 
 class TrainEngine:
@@ -103,8 +98,8 @@ class TrainEngine:
         # global-batch InfoNCE: the model issues the alignment all-gather itself, right behind the heads (asynchronous, on a
         # communication stream: losses.mirror_loss.prefetch_alignment_gather); the loss only awaits it
         # (armed around the engine's own model calls only: a rank-local forward elsewhere must not issue an unmatched collective)
-        self._align_gather = ((clip.process_group,) if (clip is not None and getattr(clip, "gather_distributed", False) and self.world > 1
-                                                        and _ASYNC_GATHER) else None)
+        gather = clip is not None and getattr(clip, "gather_distributed", False) and self.world > 1
+        self._align_gather = (clip.process_group,) if gather else None
         model._align_gather = None
         params = [p for p in model.parameters() if p.requires_grad]
         if not params or not params[0].is_cuda:
@@ -406,7 +401,7 @@ class TrainEngine:
             for k, t in enumerate((wsi, rna) if mask is None else (wsi, rna, mask)):
                 if self._g_src[k] is not t or self._g_ver[k] != t._version:
                     dst = self._g_in[k]
-                    if (_KERNEL_D2D and t.dtype in (f32, bf16) and t.dtype == dst.dtype and t.is_contiguous() and t.numel() >= (1 << 20)
+                    if (t.dtype in (f32, bf16) and t.dtype == dst.dtype and t.is_contiguous() and t.numel() >= (1 << 20)
                             and t.numel() % 4 == 0 and t.data_ptr() % 16 == 0):
                         # a KERNEL, not the copy engine: a device-to-device hipMemcpyAsync is queued on the same in-order SDMA engine
                         # as the feeder's host -> device copy of the NEXT batch, which the host enqueued first and which waits for the
@@ -422,8 +417,8 @@ class TrainEngine:
                 self.model_ema._touch()          # the replay updated the EMA arena: its bf16 copies are stale
             # the replay ran Adam: the transposed copies trail it and the arena holds this step's gradients until the next
             # step's start — the Python flags of _step_body have to say so after a replay too (out-of-step backward)
-            self._t_stale = self.shadow_t is not None and _TRANSPOSE_AT_START
-            self._zero_pending = self._zero_pending or _TRANSPOSE_AT_START
+            self._t_stale = self.shadow_t is not None
+            self._zero_pending = True
             return self._g_out
         if self._graph_warm < 2:                            # allocator, shadows, sink counts and lazy inits settle first
             self._graph_warm += 1
@@ -478,22 +473,18 @@ class TrainEngine:
             if self._proto is not None:
                 w = self._proto.weight
                 K.rownorm_(w.data, shadow=Fn.shadow(w, POLICIES[self.precision]) if self.shadow is not None else None)
-        t_done = None
-        if not _TRANSPOSE_AT_START:
-            renorm_prototypes()
-        if _TRANSPOSE_AT_START:
-            # The transposed bf16 weight copies are read by BACKWARD kernels only (data gradients of the [B, D]-row linears): instead
-            # of 50 us behind Adam at the end of every step they are rebuilt at the start of the next one, on the RNA branch's
-            # stream, beside the WSI forward; the backward below waits for them.
-            main, side = torch.cuda.current_stream(), Fn._side_stream(self.device, 1)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                renorm_prototypes()          # read by the prototype head only, which runs on this stream (forward and backward)
-                self._refresh_transposes()
-                if self._zero_pending:           # the gradient arena of the update that ended the previous step
-                    self.grad.zero_()
-                    self._zero_pending = False
-                t_done = side.record_event()
+        # The transposed bf16 weight copies are read by BACKWARD kernels only (data gradients of the [B, D]-row linears): instead
+        # of 50 us behind Adam at the end of every step they are rebuilt at the start of the next one, on the RNA branch's
+        # stream, beside the WSI forward; the backward below waits for them.
+        main, side = torch.cuda.current_stream(), Fn._side_stream(self.device, 1)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            renorm_prototypes()          # read by the prototype head only, which runs on this stream (forward and backward)
+            self._refresh_transposes()
+            if self._zero_pending:           # the gradient arena of the update that ended the previous step
+                self.grad.zero_()
+                self._zero_pending = False
+            t_done = side.record_event()
         kw = {} if wsi_key_padding_mask is None else {"wsi_key_padding_mask": wsi_key_padding_mask}
         self.model._align_gather = self._align_gather
         try:
@@ -501,13 +492,12 @@ class TrainEngine:
         finally:
             self.model._align_gather = None
         losses = self.loss_fn(*outs)
-        if t_done is not None:
-            torch.cuda.current_stream().wait_event(t_done)
+        torch.cuda.current_stream().wait_event(t_done)
         Fn.set_grad_sink(self)
         # one process, no graphed RNA branch: the ~18 weight gradients of the [B, D]-row linears (RNA branch, heads) are queued during
         # the backward and run as ONE launch on the branch's stream behind it (with data parallelism they stay where they are: their
         # buckets should be reduced as early as possible)
-        defer = _DEFER_SKINNY and self.world == 1 and self._rna_branch_state != "on" and self.shadow is not None
+        defer = self.world == 1 and self._rna_branch_state != "on" and self.shadow is not None
         # two-launch optimizer step: only where nothing couples the ranges (no gradient reduction, no accumulation window, no global
         # clipping norm) — otherwise the one launch behind the backward, as before
         early = self._early_range if (_EARLY_ADAM and defer and self.accum_steps == 1 and self.clip_grad is None
@@ -580,20 +570,14 @@ class TrainEngine:
                clamp=clamp, counter=base, counter_add=used,
                tick=early is None, hole=early,     # the RNA encoder's range was updated (and t advanced) beside the WSI backward
                **({} if self.model_ema is None else {"ema": self._ema_arena[:self.numel], "ema_cfg": self._ema_cfg}))
-        if _TRANSPOSE_AT_START:
-            self._t_stale = self.shadow_t is not None
-        else:
-            self._refresh_transposes()
+        self._t_stale = self.shadow_t is not None
         if self._logit is not None and clamp is None:          # a frozen logit_scale is not in the arena
             K.clamp_(self._logit.data.reshape(1), 0.0, math.log(100.0))
             if self.shadow is not None:
                 K.cast(self._logit.data.reshape(1), bf16, out=Fn.shadow(self._logit, POLICIES[self.precision]).reshape(1))
         if self.model_ema is not None:
             self._ema_step()          # behind the clamp, as model_ema.update (:1284) follows it (:1255)
-        if _TRANSPOSE_AT_START:
-            self._zero_pending = True        # cleared by the next step, beside its forward (nobody reads the arena in between)
-        else:
-            self.grad.zero_()
+        self._zero_pending = True        # cleared by the next step, beside its forward (nobody reads the arena in between)
         return self._loss_out(losses)
 
     @staticmethod

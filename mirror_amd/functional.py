@@ -238,21 +238,16 @@ def _split_k_for(rows: int, n: int, k: int, batch: int = 1) -> int:
     return int(max(1, min(want, rows // 256)))
 
 
-_GEMM_SPLIT = True      # for the row split below
 _CUS = 256       # MI355X compute units = workgroup slots of the one-workgroup-per-CU 256 x 256 GEMM tile
 
 
-_TAIL_SKINNY = True      # (test hook)
-
-
-_TAIL_ASIDE = True      # (test hook) the ragged-row launches of a captured step run on a parallel branch beside their tiled launch
 import contextlib
 
 
 def _tail_fork():
     """Call BEFORE a tiled launch whose few ragged rows follow as tiny launches (_tail_rows): inside a HIP-graph capture it marks the
     point from which those launches may run in parallel (an event on the capturing stream); None otherwise (eager: same stream)."""
-    if not (_TAIL_ASIDE and torch.cuda.is_current_stream_capturing()):
+    if not torch.cuda.is_current_stream_capturing():
         return None
     cur = torch.cuda.current_stream()
     if any(st == cur for st in _side_streams.values()):
@@ -284,7 +279,7 @@ def _tail_rows(a2, b, out2, *, bias=None, act=ACT_NONE, mma, wt=None):
     product is the [B, D]-row shape of the RNA linears: the weight-streaming kernel (mh_skinny_fwd, ~6 us) instead of a tiled GEMM
     launch (13-22 us for one MFMA row block per workgroup).  b is a weight VIEW: W^T of a forward ([N, K] row-major underneath),
     or the weight itself in a data gradient, where `wt` is its transposed bf16 shadow."""
-    if _TAIL_SKINNY and mma == MH_BF16 and a2.dim() == 2:
+    if mma == MH_BF16 and a2.dim() == 2:
         W = b.t() if b.stride(0) == 1 else wt
         if W is not None and W.shape[0] == b.shape[1] and K.skinny_rows_ok(a2, W, out2):
             return K.skinny_fwd(a2, W, bias, act, out2.dtype, out=out2)
@@ -298,7 +293,7 @@ def _gemm_rows(a, b, *, bias=None, act=ACT_NONE, mma, out_dtype, out=None, wt=No
     launch and the remaining rows to a second one, which is too small for the big tile and runs on the 128 x 128 kernel
     (4x smaller tiles, 2 workgroups per CU): 2.1 rounds cost ~2.3 instead of 3."""
     if (a.dim() >= 2 and a.is_contiguous() and b.dim() == 2 and a.dtype == bf16 and b.dtype == bf16 and mma == MH_BF16
-            and (out_dtype or a.dtype) in (bf16, f32) and _GEMM_SPLIT
+            and (out_dtype or a.dtype) in (bf16, f32)
             and (out is None or (out.dim() == a.dim() and out.stride(-1) == 1 and all(
                 out.stride(i) == out.shape[i + 1] * out.stride(i + 1) for i in range(out.dim() - 2))))):
         R, Kd, N = a.numel() // a.shape[-1], a.shape[-1], b.shape[1]
@@ -326,9 +321,6 @@ def _gemm_rows(a, b, *, bias=None, act=ACT_NONE, mma, out_dtype, out=None, wt=No
                     K.gemm(a2[rows_main:], b, out=o2[rows_main:], bias=bias, act=act, mma=mma)
                     return o2.reshape(*a.shape[:-1], N) if out is None else out
     return K.gemm(a, b, out=out, bias=bias, act=act, mma=mma, out_dtype=out_dtype)
-
-
-_PAD_SKIP = True      # to_qkv / its data gradient skip the front-pad rows
 
 
 def _rows_window(a3, b2, out3, r0, R, *, mma, wt=None):
@@ -361,21 +353,13 @@ def _rows_scatter(dy, b2, dx, r0, R, *, mma, wt=None):
 
 
 def _rows_window_ok(a3, out3, r0, R, N, prec) -> bool:
-    return (_PAD_SKIP and r0 > 0 and prec.mma == MH_BF16 and prec.act == bf16 and not prec.fp8_fwd and (a3.shape[0] * R) % 256 <= 32
+    return (r0 > 0 and prec.mma == MH_BF16 and prec.act == bf16 and not prec.fp8_fwd and (a3.shape[0] * R) % 256 <= 32
             and K.gemm_rows_window_ok(a3, out3, r0, R, N))
-
-
-_GEMM_WINDOW = True      # (test hook)
-_LM_FIRST = False     # (experiment hook, round 5) tile-path geometries: only the landmark rows of to_qkv in front of the pinv fork, the sequence rows'
-                      # q | k | v as one launch beside the iteration: template +0.2 % +- 0.1 (20.137 vs 20.115 ms against the same base), off
-_DEFER_QK = False     # (experiment hook, round 5) the sequence rows of q | k under the pinv chain with the v columns (one launch), only the
-                      # landmark rows in front of the fork: measured +0.61 % +- 0.17 SLOWER (the window grows by more than the 93 us it
-                      # takes out of the serial part: in-window GEMMs run on the non-persistent kernel beside the half-chip chain)
 
 
 def _wt_of(w, prec, dy):
     """the transposed bf16 shadow of `w` when the rows of `dy` leave a ragged tail for _tail_rows (else None: nothing to look up)"""
-    if not _TAIL_SKINNY or prec.mma != MH_BF16 or w is None or w.dim() != 2:
+    if prec.mma != MH_BF16 or w is None or w.dim() != 2:
         return None
     rows = dy.shape[-2] if dy.dim() == 3 else dy.numel() // dy.shape[-1]
     flat = dy.numel() // dy.shape[-1]
@@ -391,7 +375,7 @@ def _gemm_window(a3, b2, out3, *, bias=None, mma, wt=None):
     own small launch instead and the rest is whole tiles (512 workgroups, two full rounds)."""
     R = a3.shape[1]
     hr = R % 256
-    if a3.dim() == 3 and R > 256 and 0 < hr <= 32 and mma == MH_BF16 and _GEMM_WINDOW:
+    if a3.dim() == 3 and R > 256 and 0 < hr <= 32 and mma == MH_BF16:
         K.gemm(a3[:, hr:], b2, out=out3[:, hr:], bias=bias, mma=mma)
         if hr == 1:      # one row per slide: [B, K] rows a batch stride apart
             _tail_rows(a3[:, 0], b2, out3[:, 0], bias=bias, mma=mma, wt=wt)
@@ -468,12 +452,12 @@ class LinearFn(Function):
     def forward(ctx, x, w, b, act, prec, out_dtype, defer_from=None):
         wa = shadow(w, prec)
         # [B, D] activations: weight-streaming kernels, which take an f32 operand as it is (rounded to bf16 on load: no cast launch)
-        ctx.skinny = prec.act == bf16 and _SKINNY_F32 and x.dtype == f32 and _skinny_ok(x, wa)
+        ctx.skinny = prec.act == bf16 and x.dtype == f32 and K.skinny_ok(x, wa)
         xa = x if (x.dtype == prec.act or ctx.skinny) else K.cast(x.contiguous(), prec.act)
         bd = None if b is None else b.detach()
-        ctx.skinny = ctx.skinny or (prec.act == bf16 and _skinny_ok(xa, wa))
+        ctx.skinny = ctx.skinny or (prec.act == bf16 and K.skinny_ok(xa, wa))
         y = None
-        if (defer_from and _DEFER_V and not ctx.skinny and not prec.fp8_fwd and b is None and act == ACT_NONE
+        if (defer_from and not ctx.skinny and not prec.fp8_fwd and b is None and act == ACT_NONE
                 and xa.is_contiguous() and 0 < defer_from < wa.shape[0]):
             # to_qkv: the q | k columns now, the v columns when NystromCoreFn asks for them (under the pinv chain)
             y = torch.empty(tuple(xa.shape[:-1]) + (wa.shape[0],), device=xa.device, dtype=out_dtype or prec.act)
@@ -501,13 +485,13 @@ class LinearFn(Function):
         else:
             if not dy.is_contiguous():
                 dy = dy.contiguous()
-            if dy.dtype != prec.act and not (ctx.skinny and _SKINNY_F32 and dy.dtype == f32 and dy.dim() == 2):
+            if dy.dtype != prec.act and not (ctx.skinny and dy.dtype == f32 and dy.dim() == 2):
                 dy = K.cast(dy, prec.act)          # (the skinny kernels round an f32 gradient on load)
         N, Kd = wa.shape
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             t_managed = N % 32 == 0 and Kd % 32 == 0      # the engine keeps W^T current for these (engine.py: two_d); others are transposed per call
-            if ctx.skinny and (t_managed or (w.numel() <= (1 << 21) and (N % 32 == 0 or (_SKINNY_ANY and N < 1024)))):
+            if ctx.skinny and (t_managed or (w.numel() <= (1 << 21) and (N % 32 == 0 or N < 1024))):
                 # (a short N that is no multiple of 32 runs the element-wise instance of the kernel on a W^T that shadow_t transposes per
                 #  call: the engine keeps transposes for multiples of 32 only.  Long ones — the 3000 prototypes, the template's 1975-wide MLP
                 #  — keep the split contraction below: with the per-call transpose the skinny form measured +0.34 % +- 0.22 on the c2 step;
@@ -658,7 +642,7 @@ class LinearPairFn(Function):
                 grads += [None, None]
                 continue
             dy = dy.contiguous()
-            if dy.dtype not in (f32, bf16) or (dy.dtype == f32 and not _SKINNY_F32):
+            if dy.dtype not in (f32, bf16):
                 dy = K.cast(dy, prec.act)
             if ctx.needs_input_grad[0]:
                 last = k == 1 or dy2 is None
@@ -672,9 +656,9 @@ class LinearPairFn(Function):
 def linear_pair(x, w1, b1, w2, b2, *, prec: Precision, out_dtype=None):
     """(linear(x, w1, b1), linear(x, w2, b2)); one autograd node on the [B, D]-row kernels, two plain linears otherwise."""
     if (prec.act == bf16 and not prec.fp8_fwd and x.is_cuda and x.dim() == 2 and w1.shape == w2.shape and w1.shape[0] % 32 == 0
-            and (x.dtype == bf16 or (x.dtype == f32 and _SKINNY_F32))):
+            and x.dtype in (bf16, f32)):
         wa1, wa2 = shadow(w1, prec), shadow(w2, prec)
-        if _skinny_ok(x, wa1) and _skinny_ok(x, wa2):
+        if K.skinny_ok(x, wa1) and K.skinny_ok(x, wa2):
             return LinearPairFn.apply(x, w1, b1, w2, b2, prec, out_dtype)
     return linear(x, w1, b1, prec=prec, out_dtype=out_dtype), linear(x, w2, b2, prec=prec, out_dtype=out_dtype)
 
@@ -685,13 +669,6 @@ def linear(x, w, b=None, *, act=ACT_NONE, prec: Precision, out_dtype=None, defer
     return LinearFn.apply(x, w, b, act, prec, out_dtype, defer_from)
 
 
-_DEFER_V = True      # (test hook)
-_SKINNY_F32 = True      # f32 operands straight into the skinny kernels
-_SKINNY_ANY = True      # (test hook, round 5) [B, D]-row linears whose K / N is no multiple of 32 on the skinny kernels' element-wise instance
-
-
-def _skinny_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
-    return K.skinny_ok(x, w) and (_SKINNY_ANY or K.skinny_vec_ok(x, w))
 _deferred: dict = {}        # data_ptr of a partly computed linear output -> the launch that completes it
 
 
@@ -765,7 +742,6 @@ def flush_deferred_bwd() -> None:
         _deferred_bwd.popitem()[1]()
 
 
-_HEAD_FOLD_FIRST = False     # (experiment hook) retention_head's bias-gradient fold in front of its two products: graph topology probe
 _BIAS_IN_PRODUCER = True     # (test hook, round 5) bias gradients left by the pass that wrote dy instead of an mh_colsum launch over it
 
 
@@ -811,7 +787,6 @@ def _linear_rows_bwd(ctx_needs, x, wa, w, b, r0, R, prec, dy, dx_dtype=None, def
     return dx, dw, db
 
 
-_DROP_COLSUM = True      # (test hook)
 _DROP_IN_LN_BWD = True      # (test hook, round 5) to_out's Dropout backward + bias gradient inside the LayerNorm backward that produces its dy
 
 
@@ -887,7 +862,7 @@ class ToOutDropAddFn(Function):
             gb = torch.empty(dy.shape, device=dy.device, dtype=ctx.prec.act)
         if handed is not None:
             pass
-        elif (_DROP_COLSUM and b is not None and ctx.needs_input_grad[3] and dy.dtype == f32 and gb.dtype == bf16
+        elif (b is not None and ctx.needs_input_grad[3] and dy.dtype == f32 and gb.dtype == bf16
                 and K.dropout_lite_colsum_ok(dy.shape[-1])):
             # the same pass leaves the bias gradient (column sums of the masked bf16 gradient): no mh_colsum launch over it
             dbuf, sunk = _gbuf(b, (dy.shape[-1],))
@@ -966,12 +941,7 @@ class HeadSqErrFn(Function):
             if tok.ptr == dy.data_ptr():
                 db_table = tok.ws
             tok.ws = None
-        db_have = None
-        if _HEAD_FOLD_FIRST and db_table is not None and b is not None and ctx.needs_input_grad[2]:
-            dbuf, sunk = _gbuf(b, (wa.shape[0],))        # the measured-slower order (see above), kept as a hook for the probe experiments
-            K.colsum(db_table, dbuf)
-            db_have, db_table = (dbuf, sunk), None
-        dx, dw, db = _linear_rows_bwd(ctx.needs_input_grad[0:3], x, wa, w, b, ctx.r0, ctx.R, prec, dy, db_table=db_table, db_have=db_have)
+        dx, dw, db = _linear_rows_bwd(ctx.needs_input_grad[0:3], x, wa, w, b, ctx.r0, ctx.R, prec, dy, db_table=db_table)
         return dx, dw, db, None, None, None, None, None, None, None
 
 
@@ -1117,8 +1087,7 @@ class LayerNormFn(Function):
         # e4m3 copy the projection reads, with that site's delayed scale — no quantisation pass over the LayerNorm output
         st = _fp8_state
         site = st["sites"].get(q8_key) if (q8_key is not None and st["tick"] is not None) else None
-        if (site is not None and st["host_step"] - site[1] >= 2 and x.dtype == f32 and out_dtype == bf16 and D % 4 == 0 and D <= 2048
-                and _LN_Q8):
+        if site is not None and st["host_step"] - site[1] >= 2 and x.dtype == f32 and out_dtype == bf16 and D % 4 == 0 and D <= 2048:
             q = torch.empty((Bn, pad + rows, D), device=x.device, dtype=torch.uint8)
             if pad:
                 q[:, :pad].zero_()
@@ -1220,17 +1189,7 @@ class NormQkvLmFn(Function):
         qkv = _alias(qe, 0, (Bn, n_p, N3), (n_p * N3, N3, 1))
         fast = (pad > 0 and prec.mma == MH_BF16 and c0 % 256 == 0 and (N3 - c0) % 256 == 0
                 and K.gemm_rows_ext_ok(Bn, n_p, pad, rows, E, D, c0, xe, qe[:, :c0]) and _rows_window_ok(xs, qkv[..., c0:], pad, rows, N3 - c0, prec))
-        if fast and _DEFER_QK and E % 256 == 0 and _rows_window_ok(xs, qkv, pad, rows, N3, prec):
-            # (round 5 experiment, off) only the LANDMARK rows of q | k are needed in front of the fork (sim2 and the pinv chain read nothing
-            # else): a [B m, D] x [D, 2D] product on 64 workgroups; the sequence rows of q, k AND v as one launch under the chain
-            K.gemm(xe[P:], wa[:c0].t(), out=qe[P:, :c0], mma=prec.mma)
-
-            def later():      # q = k = v = 0 on the pad rows (they take part in the softmaxes as zero keys)
-                fork = _tail_fork()
-                _rows_window(xs, wa.t(), qkv, pad, rows, mma=prec.mma)
-                with _tail_branch(fork, x.device):
-                    qkv[:, :pad].zero_()
-        elif fast:
+        if fast:
             fork = _tail_fork()
             tail = K.gemm_rows_ext(xe, wa[:c0].t(), qe[:, :c0], Bn, n_p, pad, rows, E)
             if tail:
@@ -1242,14 +1201,6 @@ class NormQkvLmFn(Function):
                 _rows_window(xs, wa[c0:].t(), qkv[..., c0:], pad, rows, mma=prec.mma)
                 with _tail_branch(fork, x.device):
                     qkv[:, :pad].zero_()
-        elif _LM_FIRST and _TILE_SIDE and prec.mma == MH_BF16 and prec.pinv_mma == MH_BF16 and m != K.PINV_CHAIN_M and K.gemm_tile_ok(m, m, m):
-            # the template's geometry (m = 384): the Moore-Penrose iteration is the longer side of the window it opens in NystromCoreFn and
-            # reads the landmarks only — their [B m, D] x [D, 2D] product stands in front of the fork, the sequence rows' q | k | v follow as
-            # ONE launch beside the iteration (run_deferred) instead of q | k (165 us) in front of it
-            K.gemm(xe[P:], wa[:c0].t(), out=qe[P:, :c0], mma=prec.mma)
-
-            def later():
-                K.gemm(xe[:P], wa.t(), out=qe[:P], mma=prec.mma)           # zero pad rows in, zero rows out
         else:
             K.gemm(xe, wa[:c0].t(), out=qe[:, :c0], mma=prec.mma)      # zero pad rows in, zero rows out
 
@@ -1402,16 +1353,12 @@ def layer_norm_landmarks_ok(x, rows: int, pad: int, l: int, prec: Precision) -> 
             and x.shape[-1] <= 2048 and (pad + rows) % l == 0 and x.shape[0] * rows >= 64)
 
 
-_LN_Q8 = True      # LayerNorm writes the e4m3 copy of its output (fp8 policy)
-
-
 def fp8_site_key(w: torch.Tensor, prec: "Precision"):
     """The key under which `linear(x, w)` keeps the delayed-scaling state of its activation operand (for a producer that
     quantises on its behalf: layer_norm(..., q8_key=))."""
     return (shadow(w, prec).data_ptr(), "x")
 
 
-_LN_DUAL = True      # (test hook)
 _FAN_IN_LN_BWD = True      # (test hook, round 5) the fan-out sum of the encoder output's gradients inside its LayerNorm's backward
 
 
@@ -1433,7 +1380,7 @@ def layer_norm(x, gamma, beta, eps, *, rows=None, pad=0, out_dtype=f32, q8_key=N
         x = x.unsqueeze(0)
     r = x.shape[1] if rows is None else rows
     dual = None
-    if (bf16_copy and _LN_DUAL and not squeeze and x.dtype == f32 and out_dtype == f32 and pad == 0 and x.shape[-1] % 4 == 0
+    if (bf16_copy and not squeeze and x.dtype == f32 and out_dtype == f32 and pad == 0 and x.shape[-1] % 4 == 0
             and x.shape[-1] <= 2048 and q8_key is None):
         dual = []
     slot = _FanSlot() if (_FAN_IN_LN_BWD and not squeeze and pad == 0 and out_dtype == f32 and x.dtype == f32) else None
@@ -1719,9 +1666,6 @@ def fc1_seq(wsi, w, b, cls, add_len: int, prec: Precision):
     return seq
 
 
-_PPEG_SCATTER = True      # (test hook)
-
-
 class PPEGFn(Function):
     """PPEG.forward (models/mirror.py:324-331) as one merged depthwise 7x7 on the token-major sequence."""
 
@@ -1737,15 +1681,11 @@ class PPEGFn(Function):
     def backward(ctx, dy):
         x, merged, bsum = ctx.saved_tensors
         S = ctx.S
-        D = x.shape[-1]
         dy = dy.contiguous()
         dx = K.ppeg(dy, merged, bsum, S, flip=True)
         dm = zeros(tuple(merged.shape), merged.device)
         dbs = zeros(tuple(bsum.shape), bsum.device)
         K.ppeg_wgrad(x, dy, dm, dbs, S)
-        if not _PPEG_SCATTER:       # A/B: the torch-side split (13 tiny launches with autograd's accumulation)
-            dm = dm.t().reshape(D, 1, 7, 7)
-            return (dx, dm.contiguous(), dbs, dm[:, :, 1:6, 1:6].contiguous(), dbs.clone(), dm[:, :, 2:5, 2:5].contiguous(), dbs.clone(), None)
         # merged gradient -> the six parameter gradients in one accumulating launch (straight into the engine's arena)
         bufs = [_gbuf(p, tuple(p.shape)) for p in ctx.params]
         K.ppeg_grad_scatter(dm, dbs, *[bufs[i][0] for i in (0, 2, 4, 1, 3, 5)])
@@ -1906,12 +1846,7 @@ def _pair(first: torch.Tensor, second: torch.Tensor) -> torch.Tensor:
     return torch.as_strided(first, (2,) + tuple(first.shape), (first.numel(),) + tuple(first.stride()))
 
 
-_S2_TAIL = True      # (test hook)
-_Z0_ROWS = True      # (test hook)
 _SIM2_MASKED = True      # (test hook, round 5) the one-launch sim2 + softmax + maxima + panels also under a key-padding mask (config 4)
-_SIM2_SIDE = True      # nys_sim2 opens the chain's branch instead of preceding the fork
-_S2_SIDE = True      # sim2's landmark gradients on the chain's stream
-_LM_MERGE_LATE = True      # (test hook) the landmark rows' merge + data gradient beside the sequence rows' data gradient (-0.24 % +- 0.29)
 _pending_lm_merge: dict = {}      # data_ptr of the landmark-gradient view NystromCoreFn.backward returned -> (address of the buffer
                                   # `de` the merge writes into, its deferred merge launch); see pending_lm_merge_reset
 
@@ -1926,8 +1861,6 @@ def pending_lm_merge_reset(where: str, strict: bool = False) -> None:
         if strict:
             raise K.MirrorHipError(f"{where}: {n} deferred landmark-gradient merge(s) were never run (NormQkvLmFn.backward did not follow "
                                    "NystromCoreFn.backward)")
-_W2_ON_CHAIN = True      # (test hook) w2 = pinv (attn3 v) at the end of the chain's branch instead of behind the join (-0.22 % +- 0.06)
-_DZ_DAV = True      # (test hook)
 _RC_FUSED = True      # (test hook) res_conv inside attn3's forward launch, its two gradients as one pass over dout (round 5)
 _A1_DQ_IN_WINDOW = False     # (test hook, round 5) attn1's dq kernel beside the pinv chain's backward: -0.35 % +- 0.02 when it was built, but
                              # +0.80 % +- 0.20 (8 ABBA rounds) on the round's final tree — the one-pass attn3 backward and the other kernels that joined the
@@ -1973,15 +1906,11 @@ class NystromCoreFn(Function):
         # sim2, its softmax, the tensor-wide abs-sum maxima and the chain's operand packing in ONE launch (nystrom_sim2.hip)
         one = chain and (kmask is None or _SIM2_MASKED) and dh == 64 and K.nys_sim2_ok(lm, h)      # (mask-aware since round 5: mlm of mh_nys_sim2)
         mlm_s2 = None if kmask is None else mlm
-        z0f = None
-        sim2_side = one and _SIM2_SIDE and _Z0_ROWS
-        if sim2_side:
+        if one:
             # nothing on the main stream needs attn2 before the join: the launch (128 workgroups, half of the chip, ~45 us) opens the
             # chain's branch instead of standing in front of the fork.  Buffers from the main stream's allocator, as chain_saved.
             a2, xt = K.nys_sim2_alloc(lm, h)
             st = zeros((4,), qkv.device).view(torch.int64)
-        elif one:
-            a2, xt, z0f, st = K.nys_sim2(lm, h, scale, zeros((4,), qkv.device).view(torch.int64), want_z0f=not _Z0_ROWS, mlm=mlm_s2)
         else:
             a2 = K.gemm(ql, kl.transpose(-1, -2), alpha=scale, mma=mma, out_dtype=f32)      # [B,h,m,m]
             if kmask is None:
@@ -2004,12 +1933,11 @@ class NystromCoreFn(Function):
             side = _side_stream(qkv.device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                if sim2_side:
+                if one:      # z_0 from the rows of attn2 inside the chain launch: nys_sim2 has no second pass and no f32 transpose
                     K.nys_sim2(lm, h, scale, st, out=(a2, xt), mlm=mlm_s2)
-                if one and _Z0_ROWS:      # z_0 from the rows of attn2 inside the chain launch: nys_sim2 has no second pass and no f32 transpose
                     K.pinv_chain_fwd(xt, chain_saved, zfT, iters, z0f=a2, stats=st, z0_rowmajor=True)
                 else:
-                    K.pinv_chain_fwd(xt, chain_saved, zfT, iters, z0f=z0f, stats=st if one else None)
+                    K.pinv_chain_fwd(xt, chain_saved, zfT, iters)
             saved = [(xt, chain_saved, z0 if z0 is not None else st)]      # (no stored f32 z_0 on the one-launch path: a placeholder)
             ctx.z0_stored = z0 is not None
             K.shared_chip = True         # until the join below: no persistent GEMM kernel beside the half-chip chain
@@ -2055,10 +1983,11 @@ class NystromCoreFn(Function):
         # GEMMs that meet activation-dtype tensors cannot use the exact-f32 MFMA unless the activations are f32 too
         pio = pm if (pm == MH_BF16 or A == f32) else mma
         w2 = None
-        if side is not None and fused and _W2_ON_CHAIN:
+        if side is not None and fused:
             # w2 = pinv(attn2) (attn3 v) is a [256 x 256] x [256 x 64] product per (b, h): ~11 us of launch that stood alone behind the
             # join.  av is complete here (the main side of the window is past attn3), the pseudo-inverse when the chain's stream gets to
-            # it: the product goes to the END of the chain's branch, beside res_conv on the main side, and the join covers it.
+            # it: the product goes to the END of the chain's branch, beside res_conv on the main side, and the join covers it
+            # (-0.22 % +- 0.06).
             w2 = torch.empty((Bn, h, m_l, dh), device=qkv.device, dtype=A)
             av_ready = torch.cuda.current_stream().record_event()
             with torch.cuda.stream(side):
@@ -2079,7 +2008,7 @@ class NystromCoreFn(Function):
             # fp8 forward policy: once to_out's call site has a scale history, attn1 also writes the e4m3 copy that projection reads
             st8 = _fp8_state
             site = st8["sites"].get(q8_key) if (q8_key is not None and st8["tick"] is not None and kmask is None) else None
-            if site is not None and st8["host_step"] - site[1] >= 2 and _LN_Q8:
+            if site is not None and st8["host_step"] - site[1] >= 2:
                 q8 = torch.empty(out.shape, device=out.device, dtype=torch.uint8)
                 lse1, sc8 = K.nys_attn1_fwd_q8(qkv, lm, w2, out, h, scale, True, q8, site[0], st8["tick"], o1=o1)
                 _prequant[out.data_ptr()] = (q8, sc8)
@@ -2155,7 +2084,7 @@ class NystromCoreFn(Function):
         sd = f32 if pm == MH_F32 else bf16
         pio = pm if (pm == MH_BF16 or A == f32) else mma
         # dZ = dW2 av^T (the chain's input, packed) and dAV = Z^T dW2: ONE launch on the fused bf16 path (nystrom_sim2.hip)
-        one2 = (_DZ_DAV and chain and fused and A == bf16 and pio == MH_BF16 and dh == 64 and m == 256 and dW2.dtype == f32 and av.dtype == f32)
+        one2 = (chain and fused and A == bf16 and pio == MH_BF16 and dh == 64 and m == 256 and dW2.dtype == f32 and av.dtype == f32)
         dAV = dzb = None
         if one2:
             dzb, dAV = K.nys_dz_dav(dW2, av.contiguous(), zfT)
@@ -2170,7 +2099,7 @@ class NystromCoreFn(Function):
             dz0 = torch.empty_like(a2)
             if dzb is None:
                 dzb = K.pinv_chain_pack(dZ)
-            if _S2_SIDE and fused and (kmask is None or _SIM2_MASKED):
+            if fused and (kmask is None or _SIM2_MASKED):
                 # sim2's share of the landmark gradients leaves the serial tail behind the join: the chain's stream has slack
                 # in this window.  The attention kernels on the main stream add into dlm with atomics meanwhile, so the two
                 # products go to a buffer of their own and one add (which is also the cast) merges them after the join.
@@ -2179,7 +2108,7 @@ class NystromCoreFn(Function):
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 K.pinv_chain_bwd(xb, chain_saved, dzb, work, dS2, dz0, iters)
-                if _S2_TAIL and (kmask is None or _SIM2_MASKED) and not ctx.z0_stored and a2.shape[-1] == 256:
+                if (kmask is None or _SIM2_MASKED) and not ctx.z0_stored and a2.shape[-1] == 256:
                     # z_0 backward, the maxima's sub-gradients and attn2's (masked) softmax backward: one pass
                     K.pinv_s2_bwd(a2, dz0, st, dS2, _zeroed1(a2.device), mlm=mlm if kmask else None, heads=h)
                 else:
@@ -2244,12 +2173,9 @@ class NystromCoreFn(Function):
         if de is not None and (kmask is None or (lscale is None and dlm2 is not None)):
             # the merge of the two f32 partial sums is also the cast, written as rows [dq_l | dk_l | 0] behind the sequence rows.
             # Nothing but the landmark rows' own products needs it: NormQkvLmFn.backward runs it (and the landmark rows' data gradient)
-            # on a parallel branch beside the data gradient of the sequence rows instead of in front of it
+            # on a parallel branch beside the data gradient of the sequence rows instead of in front of it (-0.24 % +- 0.29)
             merge = lambda: K.lm_merge(dlm, dlm2, de[Bn * n_p:], D3 - 2 * D)      # noqa: E731
-            if _LM_MERGE_LATE:
-                _pending_lm_merge[dlm_out.data_ptr()] = (de.data_ptr(), merge)
-            else:
-                merge()
+            _pending_lm_merge[dlm_out.data_ptr()] = (de.data_ptr(), merge)
             return dqkv, dres, None, None, None, None, None, None, dlm_out
         if dlm2 is not None:
             dlm = K.add(dlm, dlm2, out_dtype=A)

@@ -29,12 +29,7 @@ f32 = torch.float32
 
 _DEFAULT_PRECISION: Optional[str] = None
 
-# program order of the two encoder branches in MIRROR.forward (see there): 1 = WSI encoder launches first (default)
-_RNA_LATE = True      # (test hook)
-# 1 (default) = the alignment / style heads run on the RNA branch's helper stream, 0 = on the caller's stream (A/B switch)
-_HEADS_SIDE = True      # (test hook)
 _LM_MASKED = True      # (test hook, round 5) the landmark-row LayerNorm + to_qkv node also under a key-padding mask (BASELINE config 4)
-_OWN_NOISE = True      # (test hook, round 5) the step's four random draws as one launch on the dropout stream instead of torch's generator
 # (measured and removed: the four noise draws + the prototype renorm on the RNA stream cost 0.5 - 1 % of the step)
 
 
@@ -548,7 +543,7 @@ class MIRROR(nn.Module):
         # come from ONE launch on the dropout stream, issued on the side stream that consumes them (round 5: as torch draws they were four
         # launches in front of the WSI encoder's first GEMM plus two generator-state fills in front of every graph replay).  Eval mode keeps
         # torch's generator: validate() runs outside the step protocol that advances the dropout stream's device base
-        own_draws = _OWN_NOISE and _HEADS_SIDE and self.training and not any(k in noise for k in ("wsi_mask", "rna_mask", "wsi_eps", "rna_eps"))
+        own_draws = self.training and not any(k in noise for k in ("wsi_mask", "rna_mask", "wsi_eps", "rna_eps"))
         if not own_draws:
             if "wsi_mask" not in noise:
                 noise["wsi_mask"] = torch.rand(B, wsi_emb.shape[1], device=dev)
@@ -588,7 +583,7 @@ class MIRROR(nn.Module):
         # masks do not depend on the launch order): the RNA range is reserved up front once its length is known.
         st = Fn._dropout_state
         key = (tuple(rna_emb.shape), self.training, torch.is_grad_enabled(), rna_mask_ratio)
-        n_rna = self._rna_drop_n.get(key) if _RNA_LATE else None
+        n_rna = self._rna_drop_n.get(key)
         if n_rna is not None:
             off0 = st["offset"]
             st["offset"] = off0 + n_rna
@@ -611,7 +606,7 @@ class MIRROR(nn.Module):
         # RNA branch's stream they run beside the retention decoder (a whole TransLayer) instead of in front of its backward.
         # (A third helper stream that waits for both the main and the RNA stream before its first kernel makes
         # hipStreamEndCapture of the whole-step graph segfault on ROCm 7.2.)
-        heads = side if _HEADS_SIDE else main
+        heads = side
         heads.wait_event(main.record_event())
         wsi_cls.record_stream(heads)
         with torch.cuda.stream(heads):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """ms per replayed c2 step with module-level test hooks flipped, one process per setting (the step is captured once per process).
-usage: python3 tools/exp/flag_time.py [steps] [module.NAME=value ...]   e.g. functional._TAIL_ASIDE=False engine._DEFER_SKINNY=False"""
+usage: python3 tools/exp/flag_time.py [steps] [module.NAME=value ...]   e.g. functional._TILE_SIDE=False engine._EARLY_ADAM=False"""
 import importlib
 import os
 import sys
