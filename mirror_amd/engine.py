@@ -452,19 +452,16 @@ class TrainEngine:
         # validate() or a bare model call must neither read nor advance these rings, and a freed engine's table must not stay
         # reachable from the module global
         sites_before = Fn._fp8_state["sites"]
-        Fn.pending_lm_merge_reset("TrainEngine.step (start)")
         try:
             return self._step_body(wsi, rna, noise, wsi_key_padding_mask)
         finally:
             Fn.zero_arena_end()      # also after an exception: nothing outside a step may carve from an arena that is not re-zeroed
             Fn.fp8_delayed_scaling(None)      # delayed fp8 scaling belongs to training steps only
             Fn._fp8_state["sites"] = sites_before
-            Fn.pending_lm_merge_reset("TrainEngine.step (end)")      # an aborted backward must not pin its buffers
 
     def _step_body(self, wsi: torch.Tensor, rna: torch.Tensor, noise: Optional[dict],
                    wsi_key_padding_mask: Optional[torch.Tensor] = None):
         Fn.dropout_step_begin(self.device)
-        Fn._res_grads.clear()
         Fn.probe("step_start")
         if POLICIES[self.precision].fp8_fwd:       # delayed fp8 scaling keys its amax rings on the device-side step counter
             Fn._fp8_state["sites"] = self._fp8_sites
@@ -509,8 +506,6 @@ class TrainEngine:
                 self._one = torch.ones((), device=losses[0].device, dtype=losses[0].dtype)
             Fn.probe("loss_done")
             losses[0].backward(self._one)        # a persistent root gradient: no ones_like fill launch per step
-            Fn.pending_lm_merge_reset("TrainEngine.step (after backward)", strict=True)
-            Fn.flush_deferred_bwd()
             if defer:
                 with torch.cuda.stream(Fn._side_stream(self.device, 1)):
                     Fn.probe("side_bwd_end")

@@ -392,24 +392,21 @@ def _gemm_window(a3, b2, out3, *, bias=None, mma, wt=None):
 _fp8_state = {"tick": None, "sites": {}, "host_step": 0}
 
 
-_prequant: dict = {}        # data_ptr of a producer's bf16 output -> (e4m3 copy, scale) the producer wrote in the same pass
-
-
 def fp8_delayed_scaling(tick: Optional[torch.Tensor], host_step: int = 0) -> None:
     """tick: device f32[1] step counter (TrainEngine._state[0:1]) for the duration of a training step; None: back to the exact
     two-pass quantisation (evaluation, module use without an engine).  The per-site amax rings survive a None."""
     _fp8_state["tick"] = tick
     _fp8_state["host_step"] = int(host_step)
-    _prequant.clear()
 
 
 def _quant_site(t: torch.Tensor, key):
     st = _fp8_state
     if st["tick"] is None:
         return K.quant_fp8(t)
-    pq = _prequant.get(t.data_ptr())
-    if pq is not None and pq[0].shape == t.shape:
-        return pq                       # the LayerNorm that produced `t` already wrote its e4m3 copy (layernorm_fwd_q8)
+    src = t if t._base is None else t._base      # (to_out's row window at pad 0 is a view of the whole attention output)
+    pq = getattr(src, "_q8", None)
+    if pq is not None and pq[0].shape == t.shape and src.data_ptr() == t.data_ptr():
+        return pq                       # the producer of `t` already wrote its e4m3 copy (layer_norm(q8_key=), TransLayer's attention)
     site = st["sites"].get(key)
     if site is None:
         site = st["sites"][key] = [torch.zeros(3, device=t.device, dtype=torch.int32), st["host_step"]]
@@ -449,7 +446,7 @@ class LinearFn(Function):
     W: [N, K] f32 master.  Replaces nn.Linear (+ nn.ReLU for _fc1, models/mirror.py:346)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, act, prec, out_dtype, defer_from=None):
+    def forward(ctx, x, w, b, act, prec, out_dtype, defer_from=None, link=None):
         wa = shadow(w, prec)
         # [B, D] activations: weight-streaming kernels, which take an f32 operand as it is (rounded to bf16 on load: no cast launch)
         ctx.skinny = prec.act == bf16 and x.dtype == f32 and K.skinny_ok(x, wa)
@@ -457,13 +454,13 @@ class LinearFn(Function):
         bd = None if b is None else b.detach()
         ctx.skinny = ctx.skinny or (prec.act == bf16 and K.skinny_ok(xa, wa))
         y = None
-        if (defer_from and not ctx.skinny and not prec.fp8_fwd and b is None and act == ACT_NONE
+        if (defer_from and link is not None and not ctx.skinny and not prec.fp8_fwd and b is None and act == ACT_NONE
                 and xa.is_contiguous() and 0 < defer_from < wa.shape[0]):
             # to_qkv: the q | k columns now, the v columns when NystromCoreFn asks for them (under the pinv chain)
             y = torch.empty(tuple(xa.shape[:-1]) + (wa.shape[0],), device=xa.device, dtype=out_dtype or prec.act)
             c0, od = defer_from, out_dtype or prec.act
             _gemm_rows(xa, wa[:c0].t(), mma=prec.mma, out_dtype=od, out=y[..., :c0])
-            _deferred[y.data_ptr()] = lambda: _gemm_rows(xa, wa[c0:].t(), mma=prec.mma, out_dtype=od, out=y[..., c0:])
+            link.v_cols = lambda: _gemm_rows(xa, wa[c0:].t(), mma=prec.mma, out_dtype=od, out=y[..., c0:])
         if ctx.skinny:
             y = K.skinny_fwd(xa, wa, bd, act, out_dtype or prec.act)
         elif prec.fp8_fwd:
@@ -520,7 +517,7 @@ class LinearFn(Function):
                 if _wgrad_queue is not None and sunk and (dbuf is None or sunk_b) and dy.dim() == 2:
                     # engine step: every [B, D]-row weight gradient of the backward goes into ONE launch at its end (flush_skinny_wgrads)
                     _wgrad_queue.append((dy, xa, dw, dbuf, w, b if fused_db else None, torch.cuda.current_stream()))
-                    return dx, None, None, None, None, None, None
+                    return dx, None, None, None, None, None, None, None
                 K.skinny_wgrad(dy, xa, dw, accumulate=True, db=dbuf)
                 if fused_db:
                     db = _gret(b, dbuf, sunk_b)
@@ -531,7 +528,7 @@ class LinearFn(Function):
             db, sunk = _gbuf(b, (N,))
             K.colsum(dy.reshape(-1, N), db)
             db = _gret(b, db, sunk)
-        return dx, dw, db, None, None, None, None
+        return dx, dw, db, None, None, None, None, None
 
 
 # deferred weight gradients of the skinny linears: a list while an engine step's backward runs (TrainEngine sets it), else None
@@ -663,19 +660,10 @@ def linear_pair(x, w1, b1, w2, b2, *, prec: Precision, out_dtype=None):
     return linear(x, w1, b1, prec=prec, out_dtype=out_dtype), linear(x, w2, b2, prec=prec, out_dtype=out_dtype)
 
 
-def linear(x, w, b=None, *, act=ACT_NONE, prec: Precision, out_dtype=None, defer_from=None):
-    """defer_from = c: only output columns [0, c) are computed here; the rest is a pending launch that the consumer runs
-    with run_deferred(y) (NystromCoreFn does, right after it has forked the pinv chain)."""
-    return LinearFn.apply(x, w, b, act, prec, out_dtype, defer_from)
-
-
-_deferred: dict = {}        # data_ptr of a partly computed linear output -> the launch that completes it
-
-
-def run_deferred(y: torch.Tensor) -> None:
-    t = _deferred.pop(y.data_ptr(), None)
-    if t is not None:
-        t()
+def linear(x, w, b=None, *, act=ACT_NONE, prec: Precision, out_dtype=None, defer_from=None, link=None):
+    """defer_from = c with a NystromLink: only output columns [0, c) are computed here; the rest is a pending launch left in
+    link.v_cols (NystromCoreFn runs it, right after it has forked the pinv chain)."""
+    return LinearFn.apply(x, w, b, act, prec, out_dtype, defer_from, link)
 
 
 class LinearRowsFn(Function):
@@ -727,28 +715,15 @@ class LinearRowsFn(Function):
 
 
 _TO_OUT_WGRAD_IN_WINDOW = True      # (test hook, round 5) to_out's weight gradient beside the pinv chain's backward (-0.23 % +- 0.15)
-_deferred_bwd: dict = {}    # data_ptr of a data gradient -> a weight-gradient launch that its consumer runs where it has idle CUs
-
-
-def run_deferred_bwd(dx: torch.Tensor) -> None:
-    t = _deferred_bwd.pop(dx.data_ptr(), None)
-    if t is not None:
-        t()
-
-
-def flush_deferred_bwd() -> None:
-    """Launch whatever nobody claimed (a to_out whose data gradient did not reach a NystromCoreFn.backward): never lose a gradient."""
-    while _deferred_bwd:
-        _deferred_bwd.popitem()[1]()
 
 
 _BIAS_IN_PRODUCER = True     # (test hook, round 5) bias gradients left by the pass that wrote dy instead of an mh_colsum launch over it
 
 
-def _linear_rows_bwd(ctx_needs, x, wa, w, b, r0, R, prec, dy, dx_dtype=None, defer_wgrad=False, db_have=None, db_table=None):
+def _linear_rows_bwd(ctx_needs, x, wa, w, b, r0, R, prec, dy, dx_dtype=None, defer_to=None, db_have=None, db_table=None):
     """Backward of y = x[:, r0:r0+R] @ W^T + b given dy [B, R, N] in the activation dtype: (dx over all of x's rows, dW, db).
-    defer_wgrad: when the weight gradient goes straight into the gradient sink, its launch is left to whoever consumes dx
-    (run_deferred_bwd(dx)): NystromCoreFn.backward issues to_out's weight gradient beside the half-chip pinv chain."""
+    defer_to: a NystromLink whose NystromCoreFn produced x — when the weight gradient goes straight into the gradient sink, its
+    launch is left in defer_to.wgrad: NystromCoreFn.backward issues to_out's weight gradient beside the half-chip pinv chain."""
     N, Kd = wa.shape
     dx = dw = db = None
     if ctx_needs[0]:
@@ -765,13 +740,13 @@ def _linear_rows_bwd(ctx_needs, x, wa, w, b, r0, R, prec, dy, dx_dtype=None, def
                 dx[:, r0 + R:].zero_()
     if ctx_needs[1]:
         dw, sunk = _gbuf(w, (N, Kd))
-        if defer_wgrad and sunk and dx is not None and _TO_OUT_WGRAD_IN_WINDOW:
+        if defer_to is not None and defer_to.core and sunk and dx is not None and _TO_OUT_WGRAD_IN_WINDOW:
             dwb = dw
 
             def later():
                 _wgrad(dy, x[:, r0:r0 + R], N, Kd, prec, dwb)
                 _gret(w, dwb, True)
-            _deferred_bwd[dx.data_ptr()] = later
+            defer_to.wgrad = later
             dw = None
         else:
             _wgrad(dy, x[:, r0:r0 + R], N, Kd, prec, dw)
@@ -804,8 +779,45 @@ class _DropSite:
 
 
 # (the site travels ON the output tensor — `out._drop_site`, read by LayerNormFn.forward — not in a table keyed by its address: a stale
-#  address entry could meet an unrelated tensor once the allocator recycles the block, ADVICE r4 on _pending_lm_merge)
+#  address entry could meet an unrelated tensor once the allocator recycles the block)
 
+
+class _Link:
+    __slots__ = ()
+
+    def take(self, name: str):
+        """The content of field `name`, which is cleared: a hand-over is consumed once."""
+        v = getattr(self, name)
+        setattr(self, name, None)
+        return v
+
+
+class NystromLink(_Link):
+    """Hand-overs between the nodes of one TransLayer, made by TransLayer.forward and held by every node it pairs (dies with the graph).
+    v_cols: to_qkv's pending v-column launch (linear(defer_from=) / NormQkvLmFn), run by NystromCoreFn.forward under the pinv chain;
+    core: NystromCoreFn took the link (its backward runs when its output needs a gradient); wgrad: to_out's weight-gradient launch
+    (ToOutDropAddFn.backward), run by NystromCoreFn.backward beside the chain; lm_merge: (de, the landmark rows' merge into de) for
+    NormQkvLmFn.backward."""
+    __slots__ = ("v_cols", "core", "wgrad", "lm_merge")
+
+    def __init__(self):
+        self.v_cols = self.wgrad = self.lm_merge = None
+        self.core = False
+
+    def run(self, name: str) -> None:
+        """Take and run the pending launch `name` ("v_cols" or "wgrad"), if there is one."""
+        f = self.take(name)
+        if f is not None:
+            f()
+
+
+class ResidualLink(_Link):
+    """Hand-over between the residual add of a pre-norm block x + f(LN(x)) (AddFn, DropoutAddFn, ToOutDropAddFn) and that LayerNorm,
+    made by the block: the add's backward leaves x's gradient tensor in `grad`, the norm's backward adds its own dx INTO it."""
+    __slots__ = ("grad",)
+
+    def __init__(self):
+        self.grad = None
 
 
 class ToOutDropAddFn(Function):
@@ -816,7 +828,7 @@ class ToOutDropAddFn(Function):
     one mh_dropout draws for the same (seed, offset, element))."""
 
     @staticmethod
-    def forward(ctx, resid, core, w, b, r0, R, p, prec, site=None):
+    def forward(ctx, resid, core, w, b, r0, R, p, prec, site=None, res=None, link=None):
         wa = shadow(w, prec)
         Bn, _, Kd = core.shape
         N = wa.shape[0]
@@ -835,7 +847,7 @@ class ToOutDropAddFn(Function):
                 K.dropout_lite(yt, p, ctx.seed, ctx.offset + (M - tail) * N, ctx.base, add_to=resid.view(M, N)[M - tail:],
                                out=out.view(M, N)[M - tail:])
         ctx.save_for_backward(core, wa, w, b)
-        ctx.r0, ctx.R, ctx.prec, ctx.res_key = r0, R, prec, resid.data_ptr()
+        ctx.r0, ctx.R, ctx.prec, ctx.res, ctx.link = r0, R, prec, res, link
         ctx.site = site
         if site is not None:
             site.fill(p, ctx.seed, ctx.offset, ctx.base, out.shape)
@@ -870,28 +882,29 @@ class ToOutDropAddFn(Function):
             db_done, fused_db = _gret(b, dbuf, sunk), True
         else:
             K.dropout_lite(dy, ctx.p, ctx.seed, ctx.offset, ctx.base, out=gb)       # masked, scaled gradient of the projection output
-        _res_grads[ctx.res_key] = dy         # the block's LayerNorm accumulates its dx into the residual gradient (see AddFn)
+        if ctx.res is not None:
+            ctx.res.grad = dy         # the block's LayerNorm accumulates its dx into the residual gradient (ResidualLink)
         needs = list(ctx.needs_input_grad[1:4])
         if fused_db:
             needs[2] = False
-        dcore, dw, db = _linear_rows_bwd(needs, core, wa, w, b, ctx.r0, ctx.R, ctx.prec, gb, defer_wgrad=True)
+        dcore, dw, db = _linear_rows_bwd(needs, core, wa, w, b, ctx.r0, ctx.R, ctx.prec, gb, defer_to=ctx.link)
         if fused_db:
             db = db_done
-        return dy, dcore, dw, db, None, None, None, None, None
+        return dy, dcore, dw, db, None, None, None, None, None, None, None
 
 
-def to_out_dropout_add(resid, core, w, b, r0: int, R: int, p: float, training: bool, prec: Precision):
+def to_out_dropout_add(resid, core, w, b, r0: int, R: int, p: float, training: bool, prec: Precision, res=None, link=None):
     """x + Dropout(to_out(core)[:, r0:r0+R]): fused when the shapes are on the 256 x 256-tile kernel (bf16 policy, training)."""
     if (training and p > 0.0 and prec.act == bf16 and not prec.fp8_fwd and resid.dtype == f32 and resid.is_contiguous()
             and core.dtype == bf16 and tuple(resid.shape) == (core.shape[0], R, w.shape[0]) and (core.shape[0] * R * w.shape[0]) % 8 == 0
             and K.linear_fused_ok(core, shadow(w, prec), (r0, R))):
         site = _DropSite() if (_DROP_IN_LN_BWD and b is not None) else None
-        out = ToOutDropAddFn.apply(resid, core, w, b, r0, R, p, prec, site)
+        out = ToOutDropAddFn.apply(resid, core, w, b, r0, R, p, prec, site, res, link)
         if site is not None:
             out._drop_site = site       # a LayerNorm that reads this tensor may do the Dropout's backward in its own (LayerNormFn)
         return out
     y = LinearRowsFn.apply(core, w, b, r0, R, prec, prec.act)
-    return dropout_add(resid, y, p, training, lite=True)
+    return dropout_add(resid, y, p, training, lite=True, res=res)
 
 
 class _ColsumToken:
@@ -1059,11 +1072,11 @@ class LayerNormFn(Function):
     [3P] NystromAttention).  Output [B, pad + rows, D] in `out_dtype`."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps, rows, pad, out_dtype, q8_key=None, dual=None, fan_slot=None):
+    def forward(ctx, x, gamma, beta, eps, rows, pad, out_dtype, q8_key=None, dual=None, fan_slot=None, res=None, q8_out=None):
         x = x.contiguous()
         Bn, T, D = x.shape
         y = torch.empty((Bn, pad + rows, D), device=x.device, dtype=out_dtype)
-        ctx.fan_slot = fan_slot
+        ctx.fan_slot, ctx.res = fan_slot, res
         # x = resid + Dropout(to_out(.)) of the TransLayer in front: this norm's dx is that Dropout's upstream gradient (see backward)
         ctx.drop_site = getattr(x, "_drop_site", None) if (_DROP_IN_LN_BWD and pad == 0 and x.dtype == f32) else None
         if ctx.drop_site is not None and ctx.drop_site.shape != (Bn, T, D):
@@ -1093,7 +1106,7 @@ class LayerNormFn(Function):
                 q[:, :pad].zero_()
             sc = K.layernorm_fwd_q8(x, gamma.detach(), beta.detach(), y[:, pad:], mean, rstd, Bn, rows, D, T * D, (pad + rows) * D, eps,
                                     q[:, pad:], site[0], st["tick"])
-            _prequant[y.data_ptr()] = (q, sc)
+            q8_out.append((q, sc))        # (layer_norm attaches it to y)
         else:
             K.layernorm_fwd(x, gamma.detach(), beta.detach(), y[:, pad:], mean, rstd, Bn, rows, D, T * D, (pad + rows) * D, eps)
         ctx.save_for_backward(x, gamma, mean, rstd, beta)
@@ -1117,15 +1130,15 @@ class LayerNormFn(Function):
             fan, ctx.fan_slot.extra = ctx.fan_slot.extra, None
             if pad or not K.layernorm_bwd_fan_ok(dy, x, x, fan[0], fan[2], Bn, rows, D):     # (rows < T is fine: x_bs carries the stride)
                 dy, fan = K.fanout_bwd(dy.float(), fan[0], fan[1], fan[2], Bn, rows, D), None
-        # pre-norm residual block  x + f(LN(x)):  the residual add's backward ran first and left its gradient for x in
-        # _res_grads; LN adds its own dx INTO that tensor (mh_layernorm_bwd accumulate_dx) instead of handing autograd a
+        # pre-norm residual block  x + f(LN(x)):  the residual add's backward ran first and left its gradient for x in the
+        # ResidualLink; LN adds its own dx INTO that tensor (mh_layernorm_bwd accumulate_dx) instead of handing autograd a
         # second [B, T, D] f32 gradient to sum (a 400 MB elementwise pass per block)
-        G = _res_grads.pop(x.data_ptr(), None)
+        G = None if ctx.res is None else ctx.res.take("grad")
         if G is not None and G.numel() == x.numel() and G.dtype == x.dtype and G.is_contiguous():
             G = G.view(x.shape)          # the RNA blocks run on [B, D]: layer_norm() added a leading 1
             K.layernorm_bwd(dy[:, pad:], x, gamma.detach(), mean, rstd, G, dg, db, Bn, rows, D, T * D, (pad + rows) * D,
                             accumulate_dx=True, fan=fan)
-            return None, _gret(gamma, dg, sunk_g), _gret(beta, db, sunk_b), None, None, None, None, None, None, None
+            return None, _gret(gamma, dg, sunk_g), _gret(beta, db, sunk_b), None, None, None, None, None, None, None, None, None
         dx = torch.empty_like(x)
         if rows < T:
             dx[:, rows:].zero_()         # only the rows the norm never read (a zeros_like of [B, T, D] is a 268 MB fill at config 4)
@@ -1139,7 +1152,7 @@ class LayerNormFn(Function):
                 drop = (gbd, site.p, site.seed, site.offset, site.base, cs)
                 site.grad = (dx.data_ptr(), gbd, cs)
         K.layernorm_bwd(dy[:, pad:], x, gamma.detach(), mean, rstd, dx, dg, db, Bn, rows, D, T * D, (pad + rows) * D, fan=fan, drop=drop)
-        return dx, _gret(gamma, dg, sunk_g), _gret(beta, db, sunk_b), None, None, None, None, None, None, None
+        return dx, _gret(gamma, dg, sunk_g), _gret(beta, db, sunk_b), None, None, None, None, None, None, None, None, None
 
 
 def _alias(base: torch.Tensor, offset: int, size, stride) -> torch.Tensor:
@@ -1162,15 +1175,16 @@ class NormQkvLmFn(Function):
     NystromCoreFn returns d qkv and d lm as the two row ranges of ONE gradient buffer ([dq_l | dk_l | 0] rows), so the data gradient
     (whose last rows are d xpm, added to the rows' gradient by mh_layernorm_bwd_lm) and the weight gradient (one contraction over
     all B n_p + B m rows) need no landmark launches either.  Returns (qkv [B, n_p, 3D], lm [B, m, 2D] with row stride 3D).
-    The v columns of the sequence rows are a deferred launch (run_deferred(qkv), under the pinv chain); the pad rows are skipped
+    The v columns of the sequence rows are a deferred launch (link.v_cols, under the pinv chain); the pad rows are skipped
     by the flat row-window kernels (K.gemm_rows_ext) when the geometry allows, else every physical row is multiplied."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps, rows, pad, l, w, prec, rmask=None, lscale=None):
+    def forward(ctx, x, gamma, beta, eps, rows, pad, l, w, prec, link, rmask=None, lscale=None, res=None):
         """rmask (f32 [B, pad + rows], BASELINE config 4): the front-padded key-padding mask — masked rows leave the norm as zero rows and
         stay out of the landmark sums (mh_layernorm_fwd_lm); lscale (f32 [B, m]) = l / valid count per group: the landmark rows leave
         as the masked MEANS ([3P] `q_landmarks /= divisor`), NystromCoreFn then gets kmask with a None scale."""
         ctx.relu_slot = getattr(x, "_relu_slot", None)      # x is Fc1SeqFn's sequence (layer 1): see backward
+        ctx.link, ctx.res = link, res       # (NystromLink: v_cols out, lm_merge in; ResidualLink of the TransLayer's residual add)
         x = x.contiguous()
         Bn, T, D = x.shape
         n_p = pad + rows
@@ -1206,7 +1220,7 @@ class NormQkvLmFn(Function):
 
             def later():
                 K.gemm(xe[:P], wa[c0:].t(), out=qe[:P, c0:], mma=prec.mma)
-        _deferred[qkv.data_ptr()] = later
+        link.v_cols = later
         ctx.save_for_backward(x, gamma, mean, rstd, beta, xe, wa, w)
         ctx.geo = (rows, pad, l, fast, prec)
         return qkv, _alias(qe, P * N3, (Bn, m, c0), (m * N3, N3, 1))
@@ -1220,12 +1234,11 @@ class NormQkvLmFn(Function):
         m = n_p // l
         P, E = Bn * n_p, Bn * m
         N3, c0 = wa.shape[0], 2 * wa.shape[1]
-        pend = _pending_lm_merge.pop(dlm.data_ptr(), None)         # NystromCoreFn.backward left the landmark rows' merge to this node
+        pend = ctx.link.take("lm_merge")         # NystromCoreFn.backward may have left the landmark rows' merge to this node
         merge = None if pend is None else pend[1]
         de = ext_rows_of(dqkv, dlm, P, E, N3, c0, copy_lm=merge is None)
-        if pend is not None and de.data_ptr() != pend[0]:
-            raise K.MirrorHipError("NormQkvLmFn.backward: the pending landmark merge belongs to another gradient buffer (a stale entry "
-                                   "whose address was recycled)")
+        if pend is not None and de.data_ptr() != pend[0].data_ptr():        # (pend[0] is held: its address cannot be recycled)
+            raise K.MirrorHipError("NormQkvLmFn.backward: the pending landmark merge belongs to another gradient buffer")
         dxe = torch.empty((P + E, D), device=x.device, dtype=bf16)
         # data gradient: the pad rows of dxe stay unwritten on the flat path (the LayerNorm backward reads the real rows only)
         if fast:
@@ -1252,7 +1265,7 @@ class NormQkvLmFn(Function):
         db, sunk_b = _gbuf(beta, (D,))
         dy = dxe[:P].view(Bn, n_p, D)
         gadd = dxe[P:].view(Bn, m, D)
-        G = _res_grads.pop(x.data_ptr(), None)
+        G = None if ctx.res is None else ctx.res.take("grad")
         if G is not None and G.numel() == x.numel() and G.dtype == x.dtype and G.is_contiguous():
             # x = Fc1SeqFn's sequence [cls | relu(_fc1(wsi))] (layer 1): the rows behind the cls row leave as the ReLU-masked bf16 gradient
             # _fc1's weight gradient multiplies (Fc1SeqFn.backward picks it up: no pass over x and dx of its own)
@@ -1274,7 +1287,7 @@ class NormQkvLmFn(Function):
                 dx[:, rows:].zero_()         # only the rows the norm never read (a zeros_like of [B, T, D] is a 268 MB fill at config 4)
             K.layernorm_bwd(dy[:, pad:], x, gamma.detach(), mean, rstd, dx, dg, db, Bn, rows, D, T * D, n_p * D, gadd=gadd, pad=pad, l=l,
                             row_mask=ctx.rmask, lm_scale=ctx.lscale)
-        return dx, _gret(gamma, dg, sunk_g), _gret(beta, db, sunk_b), None, None, None, None, dw, None, None, None
+        return dx, _gret(gamma, dg, sunk_g), _gret(beta, db, sunk_b), None, None, None, None, dw, None, None, None, None, None
 
 
 def ext_rows_alloc(Bn: int, n_p: int, m: int, N3: int, c0: int, device):
@@ -1372,9 +1385,10 @@ class _FanSlot:
 
 
 
-def layer_norm(x, gamma, beta, eps, *, rows=None, pad=0, out_dtype=f32, q8_key=None, bf16_copy=False):
+def layer_norm(x, gamma, beta, eps, *, rows=None, pad=0, out_dtype=f32, q8_key=None, bf16_copy=False, res=None):
     """bf16_copy=True (f32 in / f32 out, no padding): the same launch also writes a bf16 copy of the output, attached to the
-    result as `y._bf16` for a consumer that takes bf16 operands (the retention_embed projection) — no cast pass."""
+    result as `y._bf16` for a consumer that takes bf16 operands (the retention_embed projection) — no cast pass; likewise an e4m3
+    copy for q8_key's projection as `y._q8` (_quant_site).  res: the ResidualLink to the block's residual add."""
     squeeze = x.dim() == 2
     if squeeze:
         x = x.unsqueeze(0)
@@ -1384,38 +1398,38 @@ def layer_norm(x, gamma, beta, eps, *, rows=None, pad=0, out_dtype=f32, q8_key=N
             and x.shape[-1] <= 2048 and q8_key is None):
         dual = []
     slot = _FanSlot() if (_FAN_IN_LN_BWD and not squeeze and pad == 0 and out_dtype == f32 and x.dtype == f32) else None
-    y = LayerNormFn.apply(x, gamma, beta, eps, r, pad, out_dtype, q8_key, dual, slot)
+    q8 = [] if q8_key is not None else None
+    y = LayerNormFn.apply(x, gamma, beta, eps, r, pad, out_dtype, q8_key, dual, slot, res, q8)
     if dual:
         y._bf16 = dual[0]
+    if q8:
+        y._q8 = q8[0]
     if slot is not None:
         y._fan_slot = slot        # enc_fanout(y) may leave two of its three gradients here for this node's backward
     return y.squeeze(0) if squeeze else y
 
 
 # ------------------------------------------------------------------ elementwise with autograd
-_res_grads: dict = {}      # data_ptr of a residual-stream tensor -> the gradient tensor its LayerNorm should add into
-
-
 class AddFn(Function):
-    """a + b -> out_dtype (residual adds; a and b may differ in dtype).  residual=True marks `a` as the input of a
-    pre-norm block x + f(LN(x)): the backward then publishes a's gradient for that LayerNorm to accumulate into."""
+    """a + b -> out_dtype (residual adds; a and b may differ in dtype).  residual (a ResidualLink) marks `a` as the input of a
+    pre-norm block x + f(LN(x)): the backward then leaves a's gradient there for that LayerNorm to accumulate into."""
 
     @staticmethod
     def forward(ctx, a, b, out_dtype, residual):
         ctx.da, ctx.db = a.dtype, b.dtype
-        ctx.res_key = a.data_ptr() if (residual and a.is_contiguous()) else None
+        ctx.res = residual if a.is_contiguous() else None
         return K.add(a.contiguous(), b.contiguous(), out_dtype=out_dtype)
 
     @staticmethod
     def backward(ctx, dy):
         dy = dy.contiguous()
         ga = K.cast(dy, ctx.da)
-        if ctx.res_key is not None and ga.dtype == f32:
-            _res_grads[ctx.res_key] = ga
+        if ctx.res is not None and ga.dtype == f32:
+            ctx.res.grad = ga
         return ga, K.cast(dy, ctx.db), None, None
 
 
-def add(a, b, out_dtype=f32, residual=False):
+def add(a, b, out_dtype=f32, residual=None):
     return AddFn.apply(a, b, out_dtype, residual)
 
 
@@ -1543,15 +1557,15 @@ def dropout(x, p: float, training: bool):
 class DropoutAddFn(Function):
     """a + dropout(b) -> f32 in one pass (pre-norm block x + Dropout(to_out(...)), models/mirror.py:312): saves the
     dropped copy of b in the forward and, in the backward, the cast of dy in front of the dropout (the kernel reads the
-    f32 gradient and writes the masked, scaled activation-dtype gradient).  `a`'s gradient is dy itself and is published
-    for the block's LayerNorm to accumulate into (see AddFn)."""
+    f32 gradient and writes the masked, scaled activation-dtype gradient).  `a`'s gradient is dy itself and is left in `res`
+    for the block's LayerNorm to accumulate into (ResidualLink)."""
 
     @staticmethod
-    def forward(ctx, a, b, p, lite=False):
+    def forward(ctx, a, b, p, lite=False, res=None):
         a, b = a.contiguous(), b.contiguous()
         ctx.lite = bool(lite) and b.numel() % 8 == 0        # the lite stream (mh_dropout_lite), the one ToOutDropAddFn's epilogue draws
         ctx.p, ctx.seed, ctx.base = p, _dropout_state["seed"], _dropout_state["base"]
-        ctx.res_key, ctx.db = a.data_ptr(), b.dtype
+        ctx.res, ctx.db = res, b.dtype
         if ctx.lite:
             ctx.offset = _lite_offset()
             _dropout_state["offset"] = ctx.offset + b.numel()
@@ -1570,16 +1584,17 @@ class DropoutAddFn(Function):
             K.dropout_lite(dy, ctx.p, ctx.seed, ctx.offset, ctx.base, out=gb)
         else:
             K.dropout(dy, ctx.p, ctx.seed, ctx.offset, out=gb, dev_base=ctx.base)
-        _res_grads[ctx.res_key] = dy
-        return dy, gb, None, None
+        if ctx.res is not None:
+            ctx.res.grad = dy
+        return dy, gb, None, None, None
 
 
-def dropout_add(a, b, p: float, training: bool, lite: bool = False):
+def dropout_add(a, b, p: float, training: bool, lite: bool = False, res=None):
     """a + dropout(b) with `a` the f32 residual stream of a pre-norm block (falls back to the two-op form otherwise).
     lite=True: the masks of the lite stream (mh_dropout_lite) — the WSI layers, whose fused projection epilogue draws them too."""
     if training and p > 0.0 and a.dtype == f32 and a.shape == b.shape and b.numel() % 4 == 0:
-        return DropoutAddFn.apply(a, b, p, lite)
-    return add(a, dropout(b, p, training), f32, residual=True)
+        return DropoutAddFn.apply(a, b, p, lite, res)
+    return add(a, dropout(b, p, training), f32, residual=res)
 
 
 # ------------------------------------------------------------------ TransMIL sequence assembly
@@ -1847,20 +1862,6 @@ def _pair(first: torch.Tensor, second: torch.Tensor) -> torch.Tensor:
 
 
 _SIM2_MASKED = True      # (test hook, round 5) the one-launch sim2 + softmax + maxima + panels also under a key-padding mask (config 4)
-_pending_lm_merge: dict = {}      # data_ptr of the landmark-gradient view NystromCoreFn.backward returned -> (address of the buffer
-                                  # `de` the merge writes into, its deferred merge launch); see pending_lm_merge_reset
-
-
-def pending_lm_merge_reset(where: str, strict: bool = False) -> None:
-    """Entries left behind (a standalone TransLayer whose NormQkvLmFn never ran its backward, an aborted backward pass) pin tens of MB
-    through their closures and — once the allocator recycles the address — could match a later gradient view.  TrainEngine clears the
-    table at the start of a step and, with strict=True, raises behind loss.backward() if a merge was never consumed."""
-    if _pending_lm_merge:
-        n = len(_pending_lm_merge)
-        _pending_lm_merge.clear()
-        if strict:
-            raise K.MirrorHipError(f"{where}: {n} deferred landmark-gradient merge(s) were never run (NormQkvLmFn.backward did not follow "
-                                   "NystromCoreFn.backward)")
 _RC_FUSED = True      # (test hook) res_conv inside attn3's forward launch, its two gradients as one pass over dout (round 5)
 _A1_DQ_IN_WINDOW = False     # (test hook, round 5) attn1's dq kernel beside the pinv chain's backward: -0.35 % +- 0.02 when it was built, but
                              # +0.80 % +- 0.20 (8 ABBA rounds) on the round's final tree — the one-pass attn3 backward and the other kernels that joined the
@@ -1877,9 +1878,10 @@ class NystromCoreFn(Function):
     (a1 @ a2inv) @ (a3 @ v), 2 m^2 D instead of 2 n_p m^2 h flops)."""
 
     @staticmethod
-    def forward(ctx, qkv, res_w, heads, l, iters, prec, kmask=None, q8_key=None, lm_ext=None):
+    def forward(ctx, qkv, res_w, heads, l, iters, prec, kmask=None, q8_key=None, lm_ext=None, link=None, q8_out=None):
         """lm_ext: the q | k landmarks [B, m, 2D] computed by the caller (NormQkvLmFn: rows of to_qkv's output, row stride 3D); their
         gradient is returned instead of being scattered into dqkv.
+        link: the TransLayer's NystromLink; q8_out: a list that gets the e4m3 copy of the output and its scale (fp8 policy).
         kmask: None, or the package's key-padding mask prepared by TransLayer as (rows [B, n_p], landmarks [B, m],
         landmark scale [B, m]) float tensors: rows of qkv that are masked out are already zero (the caller zeroes the
         LayerNorm output in front of the bias-free to_qkv); here the landmark means become masked means and the three
@@ -1949,7 +1951,9 @@ class NystromCoreFn(Function):
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 zf, saved, st, ctx.a2b = pinv_forward_tile(a2, iters, want_a2b=True)
-        run_deferred(qkv)        # the v columns of to_qkv: nothing above reads them (landmarks are means of q and k)
+        if link is not None:
+            link.core = True
+            link.run("v_cols")       # the v columns of to_qkv: nothing above reads them (landmarks are means of q and k)
         fused = K.nys_fused_ok(qkv, h, m_l) and lm.dtype == bf16      # nystrom_fused.hip: sim1 / sim3 never reach HBM (mask-aware)
         lse1 = lse3 = a1 = a3 = None
         out = torch.empty((Bn, n_p, D), device=qkv.device, dtype=A)
@@ -2011,7 +2015,7 @@ class NystromCoreFn(Function):
             if site is not None and st8["host_step"] - site[1] >= 2:
                 q8 = torch.empty(out.shape, device=out.device, dtype=torch.uint8)
                 lse1, sc8 = K.nys_attn1_fwd_q8(qkv, lm, w2, out, h, scale, True, q8, site[0], st8["tick"], o1=o1)
-                _prequant[out.data_ptr()] = (q8, sc8)
+                q8_out.append((q8, sc8))
             else:
                 lse1 = K.nys_attn1_fwd(qkv, lm, w2, out, h, scale, accumulate=True, kmask=kmask, o1=o1)
         else:
@@ -2024,7 +2028,7 @@ class NystromCoreFn(Function):
         ctx.cfg = (heads, l, prec)
         ctx.chain = (chain, iters, fused)
         ctx.tile = tile
-        ctx.kmask = kmask
+        ctx.kmask, ctx.link = kmask, link
         return out
 
     @staticmethod
@@ -2126,7 +2130,8 @@ class NystromCoreFn(Function):
                 side.wait_event(dZ_ready)
                 dS2 = pinv_backward_tile(a2, saved, st, dZ, getattr(ctx, "a2b", None))
                 sm_bwd(a2, dS2, mlm if kmask else None, mlm if kmask else None)
-        run_deferred_bwd(dout)      # to_out's weight gradient (ToOutDropAddFn left it to us): beside the chain when there is one
+        if ctx.link is not None:
+            ctx.link.run("wgrad")      # to_out's weight gradient (ToOutDropAddFn left it to us): beside the chain when there is one
         if fused and chain and _A1_DQ_IN_WINDOW:
             K.nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dW2, dlm, h, scale, kmask, which=2)     # dq: beside the chain
         rc_bwd_one = fused and _RC_FUSED and A == bf16      # both res_conv gradients in ONE pass over dout, behind attn3's backward
@@ -2170,13 +2175,13 @@ class NystromCoreFn(Function):
             K.gemm(dS2, kl, out=dql, alpha=scale, accumulate=True, mma=pio)
         dres = _gret(res_w, dres, dres_sunk)
         dres = None if dres is None else dres.view_as(res_w)
-        if de is not None and (kmask is None or (lscale is None and dlm2 is not None)):
+        if de is not None and ctx.link is not None and (kmask is None or (lscale is None and dlm2 is not None)):
             # the merge of the two f32 partial sums is also the cast, written as rows [dq_l | dk_l | 0] behind the sequence rows.
             # Nothing but the landmark rows' own products needs it: NormQkvLmFn.backward runs it (and the landmark rows' data gradient)
             # on a parallel branch beside the data gradient of the sequence rows instead of in front of it (-0.24 % +- 0.29)
             merge = lambda: K.lm_merge(dlm, dlm2, de[Bn * n_p:], D3 - 2 * D)      # noqa: E731
-            _pending_lm_merge[dlm_out.data_ptr()] = (de.data_ptr(), merge)
-            return dqkv, dres, None, None, None, None, None, None, dlm_out
+            ctx.link.lm_merge = (de, merge)
+            return dqkv, dres, None, None, None, None, None, None, dlm_out, None, None
         if dlm2 is not None:
             dlm = K.add(dlm, dlm2, out_dtype=A)
         if kmask is not None and lscale is not None:
@@ -2185,10 +2190,10 @@ class NystromCoreFn(Function):
             if de is not None:
                 dlm_out.copy_(dlm)
                 de[Bn * n_p:, 2 * D:].zero_()
-                return dqkv, dres, None, None, None, None, None, None, dlm_out
-            return dqkv, dres, None, None, None, None, None, None, dlm
+                return dqkv, dres, None, None, None, None, None, None, dlm_out, None, None
+            return dqkv, dres, None, None, None, None, None, None, dlm, None, None
         K.landmark_bwd(K.cast(dlm, A), dqkv, l)
-        return dqkv, dres, None, None, None, None, None, None, None
+        return dqkv, dres, None, None, None, None, None, None, None, None, None
 
 
 class RowScaleFn(Function):

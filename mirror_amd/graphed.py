@@ -28,7 +28,6 @@ class GraphedBranch:
         st = Fn._dropout_state
         host_off = st["offset"]
         st["offset"] = 0                 # the branch is the first consumer of the step's dropout offsets
-        Fn._res_grads.clear()
         torch.cuda.synchronize()
         self.g_f = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_f, capture_error_mode="thread_local"):
@@ -47,7 +46,6 @@ class GraphedBranch:
         finally:
             Fn.set_grad_sink(None)
             touched, engine._capturing = engine._capturing, None
-        Fn._res_grads.clear()
         seen, self.params = set(), []
         for i in touched:               # parameters whose gradient the backward graph completes, in completion order
             if i not in seen:

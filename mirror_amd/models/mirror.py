@@ -64,8 +64,8 @@ class _Mlp(nn.Module):
         self.fc2 = nn.Linear(hidden_features, out_features)
         self.drop = drop
 
-    def forward(self, x, prec: Precision, extra_bias: Optional[torch.Tensor] = None, out_dtype=None, residual=None):
-        """residual: the pre-norm block's stream; `residual + drop2(fc2(...))` then comes back as one fused op."""
+    def forward(self, x, prec: Precision, extra_bias: Optional[torch.Tensor] = None, out_dtype=None, residual=None, res=None):
+        """residual: the pre-norm block's stream; `residual + drop2(fc2(...))` then comes back as one fused op (res: its ResidualLink)."""
         h = Fn.gelu(Fn.linear(x, self.fc1.weight, self.fc1.bias, prec=prec))
         h = Fn.dropout(h, self.drop, self.training)
         if isinstance(self.norm, nn.LayerNorm):
@@ -73,7 +73,7 @@ class _Mlp(nn.Module):
         b2 = self.fc2.bias if extra_bias is None else Fn.add(self.fc2.bias, extra_bias.reshape(-1), f32)
         y = Fn.linear(h, self.fc2.weight, b2, prec=prec, out_dtype=out_dtype)
         if residual is not None:
-            return Fn.dropout_add(residual, y, self.drop, self.training)
+            return Fn.dropout_add(residual, y, self.drop, self.training, res=res)
         return Fn.dropout(y, self.drop, self.training)
 
 
@@ -92,12 +92,12 @@ class Attention(nn.Module):
         self.proj = nn.Linear(dim, dim)
         self.proj_drop = proj_drop
 
-    def forward(self, x, prec: Precision, residual=None):
+    def forward(self, x, prec: Precision, residual=None, res=None):
         qkv = Fn.linear(x, self.qkv.weight, self.qkv.bias, prec=prec)
         o = Fn.HeadAttnFn.apply(qkv, self.num_heads)
         y = Fn.linear(o, self.proj.weight, self.proj.bias, prec=prec)
         if residual is not None:
-            return Fn.dropout_add(residual, y, self.proj_drop, self.training)
+            return Fn.dropout_add(residual, y, self.proj_drop, self.training, res=res)
         return Fn.dropout(y, self.proj_drop, self.training)
 
 
@@ -116,10 +116,11 @@ class Block(nn.Module):
         y = Fn.rna_block(x, self, prec, self.training)          # one fused call per direction (csrc/rna_block.hip) when it fits
         if y is not None:
             return y
-        h = Fn.layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps, out_dtype=prec.act)
-        x = self.attn(h, prec, residual=x)                          # x + drop(proj(...)); x feeds exactly norm1 and this add
-        h = Fn.layer_norm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, out_dtype=prec.act)
-        return self.mlp(h, prec, residual=x)
+        r1, r2 = Fn.ResidualLink(), Fn.ResidualLink()      # x feeds exactly norm1 and the add x + drop(proj(...)); likewise norm2
+        h = Fn.layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps, out_dtype=prec.act, res=r1)
+        x = self.attn(h, prec, residual=x, res=r1)
+        h = Fn.layer_norm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, out_dtype=prec.act, res=r2)
+        return self.mlp(h, prec, residual=x, res=r2)
 
 
 class TransFormer(nn.Module):
@@ -192,6 +193,7 @@ class TransLayer(nn.Module):
         pad = (m - n % m) % m
         l = math.ceil(n / m)  # noqa: E741
         lm = kmask = mrow = None
+        link, res = Fn.NystromLink(), Fn.ResidualLink()     # hand-overs between this layer's nodes; x feeds exactly self.norm and the add
         if mask is not None:
             km = mask if isinstance(mask, Fn.KeyMask) else Fn.KeyMask(mask.to(x.device))
             if tuple(km.shape) != tuple(x.shape[:2]):
@@ -204,20 +206,23 @@ class TransLayer(nn.Module):
             # key-padding mask (round 5) the same launch zeroes the masked rows and keeps them out of the landmark sums: no row-scale
             # pass over the norm's output, no landmark pass over q | k (NystromCoreFn scales the sums by l / valid count)
             lsc = None if kmask is None else kmask[2]
-            qkv, lm = Fn.NormQkvLmFn.apply(x, self.norm.weight, self.norm.bias, self.norm.eps, n, pad, l, a.to_qkv.weight, prec, mrow, lsc)
+            qkv, lm = Fn.NormQkvLmFn.apply(x, self.norm.weight, self.norm.bias, self.norm.eps, n, pad, l, a.to_qkv.weight, prec, link,
+                                           mrow, lsc, res)
             if kmask is not None:
                 kmask = (kmask[0], kmask[1], None)      # the landmark rows are masked means already
         else:
             xp = Fn.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps, pad=pad, out_dtype=prec.act,
-                               q8_key=Fn.fp8_site_key(a.to_qkv.weight, prec) if prec.fp8_fwd else None)
+                               q8_key=Fn.fp8_site_key(a.to_qkv.weight, prec) if prec.fp8_fwd else None, res=res)
             if mask is not None:
                 xp = Fn.RowScaleFn.apply(xp, mrow)           # to_qkv has no bias: zero rows in, zero q / k / v rows out
-            qkv = Fn.linear(xp, a.to_qkv.weight, None, prec=prec, defer_from=2 * a.to_qkv.weight.shape[1])
+            qkv = Fn.linear(xp, a.to_qkv.weight, None, prec=prec, defer_from=2 * a.to_qkv.weight.shape[1], link=link)
+        q8 = [] if prec.fp8_fwd else None
         core = Fn.NystromCoreFn.apply(qkv, a.res_conv.weight, a.heads, l, a.pinv_iterations, prec, kmask,
-                                      Fn.fp8_site_key(a.to_out[0].weight, prec) if prec.fp8_fwd else None, lm)
-        # to_out(...)[:, -n:], its Dropout and the residual add: one launch when the shapes allow (Fn.to_out_dropout_add).
-        # x feeds exactly self.norm and this add
-        return Fn.to_out_dropout_add(x, core, a.to_out[0].weight, a.to_out[0].bias, pad, n, a.drop, self.training, prec)
+                                      Fn.fp8_site_key(a.to_out[0].weight, prec) if prec.fp8_fwd else None, lm, link, q8)
+        if q8:
+            core._q8 = q8[0]     # attn1 also wrote the e4m3 copy to_out reads (Fn._quant_site)
+        # to_out(...)[:, -n:], its Dropout and the residual add: one launch when the shapes allow (Fn.to_out_dropout_add)
+        return Fn.to_out_dropout_add(x, core, a.to_out[0].weight, a.to_out[0].bias, pad, n, a.drop, self.training, prec, res, link)
 
 
 class PPEG(nn.Module):
@@ -526,10 +531,7 @@ class MIRROR(nn.Module):
         noise = dict(noise or {})
         if not wsi_emb.is_cuda:
             raise MirrorHipError("mirror_amd models run on MI355X only (no CPU fallback): move the inputs to the GPU")
-        Fn._res_grads.clear()
         Fn.K.shared_chip = False   # a forward that raised between a chain fork and its join must not leave the hint set
-        Fn._deferred.clear()       # hand-over slots of a backward that never completed must not meet this step's tensors
-        Fn._pending_lm_merge.clear()
         # the reference draws: rand(B,N) -> rand(B,D) -> eps_wsi -> eps_rna (models/mirror.py:630, :516, :832-833);
         # draw them up front in that order so the two encoders can then run on different streams
         B, dev = wsi_emb.shape[0], wsi_emb.device

@@ -579,6 +579,150 @@ def test_d512_bucketed_all_reduce_and_rna_graph_world2():
     assert abs(res[0][5] - res[0][6]) < 1e-2 * abs(res[0][5])
 
 
+class _AbortBackward(RuntimeError):
+    pass
+
+
+def test_an_aborted_backward_leaves_no_pending_launch_for_the_next_step(monkeypatch):
+    """to_out's weight gradient is parked by ToOutDropAddFn.backward for NystromCoreFn.backward to launch beside the pinv chain.  A
+    backward aborted in between (a Python exception from a hook on the Nystrom core output) must leave nothing that a later step runs:
+    the next clean step's gradient arena equals the same step on an engine that never saw the abort (a stale launch would add the
+    aborted step's to_out weight gradient a second time)."""
+    import mirror_amd.models as M
+    from mirror_amd import functional as Fn
+    from mirror_amd.engine import TrainEngine
+    from mirror_amd.losses import MIRRORLoss
+    wsi, rna, _ = _batch(4, 5, CFG512)
+    wsi = wsi.to(torch.bfloat16)
+
+    def engine():
+        torch.manual_seed(21)
+        model = M.mirror(**CFG512).cuda().train()
+        eng = TrainEngine(model, MIRRORLoss(), lr=0.0, precision="bf16", graph=False, seed=77, snapshot_grads=True)
+        eng._rna_branch_state = "off"
+        return eng
+
+    def clean_step(eng):
+        Fn.manual_seed(77)          # the same dropout masks and noise draws at every step (lr = 0: the same weights too)
+        eng.step(wsi, rna)
+        torch.cuda.synchronize()
+        return eng.grad_snap.clone()
+
+    orig, armed, kept = Fn.NystromCoreFn.apply, [False], []
+
+    def apply(*args):
+        core = orig(*args)
+        if armed[0] and core.requires_grad:
+            armed[0] = False
+
+            def hook(g):
+                kept.append(g)      # (keeps the gradient's block: the next step's tensors cannot land on its address)
+                raise _AbortBackward("aborted backward")
+            core.register_hook(hook)
+        return core
+    monkeypatch.setattr(Fn.NystromCoreFn, "apply", apply)
+
+    ref = engine()
+    clean_step(ref)
+    want = clean_step(ref)
+    eng = engine()
+    clean_step(eng)
+    Fn.manual_seed(77)
+    armed[0] = True
+    with pytest.raises(_AbortBackward):
+        eng.step(wsi, rna)
+    assert kept and not armed[0]
+    torch.cuda.synchronize()
+    eng._zero_pending = True        # the aborted backward's partial gradients are the caller's to discard
+    got = clean_step(eng)
+    for p, o in zip(eng.params, eng.offsets):
+        a, b = got[o:o + p.numel()], want[o:o + p.numel()]
+        assert float((a - b).norm()) <= 1e-2 * float(b.norm()) + 1e-12, (tuple(p.shape), float((a - b).norm()), float(b.norm()))
+
+
+def _translayer_with_links(monkeypatch):
+    """A train-mode TransLayer(512) on the NormQkvLmFn path, with every NystromLink it makes recorded (weakly) and a counter of the
+    landmark merges that run."""
+    import weakref
+    import mirror_amd.models as M
+    from mirror_amd import functional as Fn
+    made, merges = [], []
+
+    class Spy(Fn.NystromLink):
+        def __init__(self):
+            super().__init__()
+            made.append(weakref.ref(self))
+    monkeypatch.setattr(Fn, "NystromLink", Spy)
+    lm_merge = Fn.K.lm_merge
+    monkeypatch.setattr(Fn.K, "lm_merge", lambda *a, **k: (merges.append(1), lm_merge(*a, **k))[1])
+    torch.manual_seed(3)
+    layer = M.mirror(wsi_embed_dim=32, rna_embed_dim=24, embed_dim=512, wsi_num_tokens=16, rna_num_heads=8,
+                     num_prototypes=10).wsi_encoder.layer1.cuda().train()
+    x = torch.randn(2, 1025, 512, device="cuda").requires_grad_(True)
+    assert Fn.layer_norm_landmarks_ok(x, 1025, 255, 5, Fn.POLICIES["bf16"])
+    return layer, x, made, merges
+
+
+def test_landmark_merge_never_survives_its_backward(monkeypatch):
+    """NystromCoreFn.backward parks the landmark rows' merge on the TransLayer's link for NormQkvLmFn.backward.  A completed backward
+    runs it once and clears it; an aborted one drops it with the graph (the link dies with it): no merge reaches another step."""
+    import gc
+    from mirror_amd import functional as Fn
+    layer, x, made, merges = _translayer_with_links(monkeypatch)
+    prec = Fn.POLICIES["bf16"]
+    y = layer(x, prec)
+    y.backward(torch.randn_like(y))
+    torch.cuda.synchronize()
+    assert len(made) == 1 and len(merges) == 1 and x.grad is not None
+    link = made[0]()
+    assert link is not None and link.lm_merge is None and link.v_cols is None and link.wgrad is None
+    del link, y
+    made.clear()
+
+    orig = Fn.NormQkvLmFn.apply
+
+    def apply(*args):
+        qkv, lm = orig(*args)
+
+        def hook(g):
+            raise _AbortBackward("aborted backward")
+        qkv.register_hook(hook)          # fires behind NystromCoreFn.backward, in front of NormQkvLmFn.backward
+        return qkv, lm
+    monkeypatch.setattr(Fn.NormQkvLmFn, "apply", apply)
+    y = layer(x, prec)
+    with pytest.raises(_AbortBackward):
+        y.backward(torch.randn_like(y))
+    torch.cuda.synchronize()
+    assert len(made) == 1 and len(merges) == 1           # parked, never run
+    assert made[0]() is not None and made[0]().lm_merge is not None
+    del y
+    gc.collect()
+    assert made[0]() is None, "the link (and the merge it holds) outlived its graph"
+
+
+def test_landmark_merge_into_another_gradient_buffer_is_an_error(monkeypatch):
+    """The merge writes into the buffer NystromCoreFn.backward allocated; gradients that arrive as the two row ranges of ANOTHER such
+    buffer pass the structural check of ext_rows_of but are not the buffer the parked merge writes: NormQkvLmFn.backward raises."""
+    from mirror_amd import functional as Fn
+    layer, x, made, merges = _translayer_with_links(monkeypatch)
+    prec = Fn.POLICIES["bf16"]
+    orig = Fn.NormQkvLmFn.apply
+
+    def apply(*args):
+        qkv, lm = orig(*args)
+        (Bn, n_p, N3), m = qkv.shape, lm.shape[1]
+        _, dq2, dl2 = Fn.ext_rows_alloc(Bn, n_p, m, N3, lm.shape[2], qkv.device)
+        qkv.register_hook(lambda g: dq2.copy_(g))
+        lm.register_hook(lambda g: dl2.copy_(g))
+        return qkv, lm
+    monkeypatch.setattr(Fn.NormQkvLmFn, "apply", apply)
+    y = layer(x, prec)
+    with pytest.raises(Fn.K.MirrorHipError, match="another gradient buffer"):
+        y.backward(torch.randn_like(y))
+    torch.cuda.synchronize()
+    assert len(merges) == 0
+
+
 def test_transposed_shadows_are_current_for_a_backward_outside_the_engine():
     """TrainEngine rebuilds the transposed bf16 weight copies at the START of its next step (beside the forward) instead of
     behind Adam.  Code that differentiates through the model between two steps must still see the weights of the last update:

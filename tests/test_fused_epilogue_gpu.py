@@ -36,7 +36,6 @@ def test_to_out_dropout_residual_epilogue_equals_composed(Bn, T, r0, R, Kd, N):
         Fn._dropout_state["offset"] = 4096          # a non-zero call offset
         core, resid = core0.clone().requires_grad_(True), resid0.clone().requires_grad_(True)
         w.grad = b.grad = None
-        Fn._res_grads.clear()
         if fused:
             assert Fn.K.linear_fused_ok(core, Fn.shadow(w, prec), (r0, R))
             y = Fn.ToOutDropAddFn.apply(resid, core, w, b, r0, R, 0.1, prec)
@@ -204,9 +203,10 @@ def test_norm_qkv_with_landmark_rows_and_its_backward(Bn, n, D, m):
     for fused in (True, False):
         x, gm, bt, w = (t.clone().requires_grad_(True) for t in (x0, gm0, bt0, w0))
         if fused:
-            qkv, lm = Fn.NormQkvLmFn.apply(x, gm, bt, 1e-5, n, pad, l, w, prec)
+            link = Fn.NystromLink()
+            qkv, lm = Fn.NormQkvLmFn.apply(x, gm, bt, 1e-5, n, pad, l, w, prec, link)
             assert lm.stride(1) == 3 * D and lm.data_ptr() == qkv.data_ptr() + qkv.numel() * 2      # rows of ONE buffer
-            Fn.run_deferred(qkv)
+            link.run("v_cols")
             # the gradient arrives as NystromCoreFn hands it over: the two row ranges of one [B n_p + B m, 3D] buffer
             de, dq, dl = Fn.ext_rows_alloc(Bn, pad + n, m, 3 * D, 2 * D, x.device)
             dq.copy_(up_q)

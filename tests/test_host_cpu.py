@@ -412,18 +412,21 @@ def test_dropout_step_take_hands_the_offset_to_the_caller_once():
         st.update(saved)
 
 
-def test_pending_landmark_merges_are_cleared_per_step_and_a_leftover_is_an_error():
-    """entries of functional._pending_lm_merge pin their buffers through a closure and are keyed by a raw address; the engine
-    clears the table at the start / end of a step and raises behind backward() when a merge was never consumed."""
+def test_hand_overs_between_nodes_are_links_not_address_tables():
+    """Work and gradients pass between autograd nodes through link objects that both nodes hold and that die with the graph
+    (NystromLink, ResidualLink), never through a module-level table keyed by an address, whose stale entry could meet a recycled
+    block.  The module's dicts are the policies, the step state and the shadow / stream caches, nothing else."""
     from mirror_amd import functional as Fn
-    Fn._pending_lm_merge.clear()
-    Fn._pending_lm_merge[1234] = (5678, lambda: None)
-    Fn.pending_lm_merge_reset("test (lenient)")
-    assert not Fn._pending_lm_merge
-    Fn._pending_lm_merge[1234] = (5678, lambda: None)
-    with pytest.raises(mirror_amd.MirrorHipError, match="never run"):
-        Fn.pending_lm_merge_reset("test (strict)", strict=True)
-    assert not Fn._pending_lm_merge          # cleared even when it raises: the next step starts clean
+    tables = {k for k, v in vars(Fn).items() if isinstance(v, dict) and not k.startswith("__")}
+    assert tables == {"POLICIES", "_dropout_state", "_fp8_state", "_managed_shadows", "_managed_shadows_t", "_shadow_cache",
+                      "_shadow_t_cache", "_side_streams"}, tables
+    link = Fn.NystromLink()
+    ran = []
+    link.v_cols = lambda: ran.append(1)
+    link.run("v_cols")
+    link.run("v_cols")
+    link.run("wgrad")
+    assert ran == [1] and link.v_cols is None      # a pending launch runs once and leaves the link
 
 
 def test_split_k_partials_policy_switch_is_validated(monkeypatch):
