@@ -138,9 +138,7 @@ class ModelEmaV3(nn.Module):
         self._table_key = self._table = None
         self._nrows = 0
         # bf16 copies of the EMA weights (bf16 policies), refreshed by the forward pre-hook
-        self._shadow = self._shadow_t = None
-        self._t_table = None
-        self._published = False
+        self._bf = None
         self._dirty = True
         self._ver = -1
         self.module.register_forward_pre_hook(self._refresh_shadows)
@@ -225,7 +223,6 @@ class ModelEmaV3(nn.Module):
                 total += _pad(src[k].numel())
         arena = torch.zeros(max(total, _ALIGN), device=engine.device, dtype=f32)
         ema_sd = self.module.state_dict(keep_vars=True)
-        self._unpublish()
         with torch.no_grad():
             for k, _ in self._lay:
                 e = ema_sd[k]
@@ -234,7 +231,7 @@ class ModelEmaV3(nn.Module):
                 e.data = arena[o:o + e.numel()].view(e.shape)
         self.arena = arena
         self._lay = [(k, off[k]) for k, _ in self._lay]
-        self._shadow = self._shadow_t = self._t_table = None
+        self._bf = None          # (its copies were published for the blocks the parameters have just left: not served any more)
         rows, cp = [], []
         for k in tail:
             s = src[k].detach()
@@ -257,44 +254,18 @@ class ModelEmaV3(nn.Module):
     def _touch(self) -> None:
         self._dirty = True
 
-    def _unpublish(self) -> None:
-        if self._published:
-            for p in self.module.parameters():
-                Fn.register_shadow(p, None)
-                Fn.register_shadow_t(p, None)
-            self._published = False
-
     def _refresh_shadows(self, module, args) -> None:
         from .models.mirror import resolve_precision
         if resolve_precision(getattr(module, "precision", None)).act != bf16:
             return
         ver = self._versions()
-        if not self._dirty and self._ver == ver and self._published:
+        if not self._dirty and self._ver == ver:
             return
-        if self._shadow is None:
-            self._shadow = torch.zeros(self.arena.numel(), device=self.arena.device, dtype=bf16)
+        if self._bf is None:
             base = self.arena.data_ptr()
-            params = [(p, (p.data_ptr() - base) // 4) for p in module.parameters()]
-            two_d = [(p, o) for p, o in params if p.dim() == 2 and p.shape[0] % 32 == 0 and p.shape[1] % 32 == 0]
-            self._params_at = params
-            self._t_params = two_d
-            if two_d:
-                self._shadow_t = torch.zeros(self.arena.numel(), device=self.arena.device, dtype=bf16)
-                tab = []
-                for p, o in two_d:
-                    tab += [o, o, p.shape[0], p.shape[1]]
-                self._t_table = torch.tensor(tab, dtype=torch.int64).to(self.arena.device)
-                self._t_max = (max(p.shape[0] for p, _ in two_d), max(p.shape[1] for p, _ in two_d))
-        K.cast(self.arena, bf16, out=self._shadow)
-        if self._shadow_t is not None:
-            K.transpose_bf16_many(self._shadow, self._shadow_t, self._t_table, len(self._t_params), self._t_max[0], self._t_max[1],
-                                  vec_ok=True)      # dims % 32 == 0 at offsets that are multiples of _ALIGN = 8
-        if not self._published:
-            for p, o in self._params_at:
-                Fn.register_shadow(p, self._shadow[o:o + p.numel()].view(p.shape))
-            for p, o in self._t_params:
-                Fn.register_shadow_t(p, self._shadow_t[o:o + p.numel()].view(p.shape[1], p.shape[0]))
-            self._published = True
+            self._bf = Fn.ArenaShadows(self.arena, [(p, (p.data_ptr() - base) // 4) for p in module.parameters()])
+            self._bf.publish()
+        self._bf.refresh()
         self._dirty = False
         self._ver = ver
 

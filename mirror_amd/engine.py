@@ -116,7 +116,9 @@ class TrainEngine:
         self.grad = torch.zeros(total, device=self.device, dtype=f32)
         self.m = torch.zeros(total, device=self.device, dtype=f32)
         self.v = torch.zeros(total, device=self.device, dtype=f32)
-        self.shadow = torch.zeros(total, device=self.device, dtype=bf16) if POLICIES[precision].act == bf16 else None
+        # bf16 copies of the master arena, and W^T of the 2-D weights (skinny data-gradient kernels stream them like forward weights)
+        bf = self._bf = Fn.ArenaShadows(self.master, zip(order, offs)) if POLICIES[precision].act == bf16 else None
+        self.shadow, self.shadow_t, self._t_params = (bf.flat, bf.flat_t, bf.t_params) if bf is not None else (None, None, [])
         self.params, self.offsets = order, offs
         # the RNA encoder's parameters (80 % of the arena at c2) are one contiguous range: their gradients are complete when the RNA
         # branch's stream has flushed its deferred weight gradients, ~2 ms before the WSI encoder's last one (see _EARLY_ADAM)
@@ -132,21 +134,8 @@ class TrainEngine:
                 self.master[o:o + n].copy_(p.detach().reshape(-1))
                 p.data = self.master[o:o + n].view(p.shape)
                 p.grad = self.grad[o:o + n].view(p.shape)
-        # W^T shadows of the 2-D weights (skinny data-gradient kernels stream them like forward weights)
-        self.shadow_t = None
         self._zero_pending = False
         self._t_stale = False
-        if self.shadow is not None:
-            two_d = [(p, o) for p, o in zip(order, offs) if p.dim() == 2 and p.shape[1] % 32 == 0 and p.shape[0] % 32 == 0]
-            if two_d:
-                self.shadow_t = torch.zeros(total, device=self.device, dtype=bf16)
-                tab = []
-                for p, o in two_d:
-                    tab += [o, o, p.shape[0], p.shape[1]]
-                self._t_table = torch.tensor(tab, device=self.device, dtype=torch.int64)
-                self._t_n = len(two_d)
-                self._t_max = (max(p.shape[0] for p, _ in two_d), max(p.shape[1] for p, _ in two_d))
-                self._t_params = two_d
         self.sync_shadows()
         # gradient sink: Functions accumulate weight gradients straight into the arena (mirror_amd.functional._gbuf)
         self._slot_of = {p.data_ptr(): i for i, p in enumerate(order)}
@@ -221,13 +210,9 @@ class TrainEngine:
         """(Re)publish the bf16 copies after the master arena was written by anything but step()."""
         if self.shadow is None:
             return
-        K.cast(self.master, bf16, out=self.shadow)
-        for p, o in zip(self.params, self.offsets):
-            Fn.register_shadow(p, self.shadow[o:o + p.numel()].view(p.shape))
-        self._refresh_transposes()
-        if self.shadow_t is not None:
-            for p, o in self._t_params:
-                Fn.register_shadow_t(p, self.shadow_t[o:o + p.numel()].view(p.shape[1], p.shape[0]), owner=self)
+        self._bf.refresh()
+        self._t_stale = False
+        self._bf.publish(owner=self)
 
     def refresh_transposes_now(self) -> None:
         """The transposed copies trail an update until the next step starts (see _step_body); anything that differentiates
@@ -240,9 +225,8 @@ class TrainEngine:
 
     def _refresh_transposes(self) -> None:
         self._t_stale = False
-        if self.shadow_t is not None:
-            K.transpose_bf16_many(self.shadow, self.shadow_t, self._t_table, self._t_n, self._t_max[0], self._t_max[1],
-                                  vec_ok=True)   # 2-D weights with both dims % 32 == 0 at offsets that are multiples of _ALIGN = 8
+        if self._bf is not None:
+            self._bf.refresh_t()
 
     # ------------------------------------------------------------------ gradient sink protocol
     def slot(self, t: torch.Tensor):

@@ -42,86 +42,119 @@ FP8 = Precision("fp8", MH_BF16, bf16, MH_BF16, True)      # bf16 policy + fp8 fo
 POLICIES = {p.name: p for p in (FP32, BF16, BF16_PINV32, FP8)}
 
 # ------------------------------------------------------------------ bf16 shadows of f32 master weights
-# Entries are keyed by (address, shape) and carry a weak reference to the tensor they were made for: an entry is valid only
-# while that tensor is alive — then nothing else can own the address.  (Without it a model built after another one was freed
-# could land on the same addresses and silently pick up the old model's bf16 weights.)
 import weakref
 
-_shadow_cache: dict = {}
+
+class _Shadows:
+    """The bf16 copies of one weight, hung on the weight tensor object itself (`w._shadows`): the record dies with the tensor, so
+    nothing is keyed by an address.  Self-made copies carry the stamp (data_ptr, version) they were made from: `p.data = ...` and
+    `module.to()` re-point a live parameter without moving its version counter.  Kept copies (register_shadow / register_shadow_t)
+    are current by their keeper's word, for the block the weight had at registration only.
+    (Pickling a whole tensor would carry the record; checkpoint.py saves state dicts, which do not.)"""
+    __slots__ = ("own", "own_stamp", "own_t", "own_t_stamp", "kept", "kept_t", "kept_at", "kept_t_at", "owner")
+
+    def __init__(self):
+        self.own = self.own_stamp = self.own_t = self.own_t_stamp = None
+        self.kept = self.kept_t = self.kept_at = self.kept_t_at = self.owner = None
 
 
-def _alive(ref) -> bool:
-    return ref is not None and ref() is not None
+def _shadows_of(w: torch.Tensor) -> _Shadows:
+    rec = getattr(w, "_shadows", None)
+    if rec is None:
+        rec = w._shadows = _Shadows()
+    return rec
 
 
 def shadow(w: torch.Tensor, prec: Precision) -> torch.Tensor:
-    """The weight in the policy's GEMM operand dtype; bf16 copies are cached per (tensor, version)."""
-    wd = w.detach()
-    if wd.dtype == prec.act:
-        return wd
-    key = (wd.data_ptr(), tuple(wd.shape))
-    man = _managed_shadows.get(key)
-    if man is not None:
-        if _alive(man[1]) and man[0].dtype == prec.act:
-            return man[0]
-        if not _alive(man[1]):
-            _managed_shadows.pop(key, None)
-    hit = _shadow_cache.get(key)
-    if hit is not None and _alive(hit[2]) and hit[0] == w._version and hit[1].dtype == prec.act:
-        return hit[1]
-    s = K.cast(wd.contiguous(), prec.act)
-    _shadow_cache[key] = (w._version, s, weakref.ref(w))
-    return s
-
-
-_managed_shadows: dict = {}
-_managed_shadows_t: dict = {}
-_shadow_t_cache: dict = {}
+    """The weight in the policy's GEMM operand dtype; a bf16 copy is the keeper's while one is registered (the identical tensor
+    on every call), else cached on the weight per (address, version)."""
+    if w.dtype == prec.act:
+        return w.detach()
+    rec = _shadows_of(w)
+    at = w.data_ptr()
+    if rec.kept is not None and rec.kept_at == at and rec.kept.dtype == prec.act:
+        return rec.kept
+    stamp = (at, w._version)
+    if rec.own is None or rec.own_stamp != stamp or rec.own.dtype != prec.act:
+        rec.own, rec.own_stamp = K.cast(w.detach().contiguous(), prec.act), stamp
+    return rec.own
 
 
 def shadow_t(w: torch.Tensor, prec: Precision) -> torch.Tensor:
     """bf16 W^T [K, N] of a 2-D master weight (skinny data-gradient path streams it like a forward weight)."""
-    key = (w.data_ptr(), tuple(w.shape))
-    man = _managed_shadows_t.get(key)
-    if man is not None:
-        if _alive(man[1]):
-            owner = man[2]() if len(man) > 2 and man[2] is not None else None
-            if owner is not None and getattr(owner, "_t_stale", False):
-                owner.refresh_transposes_now()      # a backward pass outside TrainEngine.step(): its transposes trail the update
-            return man[0]
-        _managed_shadows_t.pop(key, None)
+    rec = _shadows_of(w)
+    at = w.data_ptr()
+    if rec.kept_t is not None and rec.kept_t_at == at:
+        owner = None if rec.owner is None else rec.owner()
+        if owner is not None and getattr(owner, "_t_stale", False):
+            owner.refresh_transposes_now()      # a backward pass outside TrainEngine.step(): its transposes trail the update
+        return rec.kept_t
     # An optimizer that rewrites the master through raw kernels (TrainEngine: mh_adam) does not bump the version counter:
-    # for a weight whose bf16 shadow it manages but whose transpose it does not (a dimension that is not a multiple of 32),
-    # the cached W^T would be the first step's for ever — transpose the live shadow on every call instead (small weights).
-    engine_managed = key in _managed_shadows
-    hit = _shadow_t_cache.get(key)
-    if not engine_managed and hit is not None and _alive(hit[2]) and hit[0] == w._version:
-        return hit[1]
-    t = K.transpose_bf16(shadow(w, prec).contiguous())
-    if not engine_managed:
-        _shadow_t_cache[key] = (w._version, t, weakref.ref(w))
-    return t
+    # for a weight whose bf16 shadow it keeps but whose transpose it does not (a dimension that is not a multiple of 32),
+    # a cached W^T would be the first step's for ever — transpose the live shadow on every call instead (small weights).
+    if rec.kept is not None and rec.kept_at == at:
+        return K.transpose_bf16(shadow(w, prec).contiguous())
+    stamp = (at, w._version)
+    if rec.own_t is None or rec.own_t_stamp != stamp:
+        rec.own_t, rec.own_t_stamp = K.transpose_bf16(shadow(w, prec).contiguous()), stamp
+    return rec.own_t
 
 
 def register_shadow_t(w: torch.Tensor, t: Optional[torch.Tensor], owner=None) -> None:
     """owner: the engine that keeps `t` current.  It may rebuild the transposes lazily (TrainEngine does it at the start of its
     next step); while its `_t_stale` is set, a lookup from outside one of its steps triggers `owner.refresh_transposes_now()`."""
-    key = (w.data_ptr(), tuple(w.shape))
-    if t is None:
-        _managed_shadows_t.pop(key, None)
-    else:
-        _managed_shadows_t[key] = (t, weakref.ref(w), None if owner is None else weakref.ref(owner))
+    rec = _shadows_of(w)
+    rec.kept_t, rec.kept_t_at = t, w.data_ptr()
+    rec.owner = None if t is None or owner is None else weakref.ref(owner)
 
 
 def register_shadow(w: torch.Tensor, s: Optional[torch.Tensor]) -> None:
     """An optimizer that maintains the bf16 copy itself (mh_adam writes master + shadow in one pass) publishes it
     here; whoever rewrites the master outside that optimizer must refresh the shadow (TrainEngine.sync_shadows).
-    `w` must be the long-lived parameter object: the entry dies with it."""
-    key = (w.data_ptr(), tuple(w.shape))
-    if s is None:
-        _managed_shadows.pop(key, None)
-    else:
-        _managed_shadows[key] = (s, weakref.ref(w))
+    `w` must be the long-lived parameter object: the copy is served to lookups through that object, while it stays on the block it
+    had here."""
+    rec = _shadows_of(w)
+    rec.kept, rec.kept_at = s, w.data_ptr()
+
+
+def keeps_transpose(shape) -> bool:
+    """Whether an ArenaShadows keeps W^T for a weight of this shape: 2-D with both dims multiples of 32 (the 16-byte instance of
+    mh_transpose_bf16_many); shadow_t transposes the others per call."""
+    return len(shape) == 2 and shape[0] % 32 == 0 and shape[1] % 32 == 0
+
+
+class ArenaShadows:
+    """The bf16 copies of a flat f32 arena whose weights are views of it: `flat` (same offsets) and, when any weight qualifies
+    (keeps_transpose), `flat_t` with W^T at the weight's offset.  params_at: (parameter, element offset) pairs, offsets multiples
+    of 8.  Adam and rownorm_ write through `flat`; the owner says when the transposes trail it."""
+
+    def __init__(self, arena: torch.Tensor, params_at):
+        self.arena, self.params_at = arena, list(params_at)
+        self.flat = torch.zeros(arena.numel(), device=arena.device, dtype=bf16)
+        self.t_params = [(p, o) for p, o in self.params_at if keeps_transpose(p.shape)]
+        self.flat_t = None
+        if self.t_params:
+            self.flat_t = torch.zeros(arena.numel(), device=arena.device, dtype=bf16)
+            tab = []
+            for p, o in self.t_params:
+                tab += [o, o, p.shape[0], p.shape[1]]
+            self._table = torch.tensor(tab, dtype=torch.int64).to(arena.device)
+            self._max = (max(p.shape[0] for p, _ in self.t_params), max(p.shape[1] for p, _ in self.t_params))
+
+    def refresh(self) -> None:
+        K.cast(self.arena, bf16, out=self.flat)
+        self.refresh_t()
+
+    def refresh_t(self) -> None:
+        if self.flat_t is not None:
+            K.transpose_bf16_many(self.flat, self.flat_t, self._table, len(self.t_params), self._max[0], self._max[1],
+                                  vec_ok=True)   # keeps_transpose shapes at offsets that are multiples of 8
+
+    def publish(self, owner=None) -> None:
+        for p, o in self.params_at:
+            register_shadow(p, self.flat[o:o + p.numel()].view(p.shape))
+        for p, o in self.t_params:
+            register_shadow_t(p, self.flat_t[o:o + p.numel()].view(p.shape[1], p.shape[0]), owner=owner)
 
 
 # ------------------------------------------------------------------ per-step zero arena
@@ -487,7 +520,7 @@ class LinearFn(Function):
         N, Kd = wa.shape
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            t_managed = N % 32 == 0 and Kd % 32 == 0      # the engine keeps W^T current for these (engine.py: two_d); others are transposed per call
+            t_managed = keeps_transpose(wa.shape)      # the engine keeps W^T current for these; others are transposed per call
             if ctx.skinny and (t_managed or (w.numel() <= (1 << 21) and (N % 32 == 0 or N < 1024))):
                 # (a short N that is no multiple of 32 runs the element-wise instance of the kernel on a W^T that shadow_t transposes per
                 #  call: the engine keeps transposes for multiples of 32 only.  Long ones — the 3000 prototypes, the template's 1975-wide MLP

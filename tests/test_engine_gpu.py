@@ -745,6 +745,53 @@ def test_transposed_shadows_are_current_for_a_backward_outside_the_engine():
     assert checked > 0 and not eng._t_stale
 
 
+def test_bf16_copies_made_before_the_engine_existed_give_way_to_its_own():
+    """A model (and a ModelEmaV3 module) that ran a bf16 forward on its own has bf16 copies of weights on blocks that
+    TrainEngine / ModelEmaV3._attach then free by re-pointing the parameters.  Afterwards every 2-D weight is served from the
+    owner's flat copy (the very slice Adam writes through), equal to the bf16 cast of the master, W^T likewise."""
+    from mirror_amd import functional as Fn
+    from mirror_amd.ema import ModelEmaV3
+    from mirror_amd.engine import TrainEngine
+    from mirror_amd.losses import MIRRORLoss
+    prec = Fn.POLICIES["bf16"]
+    model = _make(3)
+    model.precision = "bf16"
+    wsi, rna, noise = _batch(2, 900)
+    with torch.no_grad():
+        model(wsi, rna, noise=noise)
+    ema = ModelEmaV3(model, decay=0.9)
+    ema.module.precision = "bf16"
+    with torch.no_grad():
+        ema.module(wsi, rna, noise=noise)
+    eng = TrainEngine(model.train(), MIRRORLoss(), lr=1e-2, precision="bf16", graph=False, model_ema=ema)
+
+    def check(pairs, flat):
+        n = 0
+        for p, o in pairs:
+            if p.dim() != 2:
+                continue
+            s = Fn.shadow(p, prec)
+            if flat is not None:
+                assert s.data_ptr() == flat[o:o + p.numel()].data_ptr() == flat.data_ptr() + 2 * o, tuple(p.shape)
+            assert torch.equal(s, p.detach().bfloat16()), tuple(p.shape)
+            assert torch.equal(Fn.shadow_t(p, prec), p.detach().bfloat16().t().contiguous()), tuple(p.shape)
+            n += 1
+        assert n > 4
+
+    def ema_pairs():
+        return [(p, (p.data_ptr() - ema.arena.data_ptr()) // 4) for p in ema.module.parameters()]
+
+    check(zip(eng.params, eng.offsets), eng.shadow)
+    check(ema_pairs(), None)         # no forward since the re-pointing: copies of the new contents, not the kept ones
+    for s in range(2):
+        w, r, nz = _batch(2, 910 + s)
+        eng.step(w.to(torch.bfloat16), r, noise=nz)
+        check(zip(eng.params, eng.offsets), eng.shadow)
+        with torch.no_grad():
+            ema.module(wsi, rna, noise=noise)           # the pre-hook refreshes (and, the first time, rebuilds and publishes) the copies
+        check(ema_pairs(), ema._bf.flat)
+
+
 @pytest.mark.parametrize("graph", [False, True])
 def test_a_backward_outside_step_never_leaks_into_the_next_update(graph):
     """A backward pass between two steps accumulates into the arena views (p.grad).  The engine clears the arena for it

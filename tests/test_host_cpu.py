@@ -415,11 +415,11 @@ def test_dropout_step_take_hands_the_offset_to_the_caller_once():
 def test_hand_overs_between_nodes_are_links_not_address_tables():
     """Work and gradients pass between autograd nodes through link objects that both nodes hold and that die with the graph
     (NystromLink, ResidualLink), never through a module-level table keyed by an address, whose stale entry could meet a recycled
-    block.  The module's dicts are the policies, the step state and the shadow / stream caches, nothing else."""
+    block.  The module's dicts are the policies, the step state and the stream cache, nothing else: the bf16 copies of a weight
+    hang on the weight tensor itself."""
     from mirror_amd import functional as Fn
     tables = {k for k, v in vars(Fn).items() if isinstance(v, dict) and not k.startswith("__")}
-    assert tables == {"POLICIES", "_dropout_state", "_fp8_state", "_managed_shadows", "_managed_shadows_t", "_shadow_cache",
-                      "_shadow_t_cache", "_side_streams"}, tables
+    assert tables == {"POLICIES", "_dropout_state", "_fp8_state", "_side_streams"}, tables
     link = Fn.NystromLink()
     ran = []
     link.v_cols = lambda: ran.append(1)
@@ -427,6 +427,29 @@ def test_hand_overs_between_nodes_are_links_not_address_tables():
     link.run("v_cols")
     link.run("wgrad")
     assert ran == [1] and link.v_cols is None      # a pending launch runs once and leaves the link
+
+
+def test_bf16_copies_of_a_weight_belong_to_the_tensor_object(monkeypatch):
+    """The bf16 copies hang on the weight tensor object: a tensor on a block that a re-pointed parameter left gets its own
+    (tests/shadow_cases.py; the cast and transpose kernels replaced by torch stand-ins), and neither a deep copy of the module
+    nor its state_dict carries another weight's record."""
+    import copy
+    from mirror_amd import functional as Fn
+    from tests.shadow_cases import check_repointed_weights
+    monkeypatch.setattr(Fn.K, "cast", lambda t, dtype, out=None: t.to(dtype))
+    monkeypatch.setattr(Fn.K, "transpose_bf16", lambda t: t.t().contiguous())
+    check_repointed_weights("cpu")
+    lin = torch.nn.Linear(128, 64)
+    Fn.shadow(lin.weight, Fn.BF16)
+    Fn.shadow_t(lin.weight, Fn.BF16)
+    Fn.register_shadow(lin.bias, lin.bias.detach().bfloat16())
+    assert hasattr(lin.weight, "_shadows") and hasattr(lin.bias, "_shadows")
+    twin = copy.deepcopy(lin)
+    assert not hasattr(twin.weight, "_shadows") and not hasattr(twin.bias, "_shadows")
+    assert not any(hasattr(t, "_shadows") for t in lin.state_dict().values())
+    with torch.no_grad():
+        twin.weight.fill_(4.0)
+    assert bool((Fn.shadow(twin.weight, Fn.BF16).float() == 4.0).all()) and bool((Fn.shadow_t(twin.weight, Fn.BF16).float() == 4.0).all())
 
 
 def test_split_k_partials_policy_switch_is_validated(monkeypatch):

@@ -1789,6 +1789,13 @@ def test_shadow_cache_does_not_outlive_its_tensor():
         assert float(Fn.shadow(w3, Fn.BF16).float().mean()) == 0.5
 
 
+def test_shadows_follow_a_repointed_weight_and_never_its_old_block():
+    """The case that does not depend on the allocator (tests/shadow_cases.py): a live parameter is re-pointed with `p.data = ...`
+    and a second tensor sits on its old block with other contents and an equal version counter."""
+    from tests.shadow_cases import check_repointed_weights
+    check_repointed_weights(DEV)
+
+
 def test_attn1_forward_writes_the_e4m3_copy_of_its_output_with_the_delayed_scale():
     """mh_nys_attn1_fwd_q8 == mh_nys_attn1_fwd followed by mh_quant_fp8_delayed on `out` (accumulate mode, as the model calls it):
     same bf16 output and lse, same bytes, scale and ring update."""
