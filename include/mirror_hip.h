@@ -387,7 +387,8 @@ int64_t mh_pinv_chain_workspace_bytes(int BH, int m, int iters, int which);
  * attn1_fwd: out[:, :, head] (+)= softmax_m(scale q k_l^T) w2 (accumulate = 1 adds to what is there, e.g. the res_conv
  *            term computed while the pinv chain was running), lse1 = row logsumexp.
  * attn3_fwd: av = softmax_n(scale q_l k^T) v, lse3.
- * attn1_bwd: two parts, selected by `which` (1, 2 or 3 = both, in this order):
+ * attn1_bwd: selected by `which`.  3 = everything below from ONE kernel that walks the rows once (S, dP and the exponentials computed
+ *   once, q / dO / o1 read once; needs every buffer); 1 and 2 = the two parts as launches of their own:
  *   1: ADDS (f32 atomics) dw2 = P1^T dO and dk_l = dS1^T q into dw2 and the k_l half of dlm, and WRITES delta1[b, h, n] =
  *      sum_l P1 dP1 = sum_d dO[n, d] o1[n, d] — o1 = attn1's own output rows as mh_nys_attn1_fwd(o1 = ..) saved them (the
  *      flash-attention identity).  dw2 is all the pinv chain's backward waits for, so this part runs first.

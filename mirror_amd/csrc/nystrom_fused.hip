@@ -44,11 +44,12 @@ __device__ __forceinline__ bf16x8 frag_kc(const bf16_t* img, int row0, int k0, i
 }
 // A/B fragment, contraction index = image ROW, free index = image column (col0 + lane&31), in the accumulator's k
 // order: element j <-> image row kb + 4 hl + j (j < 4), kb + 8 + 4 hl + (j - 4) (j >= 4)
+template <int PITCH = NP>
 __device__ __forceinline__ bf16x8 frag_tr(const bf16_t* img, int col0, int kb, int lane) {
     const int g16 = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-    const bf16_t* a0 = img + (kb + 4 * (g16 >> 1) + q) * NP + col0 + 16 * (g16 & 1) + 4 * p;
+    const bf16_t* a0 = img + (kb + 4 * (g16 >> 1) + q) * PITCH + col0 + 16 * (g16 & 1) + 4 * p;
     s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a0);
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 8 * NP));
+    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 8 * PITCH));
     s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(bf16x8, v);
 }
@@ -363,7 +364,8 @@ __global__ __launch_bounds__(NT) void nys_a1_fwd_kernel(const bf16_t* __restrict
 // delta[n] = sum_l P1 dP1 is an INPUT (round 5: the dw2 kernel below computes it as sum_d dO[n, d] O1[n, d] from attn1's own saved output
 // rows, the flash-attention identity): with it known a 32-landmark block is finished in one go — S, dP, dS, dq — instead of all 8 blocks'
 // probabilities waiting in 128 registers for a first pass over dP (3 products instead of 4), and nothing the pinv chain needs comes out of
-// this kernel any more, so it runs BESIDE the chain (NystromCoreFn.backward) instead of in front of its fork.
+// this kernel any more, so it CAN run beside the chain (NystromCoreFn.backward, _A1_DQ_IN_WINDOW) instead of in front of its fork.
+// Round 6: mh_nys_attn1_bwd(which = 2) only; the step takes nys_a1_bwd_one_kernel (which = 3), which computes S, dP and dS once for dq, dw2 and dk_l.
 template <bool MASKED>
 __global__ __launch_bounds__(NT, 2) void nys_a1_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ lm,
                                                            const bf16_t* __restrict__ w2, const bf16_t* __restrict__ dout,
@@ -471,6 +473,7 @@ __device__ __forceinline__ void atomic_tile(float* dst, long ld, const f32x16& a
 // grid (splits, B h); wave w owns landmarks [64 w, 64 w + 64).  dw2 = P1^T dO,  dk_l = dS1^T q  (f32 atomics).
 // Also the producer of delta1[n] = sum_l P1 dP1 = sum_d dO[n, d] O1[n, d] (O1 = attn1's own output rows, saved by the forward): eight
 // threads share a row of the dO / O1 tiles they stage anyway.  It runs FIRST (dw2 is what the pinv chain's backward waits for).
+// Round 6: mh_nys_attn1_bwd(which = 1) only; nys_a1_bwd_one_kernel below is this walk plus dq.
 // 8 waves (two per SIMD, 32 landmarks each: round 5 — as 4 waves of 64 landmarks the kernel ran at one wave per SIMD with nothing to
 // cover a wave's softmax arithmetic and LDS traffic).
 constexpr int NTW = 512;
@@ -582,6 +585,165 @@ __global__ __launch_bounds__(NTW) void nys_a1_bwd_dw_kernel(const bf16_t* __rest
                 adk[nb] = MFMA(d1, frag_tr(s_q, 32 * nb, 32 * i + 16, lane), adk[nb]);
             }
         }
+    }
+    float* dwb = dw2 + (long)bh * NM * ND;
+    float* dkb = dlm + (long)b * NM * 2 * D + D + hd * ND;
+#pragma unroll
+    for (int nb = 0; nb < 2; nb++) {
+        atomic_tile(dwb + (long)(32 * wave) * ND + 32 * nb, ND, adw[nb], hl, c);
+        atomic_tile(dkb + (long)(32 * wave) * 2 * D + 32 * nb, 2 * D, adk[nb], hl, c);
+    }
+}
+
+// ============================================================================ attn1 backward in ONE pass (L kernel + LDS hand-over)
+// The dw2 / dk_l kernel and the dq kernel above each compute every logit, every exponential and every dP (7 products per tile, q and dO
+// read twice).  Here the dw2 / dk_l walk (wave w owns landmarks [32 w, 32 w + 32), S and dS come out [query row][landmark] with the landmark
+// on the lane, 128 query rows per step) also leaves dS in an LDS image [landmark][query row] (the lane's own row, four consecutive rows per
+// 8-byte store, as nys_a3_bwd_one_kernel below does).  Behind a barrier the eight waves switch roles: wave w takes 32 of the 128 query rows
+// and 32 of the 64 channels and contracts over ALL 256 landmarks,  dq^T = k_l^T dS,  both operands read with the transposing fragments —
+// 5 products per tile, one exponential pass, q / dO / O1 read once.  128 rows per step and not attn3's 64: there is ONE per-step output
+// (dq) where attn3 has two (dk, dv), and 128 rows x 64 channels are the eight 32 x 32 tiles that give each of the eight waves a whole
+// contraction (at 64 rows four waves would idle in phase 2 or two would split the landmarks and need a third barrier to add the halves).
+// Both per-landmark accumulators (dw2, dk_l: 64 registers) stay in registers beside the fragments; 2 barriers per step; the next step's
+// q / dO / O1 pieces wait in registers during phase 1 and move into the images (with delta1) beside phase 2.  One workgroup per CU
+// (142 KB of LDS).  grid (splits, B h); dw2 / dk_l leave as f32 atomics exactly as from nys_a1_bwd_dw_kernel.
+constexpr int DSP = TR + 8;      // pitch in bf16 of the dS image [landmark][128 query rows]: same bank walk as NP (4 dwords per row)
+template <bool MASKED>
+__global__ __launch_bounds__(NTW) void nys_a1_bwd_one_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ lm,
+                                                             const bf16_t* __restrict__ w2, const bf16_t* __restrict__ dout,
+                                                             const float* __restrict__ lse1, const bf16_t* __restrict__ o1,
+                                                             float* __restrict__ delta1, bf16_t* __restrict__ dqkv,
+                                                             float* __restrict__ dw2, float* __restrict__ dlm, Geo g,
+                                                             int tiles_per_wg) {
+    __shared__ __attribute__((aligned(16))) bf16_t s_kl[NM * NP];
+    __shared__ __attribute__((aligned(16))) bf16_t s_ds[NM * DSP];     // dS [landmark][query row 0..127]
+    __shared__ __attribute__((aligned(16))) bf16_t s_q[TR * NP];
+    __shared__ __attribute__((aligned(16))) bf16_t s_g[TR * NP];
+    __shared__ __attribute__((aligned(16))) float s_lse[TR];
+    __shared__ __attribute__((aligned(16))) float s_del[TR];
+    __shared__ __attribute__((aligned(16))) float s_mr[TR];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 31, hl = lane >> 5;
+    const int bh = blockIdx.y, b = bh / g.h, hd = bh % g.h, D = g.D;
+    const long LD = g.lm_ld;
+    const int ntiles = g.n_p / TR;
+    const int t0 = blockIdx.x * tiles_per_wg, t1 = min(t0 + tiles_per_wg, ntiles);
+    if (t0 >= t1) return;
+    constexpr bool masked = MASKED;
+    const int lq = 32 * wave + c;                  // this lane's landmark (phase 1)
+    const float ml = masked ? g.mlm[(long)b * NM + lq] : 1.f;
+    const bf16_t* klb = lm + (long)b * NM * LD + D + hd * ND;
+    const bf16_t* w2b = w2 + (long)bh * NM * ND;
+#pragma unroll
+    for (int i = 0; i < NM * 8 / NTW; i++) {
+        const int cid = tid + i * NTW, r = cid >> 3, cc = cid & 7;
+        *reinterpret_cast<u32x4*>(s_kl + r * NP + cc * 8) = *reinterpret_cast<const u32x4*>(klb + (long)r * LD + cc * 8);
+    }
+    bf16x8 klf[4], w2f[4];      // B fragments of this wave's 32 landmarks (phase 1)
+#pragma unroll
+    for (int ks = 0; ks < 4; ks++) {
+        klf[ks] = frag_g(klb + (long)lq * LD, 16 * ks, lane);
+        w2f[ks] = frag_g(w2b + (long)lq * ND, 16 * ks, lane);
+    }
+    const bf16_t* qb = qkv + (long)b * g.n_p * 3 * D + hd * ND;
+    const bf16_t* gb = dout + (long)b * g.n_p * D + hd * ND;
+    const bf16_t* ob = o1 + (long)b * g.n_p * D + hd * ND;
+    f32x16 adw[2] = {zero16(), zero16()}, adk[2] = {zero16(), zero16()};
+    constexpr int NCH = TR * 8 / NTW;       // 16-byte pieces of a [128 x 64] tile per thread: rows (tid >> 3) + 64 i, columns 8 (tid & 7) ..
+    const int pr = tid >> 3, pc = tid & 7;
+    u32x4 rq[NCH], rg[NCH], ro[NCH];
+    float rl = 0.f;
+    auto load_tiles = [&](int t) {
+#pragma unroll
+        for (int i = 0; i < NCH; i++) {
+            const long row = (long)t * TR + pr + 64 * i;
+            rq[i] = *reinterpret_cast<const u32x4*>(qb + row * 3 * D + pc * 8);
+            rg[i] = *reinterpret_cast<const u32x4*>(gb + row * D + pc * 8);
+            ro[i] = *reinterpret_cast<const u32x4*>(ob + row * D + pc * 8);
+        }
+        if (tid < TR) rl = lse1[(long)bh * g.n_p + (long)t * TR + tid];
+    };
+    // the waiting pieces -> images; delta of row r from the eight threads (pc = 0 .. 7) that hold its 64 columns of the dO and the O1 tile
+    auto stage_tiles = [&](int t) {
+#pragma unroll
+        for (int i = 0; i < NCH; i++) {
+            const int r = pr + 64 * i;
+            *reinterpret_cast<u32x4*>(s_q + r * NP + pc * 8) = rq[i];
+            *reinterpret_cast<u32x4*>(s_g + r * NP + pc * 8) = rg[i];
+            float d = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; w++) {
+                d += __uint_as_float(rg[i][w] << 16) * __uint_as_float(ro[i][w] << 16);
+                d += __uint_as_float(rg[i][w] & 0xffff0000u) * __uint_as_float(ro[i][w] & 0xffff0000u);
+            }
+            d += __shfl_xor(d, 1, 64);
+            d += __shfl_xor(d, 2, 64);
+            d += __shfl_xor(d, 4, 64);
+            if (pc == 0) {
+                s_del[r] = -d * g.scale;            // staged negated and scaled: the tile arithmetic is two multiply-adds per element
+                delta1[(long)bh * g.n_p + (long)t * TR + r] = d;
+            }
+        }
+        if (tid < TR) {
+            s_lse[tid] = -rl * LOG2E;
+            s_mr[tid] = masked ? g.mrow[(long)b * g.n_p + (long)t * TR + tid] : 1.f;
+        }
+    };
+    load_tiles(t0);
+    stage_tiles(t0);
+    __syncthreads();
+    const int qb2 = wave & 3, dhalf = wave >> 2;      // phase 2 roles: query rows 32 qb2 .., channels 32 dhalf ..
+#pragma unroll 1
+    for (int t = t0; t < t1; t++) {
+        const bool more = t + 1 < t1;
+        if (more) load_tiles(t + 1);
+        // ---- phase 1: this wave's 32 landmarks against the step's 128 query rows, 32 at a time
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const f32x16 lv = rowvals16(s_lse + 32 * i, hl), dv = rowvals16(s_del + 32 * i, hl);      // -lse1 log2(e), -delta1 scale
+            f32x16 s = zero16(), dp = zero16();   // S[q row][landmark], dP[q row][landmark]
+#pragma unroll
+            for (int ks = 0; ks < 4; ks++) {
+                s = MFMA(frag_kc(s_q, 32 * i, 16 * ks, lane), klf[ks], s);
+                dp = MFMA(frag_kc(s_g, 32 * i, 16 * ks, lane), w2f[ks], dp);
+            }
+            if (masked) {
+                const f32x16 vr = rowvals16(s_mr + 32 * i, hl);
+                s = s * g.scale2;
+                mask_fill16(s, vr, ml);
+                s = s + lv;
+                exp2_16(s);
+                dp = s * (dp * g.scale + dv);
+                mask_zero16(dp, vr, ml);
+            } else {
+                s = s * g.scale2 + lv;
+                exp2_16(s);
+                dp = s * (dp * g.scale + dv);
+            }
+            const bf16x8 p0 = pack8<0>(s), p1 = pack8<1>(s), d0 = pack8<0>(dp), d1 = pack8<1>(dp);
+#pragma unroll
+            for (int nb = 0; nb < 2; nb++) {
+                adw[nb] = MFMA(p0, frag_tr(s_g, 32 * nb, 32 * i, lane), adw[nb]);
+                adw[nb] = MFMA(p1, frag_tr(s_g, 32 * nb, 32 * i + 16, lane), adw[nb]);
+                adk[nb] = MFMA(d0, frag_tr(s_q, 32 * nb, 32 * i, lane), adk[nb]);
+                adk[nb] = MFMA(d1, frag_tr(s_q, 32 * nb, 32 * i + 16, lane), adk[nb]);
+            }
+            // the lane's own image row (its landmark), query rows 32 i + 8 gq + 4 hl + {0..3}: packed element 4 gq + e of d0 | d1 is
+            // accumulator register 4 gq + e = row 8 gq + 4 hl + e
+            bf16_t* drow = s_ds + lq * DSP + 32 * i + 4 * hl;
+            const u32x4 dw0 = __builtin_bit_cast(u32x4, d0), dw1 = __builtin_bit_cast(u32x4, d1);
+            *reinterpret_cast<u32x2*>(drow) = u32x2{dw0[0], dw0[1]};
+            *reinterpret_cast<u32x2*>(drow + 8) = u32x2{dw0[2], dw0[3]};
+            *reinterpret_cast<u32x2*>(drow + 16) = u32x2{dw1[0], dw1[1]};
+            *reinterpret_cast<u32x2*>(drow + 24) = u32x2{dw1[2], dw1[3]};
+        }
+        __syncthreads();      // the dS image is complete; nobody reads s_q / s_g / the row vectors any more
+        // ---- phase 2: dq^T, query rows 32 qb2 .., channels 32 dhalf .., over all 256 landmarks; the next tiles move in beside it
+        if (more) stage_tiles(t + 1);
+        f32x16 a2 = zero16();      // dq^T [d][query row]
+#pragma unroll
+        for (int kt = 0; kt < NM / 16; kt++) a2 = MFMA(frag_tr(s_kl, 32 * dhalf, 16 * kt, lane), frag_tr<DSP>(s_ds, 32 * qb2, 16 * kt, lane), a2);
+        store_row8(dqkv + ((long)b * g.n_p + (long)t * TR + 32 * qb2 + c) * 3 * D + hd * ND + 32 * dhalf, a2, hl);
+        __syncthreads();      // the dS image may be overwritten; the next tiles are in place
     }
     float* dwb = dw2 + (long)bh * NM * ND;
     float* dkb = dlm + (long)b * NM * 2 * D + D + hd * ND;
@@ -1243,11 +1405,18 @@ extern "C" int mh_nys_attn1_bwd(const void* qkv, const void* lm, const void* w2,
                                 int n_p, int m, int dh, float scale, int64_t lm_ld, int which, mh_stream s) {
     if (int e = check_geo("mh_nys_attn1_bwd", B, h, n_p, m, dh)) return e;
     MH_REQUIRE(lm_ld == 0 || (lm_ld >= 2L * h * ND && lm_ld % 8 == 0), "mh_nys_attn1_bwd: lm_ld must be 0 or a multiple of 8 >= 2 D");
-    MH_REQUIRE(which >= 1 && which <= 3, "mh_nys_attn1_bwd: which = 1 (dw2, dk_l, delta1), 2 (dq from delta1) or 3 (both, in that order)");
+    MH_REQUIRE(which >= 1 && which <= 3, "mh_nys_attn1_bwd: which = 1 (dw2, dk_l, delta1), 2 (dq from delta1) or 3 (all of them from the one-pass kernel)");
     MH_REQUIRE(delta1 && (!(which & 1) || (o1 && dw2 && dlm && (((uintptr_t)o1) & 15) == 0)) && (!(which & 2) || dqkv),
                "mh_nys_attn1_bwd: missing buffer for the requested part");
     if (B == 0) return MH_OK;
     const Geo g{h, n_p, h * ND, scale, scale * LOG2E, mrow, mlm, 0, lm_ld > 0 ? lm_ld : 2L * h * ND, nullptr, nullptr};
+    if (which == 3) {      // both parts: one pass over the rows
+        const int ntiles = n_p / TR, splits = pick_splits(B * h, ntiles, 1), tpw = (ntiles + splits - 1) / splits;
+        NYS_LAUNCH(nys_a1_bwd_one_kernel, dim3(splits, B * h), dim3(NTW), 0, (hipStream_t)s, (const bf16_t*)qkv, (const bf16_t*)lm,
+                           (const bf16_t*)w2, (const bf16_t*)dout, lse1, (const bf16_t*)o1, delta1, (bf16_t*)dqkv, dw2, dlm, g, tpw);
+        MH_LAUNCH_CHECK("mh_nys_attn1_bwd(one pass)");
+        return MH_OK;
+    }
     if (which & 1) {
         const int ntiles = n_p / TR, splits = pick_splits(B * h, ntiles, 1), tpw = (ntiles + splits - 1) / splits;
         NYS_LAUNCH(nys_a1_bwd_dw_kernel, dim3(splits, B * h), dim3(NTW), 0, (hipStream_t)s, (const bf16_t*)qkv,

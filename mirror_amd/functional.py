@@ -2110,10 +2110,10 @@ class NystromCoreFn(Function):
             dW2 = zeros((Bn, h, m, dh), qkv.device)
             dlm = zeros((Bn, m, 2 * D), qkv.device)
             delta1 = torch.empty_like(lse1)
-            # dW2 and dk_l (+ delta1 from the saved rows of attn1): all the chain's backward waits for.  dq follows BESIDE the chain
-            K.nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dW2, dlm, h, scale, kmask, which=1)
-            if not (chain and _A1_DQ_IN_WINDOW):
-                K.nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dW2, dlm, h, scale, kmask, which=2)
+            # dW2 and dk_l (+ delta1 from the saved rows of attn1) are all the chain's backward waits for; dq comes out of the same pass
+            # over the rows (round 6: one kernel in front of the fork).  Only the hook that moves dq beside the chain takes the parts apart
+            K.nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dW2, dlm, h, scale, kmask,
+                            which=1 if (chain and _A1_DQ_IN_WINDOW) else 3)
         else:
             dW2 = K.gemm(tr(a1), dO, mma=mma, out_dtype=f32)                             # [B,h,m,dh]
             dlm = torch.empty((Bn, m, 2 * D), device=qkv.device, dtype=f32)

@@ -1168,8 +1168,9 @@ def nys_attn3_fwd(qkv, lm, heads: int, scale: float, kmask=None, rc=None):
 
 
 def nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dw2, dlm, heads: int, scale: float, kmask=None, which: int = 3) -> None:
-    """attn1's backward in two parts (mh_nys_attn1_bwd): which & 1 — ADDS into dw2 and into the k_l half of dlm (both f32, zeroed by the
-    caller) and WRITES delta1 [B, h, n_p] from the forward's saved rows o1; which & 2 — writes the q block of dqkv from delta1."""
+    """attn1's backward (mh_nys_attn1_bwd): which = 1 — ADDS into dw2 and into the k_l half of dlm (both f32, zeroed by the
+    caller) and WRITES delta1 [B, h, n_p] from the forward's saved rows o1; which = 2 — writes the q block of dqkv from delta1;
+    which = 3 (default) — all of it from ONE kernel that walks the rows once (5 products per tile instead of 4 + 3)."""
     _chk(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dw2, dlm)
     B, n_p, _ = qkv.shape
     ts = dict(qkv=qkv, lm=lm, w2=w2, dout=dout, lse1=lse1, delta1=delta1)
@@ -1178,7 +1179,7 @@ def nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dw2, dlm, heads: in
     if which & 2:
         ts.update(dqkv=dqkv)
     _nys_check("nys_attn1_bwd", B, heads, n_p, **ts)
-    prods = (4 if which & 1 else 0) + (3 if which & 2 else 0)
+    prods = 5 if which == 3 else (4 if which & 1 else 0) + (3 if which & 2 else 0)
     _nys_launch("nys_a1_bwd_kernels", prods * 2.0 * n_p * NYS_FUSED_M * NYS_FUSED_DH * B * heads,
                 lambda: _lib.call("mh_nys_attn1_bwd", _p(qkv), _p(lm), _p(w2), _p(dout), _p(lse1), _p(o1), _p(delta1), _p(dqkv),
                                   _p(dw2), _p(dlm), *_nys_masks(kmask, B, n_p), B, heads, n_p, NYS_FUSED_M, NYS_FUSED_DH, scale,
