@@ -33,7 +33,7 @@ extern "C" {
 typedef void* mh_stream; /* hipStream_t */
 
 const char* mh_last_error(void);
-int mh_version(void);
+int mh_version(void);       /* 121 */
 int mh_exp_build(void);      /* 1: built with -DMH_EXP (timing-experiment switches compiled in); the shipped build returns 0 */
 /* number of visible HIP devices whose arch is gfx950; <=0 means the library cannot run here */
 int mh_device_ok(void);
@@ -387,12 +387,10 @@ int64_t mh_pinv_chain_workspace_bytes(int BH, int m, int iters, int which);
  * attn1_fwd: out[:, :, head] (+)= softmax_m(scale q k_l^T) w2 (accumulate = 1 adds to what is there, e.g. the res_conv
  *            term computed while the pinv chain was running), lse1 = row logsumexp.
  * attn3_fwd: av = softmax_n(scale q_l k^T) v, lse3.
- * attn1_bwd: selected by `which`.  3 = everything below from ONE kernel that walks the rows once (S, dP and the exponentials computed
- *   once, q / dO / o1 read once; needs every buffer); 1 and 2 = the two parts as launches of their own:
- *   1: ADDS (f32 atomics) dw2 = P1^T dO and dk_l = dS1^T q into dw2 and the k_l half of dlm, and WRITES delta1[b, h, n] =
- *      sum_l P1 dP1 = sum_d dO[n, d] o1[n, d] — o1 = attn1's own output rows as mh_nys_attn1_fwd(o1 = ..) saved them (the
- *      flash-attention identity).  dw2 is all the pinv chain's backward waits for, so this part runs first.
- *   2: writes the q block of dqkv = dS1 k_l from delta1 (a single pass: 3 products); nothing the chain needs — it can run beside it.
+ * attn1_bwd: ONE kernel that walks the rows once (S, dP and the exponentials computed once, q / dO / o1 read once; needs every buffer).
+ *   ADDS (f32 atomics) dw2 = P1^T dO and dk_l = dS1^T q into dw2 and the k_l half of dlm, WRITES delta1[b, h, n] = sum_l P1 dP1 =
+ *   sum_d dO[n, d] o1[n, d] — o1 = attn1's own output rows as mh_nys_attn1_fwd(o1 = ..) saved them (the flash-attention identity) —
+ *   and writes the q block of dqkv = dS1 k_l.
  * attn3_bwd: writes the k and v blocks of dqkv and delta3 [B,h,m] f32 (scratch); ADDS into the q_l half of dlm. */
 /* mrow [B, n_p] / mlm [B, m] (f32 0 / 1, both or neither): the package's key-padding mask — valid sequence rows and landmark
  * groups that contain a valid row.  A logit whose row or landmark is invalid is masked_fill'ed before the softmax (a fully
@@ -401,7 +399,7 @@ int64_t mh_pinv_chain_workspace_bytes(int BH, int m, int iters, int which);
  * to_qkv's output buffer behind the sequence (landmarks = to_qkv(group means): [3P] landmarks are means over l consecutive
  * positions of q and k, and to_qkv is linear and bias-free); batch b's landmarks start at lm + b * m * lm_ld. */
 /* o1 (nullable, bf16 [B, n_p, D]): attn1's own rows softmax(scale q k_l^T) w2, WITHOUT whatever `out` held under accumulate = 1
- * (res_conv(v)): what mh_nys_attn1_bwd part 1 takes delta1 from. */
+ * (res_conv(v)): what mh_nys_attn1_bwd takes delta1 from. */
 int mh_nys_attn1_fwd(const void* qkv, const void* lm, const void* w2, void* out, float* lse1, const float* mrow, const float* mlm,
                      int B, int h, int n_p, int m, int dh, float scale, int accumulate, int64_t lm_ld, void* o1, mh_stream s);
 /* unmasked mh_nys_attn1_fwd that also writes the e4m3 copy q8 [B, n_p, D] bytes of `out` (delayed scaling: ring / tick / margin as
@@ -421,13 +419,13 @@ int mh_nys_attn3_fwd(const void* qkv, const void* lm, float* av, float* lse3, fl
                      const float* rc_w, void* rc_out, mh_stream s);
 int mh_nys_attn1_bwd(const void* qkv, const void* lm, const void* w2, const void* dout, const float* lse1, const void* o1, float* delta1,
                      void* dqkv, float* dw2, float* dlm, const float* mrow, const float* mlm, int B, int h, int n_p, int m, int dh,
-                     float scale, int64_t lm_ld, int which, mh_stream s);
+                     float scale, int64_t lm_ld, mh_stream s);
 /* av == NULL: delta3 already holds sum_d dav av (mh_nys_dz_dav wrote it); otherwise it is scratch this call fills first */
-/* one_pass != 0 (round 5): dk, dv and dq_l from ONE kernel (every logit / dP / exponential computed once, k and v read once: the
- * landmark-owning waves hand P and dS to the key-owning role through two LDS images); 0: the dk / dv kernel + the dq_l kernel */
+/* dk, dv and dq_l from ONE kernel (every logit / dP / exponential computed once, k and v read once: the landmark-owning waves hand P
+ * and dS to the key-owning role through two LDS images) */
 int mh_nys_attn3_bwd(const void* qkv, const void* lm, const float* av, const void* dav, const float* lse3, float* delta3,
                      void* dqkv, float* dlm, const float* mrow, const float* mlm, int B, int h, int n_p, int m, int dh,
-                     float scale, int64_t lm_ld, int one_pass, mh_stream s);
+                     float scale, int64_t lm_ld, mh_stream s);
 /* out[r, 0:cols] = bf16(a[r] + b[r]) (f32 [rows, cols], b may be NULL) at row stride out_ld, out[r, cols:cols + zero_cols] = 0: the
  * landmark gradient (q_l | k_l halves from the attention kernels + sim2's products) written as rows [dq_l | dk_l | 0] of to_qkv's
  * output gradient, where its data / weight gradient products pick it up together with the sequence rows. */

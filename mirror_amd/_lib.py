@@ -133,8 +133,8 @@ _SIGS = {
     "mh_nys_attn1_fwd": [P, P, P, P, P, P, P, I, I, I, I, I, F, I, L, P],
     "mh_nys_attn1_fwd_q8": [P, P, P, P, P, I, I, I, I, I, F, I, P, P, P, F, P, P],
     "mh_nys_attn3_fwd": [P, P, P, P, P, L, P, P, I, I, I, I, I, F, L, P, P],
-    "mh_nys_attn1_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, L, I],
-    "mh_nys_attn3_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, L, I],
+    "mh_nys_attn1_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, L],
+    "mh_nys_attn3_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, L],
     "mh_seq_finish": [P, P, I, I, I, I, I],
     "mh_seq_finish_bwd": [P, P, I, I, I, I, I],
     "mh_ppeg_merge": [P, P, P, P, P, P, P, P, I],
@@ -213,7 +213,7 @@ _lib = None
 # The ABI generation this binding was written against (mh_version() of csrc/errors.cpp).  _SIGS above restates the argument lists of
 # include/mirror_hip.h by hand: a library built from another generation would be called with shifted arguments (a stream where a
 # counter belongs) and corrupt device memory silently, so load() refuses anything but this exact number.
-ABI_VERSION = 120
+ABI_VERSION = 121
 
 
 class MirrorHipError(RuntimeError):

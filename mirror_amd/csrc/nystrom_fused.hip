@@ -16,10 +16,11 @@
 // kb + 8 + 4 hl + {0..3}) with ds_read_b64_tr_b16.  Which index must be contracted decides the orientation:
 //   N kernels (the landmark images are staged once per workgroup, then every wave walks its own 32-row blocks of the
 //   sequence: n in lanes, the 256 landmarks pass through registers 32 at a time):
-//       attn1 fwd (online softmax over landmark blocks), attn1 bwd dq (+ delta), attn3 bwd dk/dv
+//       attn1 fwd (online softmax over landmark blocks)
 //   L kernels (wave owns 64 landmark columns in lanes and walks 128-row tiles of the sequence, n in registers; the
 //   sequence is cut into ranges over several workgroups per (b, h)):
-//       attn3 fwd (online softmax + nys_a3_combine), attn1 bwd dw2/dk_l, attn3 bwd dq_l
+//       attn3 fwd (online softmax + nys_a3_combine), phase 1 of the two backward kernels (phase 2 contracts over the
+//       landmarks from LDS images of dS / P)
 // Every kernel has a MASKED instance for the package's key-padding mask (BASELINE config 4), see Geo.
 // Layout (SURVEY.md §8 / DESIGN.md §4): qkv [B, n_p, 3D] bf16, heads are 64-wide column slices; landmarks lm
 // [B, m, 2D] = q_l | k_l; w2, av, dav [B, h, m, 64]; out / dout [B, n_p, D].
@@ -324,7 +325,7 @@ __global__ __launch_bounds__(NT) void nys_a1_fwd_kernel(const bf16_t* __restrict
         for (int nb = 0; nb < 2; nb++) {
             o[nb] *= inv;
             // o1: attn1's OWN rows (without the res_conv addend), bf16: the backward takes delta[n] = sum_l P dP = sum_d dO[n, d] O1[n, d]
-            // from them (attn1 backward, dw2 kernel), so the dq kernel needs no first pass over dP and can run after the pinv chain's fork
+            // from them (nys_a1_bwd_one_kernel), so the backward needs no first pass over dP
             if (o1) store_row8(o1 + ((long)b * g.n_p + row) * D + hd * ND + 32 * nb, o[nb], hl);
 #pragma unroll
             for (int gq = 0; gq < 4; gq++) {
@@ -359,254 +360,31 @@ __global__ __launch_bounds__(NT) void nys_a1_fwd_kernel(const bf16_t* __restrict
     }
 }
 
-// ============================================================================ attn1 backward, dq (N kernel)
-// grid (splits, B h), same walk as the forward.  dS1 = P1 o (dO w2^T - delta) scale,  dq = dS1 k_l.
-// delta[n] = sum_l P1 dP1 is an INPUT (round 5: the dw2 kernel below computes it as sum_d dO[n, d] O1[n, d] from attn1's own saved output
-// rows, the flash-attention identity): with it known a 32-landmark block is finished in one go — S, dP, dS, dq — instead of all 8 blocks'
-// probabilities waiting in 128 registers for a first pass over dP (3 products instead of 4), and nothing the pinv chain needs comes out of
-// this kernel any more, so it CAN run beside the chain (NystromCoreFn.backward, _A1_DQ_IN_WINDOW) instead of in front of its fork.
-// Round 6: mh_nys_attn1_bwd(which = 2) only; the step takes nys_a1_bwd_one_kernel (which = 3), which computes S, dP and dS once for dq, dw2 and dk_l.
-template <bool MASKED>
-__global__ __launch_bounds__(NT, 2) void nys_a1_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ lm,
-                                                           const bf16_t* __restrict__ w2, const bf16_t* __restrict__ dout,
-                                                           const float* __restrict__ lse1, const float* __restrict__ delta1,
-                                                           bf16_t* __restrict__ dqkv, Geo g) {
-    __shared__ __attribute__((aligned(16))) bf16_t s_kl_[NM * NP];
-    __shared__ __attribute__((aligned(16))) bf16_t s_w2_[NM * NP];
-    __shared__ __attribute__((aligned(16))) float s_mlm_[NM];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 31, hl = lane >> 5;
-    const int bh = blockIdx.y, b = bh / g.h, hd = bh % g.h, D = g.D;
-    const long LD = g.lm_ld;
-    stage_rows<NM>(s_kl_, lm + (long)b * NM * LD + D + hd * ND, LD, tid);
-    stage_rows<NM>(s_w2_, w2 + (long)bh * NM * ND, ND, tid);
-    constexpr bool masked = MASKED;
-    s_mlm_[tid] = masked ? g.mlm[(long)b * NM + tid] : 1.f;
-    const int nblk = g.n_p / 32, stride = 4 * gridDim.x;
-    int rb = 4 * blockIdx.x + wave;
-    const bf16_t* qb = qkv + (long)b * g.n_p * 3 * D + hd * ND;
-    const bf16_t* gb = dout + (long)b * g.n_p * D + hd * ND;
-    bf16x8 qn[4], gn[4];
-    float lsen = 0.f, deln = 0.f;
-    if (rb < nblk) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) {
-            qn[ks] = frag_g(qb + (long)(32 * rb + c) * 3 * D, 16 * ks, lane);
-            gn[ks] = frag_g(gb + (long)(32 * rb + c) * D, 16 * ks, lane);
-        }
-        lsen = lse1[(long)bh * g.n_p + 32 * rb + c];
-        deln = delta1[(long)bh * g.n_p + 32 * rb + c];
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (; rb < nblk; rb += stride) {
-        const long row = 32L * rb + c;
-        int opq = 0;                      // see nys_a1_fwd_kernel
-        asm volatile("" : "+v"(opq));
-        const bf16_t* s_kl = s_kl_ + opq;
-        const bf16_t* s_w2 = s_w2_ + opq;
-        const float* s_mlm = s_mlm_ + opq;
-        const float mr = masked ? g.mrow[(long)b * g.n_p + row] : 1.f;
-        bf16x8 qf[4], gf[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) { qf[ks] = qn[ks]; gf[ks] = gn[ks]; }
-        const float lse2 = lsen * LOG2E, dsc = deln * g.scale;
-        if (rb + stride < nblk) {
-            const long nrow = 32L * (rb + stride) + c;
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) {
-                qn[ks] = frag_g(qb + nrow * 3 * D, 16 * ks, lane);
-                gn[ks] = frag_g(gb + nrow * D, 16 * ks, lane);
-            }
-            lsen = lse1[(long)bh * g.n_p + nrow];
-            deln = delta1[(long)bh * g.n_p + nrow];
-        }
-        f32x16 dq[2] = {zero16(), zero16()};   // dq^T[d][q row]
-        // the two logits products of block blk + 1 are issued before the softmax arithmetic of block blk (as the forward does)
-        f32x16 sn = zero16(), dpn = zero16();   // S^T, dP^T [landmark 32 blk ..][q row]
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) {
-            sn = MFMA(frag_kc(s_kl, 0, 16 * ks, lane), qf[ks], sn);
-            dpn = MFMA(frag_kc(s_w2, 0, 16 * ks, lane), gf[ks], dpn);
-        }
-#pragma unroll
-        for (int blk = 0; blk < 8; blk++) {
-            f32x16 sb = sn, dp = dpn;
-            if (blk + 1 < 8) {
-                sn = zero16();
-                dpn = zero16();
-#pragma unroll
-                for (int ks = 0; ks < 4; ks++) {
-                    sn = MFMA(frag_kc(s_kl, 32 * (blk + 1), 16 * ks, lane), qf[ks], sn);
-                    dpn = MFMA(frag_kc(s_w2, 32 * (blk + 1), 16 * ks, lane), gf[ks], dpn);
-                }
-            }
-            if (masked) {
-                sb = sb * g.scale2;
-                mask_fill16(sb, rowvals16(s_mlm + 32 * blk, hl), mr);
-                sb = fma_splat(sb, 1.f, -lse2);
-            } else {
-                sb = fma_splat(sb, g.scale2, -lse2);
-            }
-            exp2_16(sb);
-            dp = sb * fma_splat(dp, g.scale, -dsc);
-            if (masked) mask_zero16(dp, rowvals16(s_mlm + 32 * blk, hl), mr);
-            const bf16x8 d0 = pack8<0>(dp), d1 = pack8<1>(dp);
-#pragma unroll
-            for (int nb = 0; nb < 2; nb++) {
-                dq[nb] = MFMA(frag_tr(s_kl, 32 * nb, 32 * blk, lane), d0, dq[nb]);
-                dq[nb] = MFMA(frag_tr(s_kl, 32 * nb, 32 * blk + 16, lane), d1, dq[nb]);
-            }
-        }
-        bf16_t* drow = dqkv + ((long)b * g.n_p + row) * 3 * D + hd * ND;
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++) store_row8(drow + 32 * nb, dq[nb], hl);
-    }
-}
-
 // accumulator [rows in registers][cols in lanes] -> f32 atomics into dst[row * ld + col]
 __device__ __forceinline__ void atomic_tile(float* dst, long ld, const f32x16& a, int hl, int c) {
 #pragma unroll
     for (int r = 0; r < 16; r++) atomicAdd(dst + (long)(8 * (r >> 2) + 4 * hl + (r & 3)) * ld + c, a[r]);
 }
 
-// ============================================================================ attn1 backward, dw2 + dk_l (L kernel)
-// grid (splits, B h); wave w owns landmarks [64 w, 64 w + 64).  dw2 = P1^T dO,  dk_l = dS1^T q  (f32 atomics).
-// Also the producer of delta1[n] = sum_l P1 dP1 = sum_d dO[n, d] O1[n, d] (O1 = attn1's own output rows, saved by the forward): eight
-// threads share a row of the dO / O1 tiles they stage anyway.  It runs FIRST (dw2 is what the pinv chain's backward waits for).
-// Round 6: mh_nys_attn1_bwd(which = 1) only; nys_a1_bwd_one_kernel below is this walk plus dq.
-// 8 waves (two per SIMD, 32 landmarks each: round 5 — as 4 waves of 64 landmarks the kernel ran at one wave per SIMD with nothing to
-// cover a wave's softmax arithmetic and LDS traffic).
-constexpr int NTW = 512;
-template <bool MASKED>
-__global__ __launch_bounds__(NTW) void nys_a1_bwd_dw_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ lm,
-                                                            const bf16_t* __restrict__ w2, const bf16_t* __restrict__ dout,
-                                                            const float* __restrict__ lse1, const bf16_t* __restrict__ o1,
-                                                            float* __restrict__ delta1,
-                                                            float* __restrict__ dw2, float* __restrict__ dlm, Geo g,
-                                                            int tiles_per_wg) {
-    __shared__ __attribute__((aligned(16))) bf16_t s_q[TR * NP];
-    __shared__ __attribute__((aligned(16))) bf16_t s_g[TR * NP];
-    __shared__ __attribute__((aligned(16))) float s_lse[TR];
-    __shared__ __attribute__((aligned(16))) float s_del[TR];
-    __shared__ __attribute__((aligned(16))) float s_mr[TR];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 31, hl = lane >> 5;
-    const int bh = blockIdx.y, b = bh / g.h, hd = bh % g.h, D = g.D;
-    const long LD = g.lm_ld;
-    const int ntiles = g.n_p / TR;
-    const int t0 = blockIdx.x * tiles_per_wg, t1 = min(t0 + tiles_per_wg, ntiles);
-    if (t0 >= t1) return;
-    constexpr bool masked = MASKED;
-    const int lq = 32 * wave + c;                  // this lane's landmark
-    const float ml = masked ? g.mlm[(long)b * NM + lq] : 1.f;
-    const bf16_t* klb = lm + (long)b * NM * LD + D + hd * ND;
-    const bf16_t* w2b = w2 + (long)bh * NM * ND;
-    bf16x8 klf[4], w2f[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-        klf[ks] = frag_g(klb + (long)lq * LD, 16 * ks, lane);
-        w2f[ks] = frag_g(w2b + (long)lq * ND, 16 * ks, lane);
-    }
-    const bf16_t* qb = qkv + (long)b * g.n_p * 3 * D + hd * ND;
-    const bf16_t* gb = dout + (long)b * g.n_p * D + hd * ND;
-    const bf16_t* ob = o1 + (long)b * g.n_p * D + hd * ND;
-    f32x16 adw[2] = {zero16(), zero16()}, adk[2] = {zero16(), zero16()};
-    constexpr int NCH = TR * 8 / NTW;       // 16-byte pieces of a [128 x 64] tile per thread: rows (tid >> 3) + 64 i, columns 8 (tid & 7) ..
-    const int pr = tid >> 3, pc = tid & 7;
-    u32x4 rq[NCH], rg[NCH], ro[NCH];
-    float rl = 0.f;
-    auto load_tiles = [&](int t) {
-#pragma unroll
-        for (int i = 0; i < NCH; i++) {
-            const long row = (long)t * TR + pr + 64 * i;
-            rq[i] = *reinterpret_cast<const u32x4*>(qb + row * 3 * D + pc * 8);
-            rg[i] = *reinterpret_cast<const u32x4*>(gb + row * D + pc * 8);
-            ro[i] = *reinterpret_cast<const u32x4*>(ob + row * D + pc * 8);
-        }
-        if (tid < TR) rl = lse1[(long)bh * g.n_p + (long)t * TR + tid];
-    };
-    load_tiles(t0);
-#pragma unroll 1
-    for (int t = t0; t < t1; t++) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < NCH; i++) {
-            const int r = pr + 64 * i;
-            *reinterpret_cast<u32x4*>(s_q + r * NP + pc * 8) = rq[i];
-            *reinterpret_cast<u32x4*>(s_g + r * NP + pc * 8) = rg[i];
-            // delta of row r: eight threads (pc = 0 .. 7) hold its 64 columns of both the dO and the O1 tile
-            float d = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-                d += __uint_as_float(rg[i][w] << 16) * __uint_as_float(ro[i][w] << 16);
-                d += __uint_as_float(rg[i][w] & 0xffff0000u) * __uint_as_float(ro[i][w] & 0xffff0000u);
-            }
-            d += __shfl_xor(d, 1, 64);
-            d += __shfl_xor(d, 2, 64);
-            d += __shfl_xor(d, 4, 64);
-            if (pc == 0) {
-                s_del[r] = -d * g.scale;            // staged negated and scaled: the tile arithmetic is two multiply-adds per element
-                delta1[(long)bh * g.n_p + (long)t * TR + r] = d;
-            }
-        }
-        if (tid < TR) {
-            s_lse[tid] = -rl * LOG2E;
-            s_mr[tid] = masked ? g.mrow[(long)b * g.n_p + (long)t * TR + tid] : 1.f;
-        }
-        __syncthreads();
-        if (t + 1 < t1) load_tiles(t + 1);
-#pragma unroll
-        for (int i = 0; i < 4; i++) {   // 32 q rows at a time
-            const f32x16 lv = rowvals16(s_lse + 32 * i, hl), dv = rowvals16(s_del + 32 * i, hl);      // -lse1 log2(e), -delta1 scale
-            f32x16 s = zero16(), dp = zero16();   // S[q row][landmark], dP[q row][landmark]
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) {
-                s = MFMA(frag_kc(s_q, 32 * i, 16 * ks, lane), klf[ks], s);
-                dp = MFMA(frag_kc(s_g, 32 * i, 16 * ks, lane), w2f[ks], dp);
-            }
-            if (masked) {
-                const f32x16 vr = rowvals16(s_mr + 32 * i, hl);
-                s = s * g.scale2;
-                mask_fill16(s, vr, ml);
-                s = s + lv;
-                exp2_16(s);
-                dp = s * (dp * g.scale + dv);
-                mask_zero16(dp, vr, ml);
-            } else {
-                s = s * g.scale2 + lv;
-                exp2_16(s);
-                dp = s * (dp * g.scale + dv);
-            }
-            const bf16x8 p0 = pack8<0>(s), p1 = pack8<1>(s), d0 = pack8<0>(dp), d1 = pack8<1>(dp);
-#pragma unroll
-            for (int nb = 0; nb < 2; nb++) {
-                adw[nb] = MFMA(p0, frag_tr(s_g, 32 * nb, 32 * i, lane), adw[nb]);
-                adw[nb] = MFMA(p1, frag_tr(s_g, 32 * nb, 32 * i + 16, lane), adw[nb]);
-                adk[nb] = MFMA(d0, frag_tr(s_q, 32 * nb, 32 * i, lane), adk[nb]);
-                adk[nb] = MFMA(d1, frag_tr(s_q, 32 * nb, 32 * i + 16, lane), adk[nb]);
-            }
-        }
-    }
-    float* dwb = dw2 + (long)bh * NM * ND;
-    float* dkb = dlm + (long)b * NM * 2 * D + D + hd * ND;
-#pragma unroll
-    for (int nb = 0; nb < 2; nb++) {
-        atomic_tile(dwb + (long)(32 * wave) * ND + 32 * nb, ND, adw[nb], hl, c);
-        atomic_tile(dkb + (long)(32 * wave) * 2 * D + 32 * nb, 2 * D, adk[nb], hl, c);
-    }
-}
-
 // ============================================================================ attn1 backward in ONE pass (L kernel + LDS hand-over)
-// The dw2 / dk_l kernel and the dq kernel above each compute every logit, every exponential and every dP (7 products per tile, q and dO
-// read twice).  Here the dw2 / dk_l walk (wave w owns landmarks [32 w, 32 w + 32), S and dS come out [query row][landmark] with the landmark
-// on the lane, 128 query rows per step) also leaves dS in an LDS image [landmark][query row] (the lane's own row, four consecutive rows per
-// 8-byte store, as nys_a3_bwd_one_kernel below does).  Behind a barrier the eight waves switch roles: wave w takes 32 of the 128 query rows
-// and 32 of the 64 channels and contracts over ALL 256 landmarks,  dq^T = k_l^T dS,  both operands read with the transposing fragments —
-// 5 products per tile, one exponential pass, q / dO / O1 read once.  128 rows per step and not attn3's 64: there is ONE per-step output
-// (dq) where attn3 has two (dk, dv), and 128 rows x 64 channels are the eight 32 x 32 tiles that give each of the eight waves a whole
+// grid (splits, B h).  P1 = exp(scale q k_l^T - lse1),  dw2 = P1^T dO,  dS1 = P1 o (dO w2^T - delta1) scale,  dk_l = dS1^T q  (both f32
+// atomics),  dq = dS1 k_l  (bf16, the q block of dqkv).  delta1[n] = sum_l P1 dP1 = sum_d dO[n, d] O1[n, d] (the flash-attention identity,
+// O1 = attn1's own output rows, saved by the forward) is formed HERE and written out: eight threads share a row of the dO / O1 tiles they
+// stage anyway, so no first pass over dP is needed and a tile is finished in one go.
+// Phase 1 is a landmark-owner walk: wave w owns landmarks [32 w, 32 w + 32), S and dS come out [query row][landmark] with the landmark on
+// the lane, 128 query rows per step, and dS is also left in an LDS image [landmark][query row] (the lane's own row, four consecutive rows
+// per 8-byte store, as nys_a3_bwd_one_kernel below does).  Behind a barrier the eight waves switch roles: wave w takes 32 of the 128 query
+// rows and 32 of the 64 channels and contracts over ALL 256 landmarks,  dq^T = k_l^T dS,  both operands read with the transposing
+// fragments — 5 products per tile, one exponential pass, q / dO / O1 read once (as two kernels, one per orientation, every logit,
+// exponential and dP was computed twice: 7 products, q and dO read twice).  128 rows per step and not attn3's 64: there is ONE per-step
+// output (dq) where attn3 has two (dk, dv), and 128 rows x 64 channels are the eight 32 x 32 tiles that give each of the eight waves a whole
 // contraction (at 64 rows four waves would idle in phase 2 or two would split the landmarks and need a third barrier to add the halves).
 // Both per-landmark accumulators (dw2, dk_l: 64 registers) stay in registers beside the fragments; 2 barriers per step; the next step's
 // q / dO / O1 pieces wait in registers during phase 1 and move into the images (with delta1) beside phase 2.  One workgroup per CU
-// (142 KB of LDS).  grid (splits, B h); dw2 / dk_l leave as f32 atomics exactly as from nys_a1_bwd_dw_kernel.
+// (142 KB of LDS).
+// 8 waves (two per SIMD, 32 landmarks each: round 5 — as 4 waves of 64 landmarks the landmark-owner walk ran at one wave per SIMD with
+// nothing to cover a wave's softmax arithmetic and LDS traffic).
+constexpr int NTW = 512;
 constexpr int DSP = TR + 8;      // pitch in bf16 of the dS image [landmark][128 query rows]: same bank walk as NP (4 dwords per row)
 template <bool MASKED>
 __global__ __launch_bounds__(NTW) void nys_a1_bwd_one_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ lm,
@@ -964,207 +742,16 @@ __global__ __launch_bounds__(256) void nys_delta3_kernel(const float* __restrict
     delta3[row] = d;
 }
 
-// ============================================================================ attn3 backward, dk + dv (N kernel)
-// grid (splits, B h), same walk as attn1.  P3 = exp(scale q_l k^T - lse3), dv = P3^T dav,
-// dS3 = P3 o (dav v^T - delta3) scale, dk = dS3^T q_l
-template <bool MASKED>
-__global__ __launch_bounds__(NT, 2) void nys_a3_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ lm,
-                                                            const float* __restrict__ delta3, const bf16_t* __restrict__ dav,
-                                                            const float* __restrict__ lse3, bf16_t* __restrict__ dqkv, Geo g) {
-    __shared__ __attribute__((aligned(16))) bf16_t s_ql_[NM * NP];
-    __shared__ __attribute__((aligned(16))) bf16_t s_g_[NM * NP];
-    __shared__ __attribute__((aligned(16))) float s_lse_[NM];
-    __shared__ __attribute__((aligned(16))) float s_del_[NM];
-    __shared__ __attribute__((aligned(16))) float s_mlm_[NM];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 31, hl = lane >> 5;
-    const int bh = blockIdx.y, b = bh / g.h, hd = bh % g.h, D = g.D;
-    const long LD = g.lm_ld;
-    stage_rows<NM>(s_ql_, lm + (long)b * NM * LD + hd * ND, LD, tid);
-    stage_rows<NM>(s_g_, dav + (long)bh * NM * ND, ND, tid);
-    s_del_[tid] = -delta3[(long)bh * NM + tid] * g.scale;      // thread = landmark; staged negated (a subtraction of per-element values
-    s_lse_[tid] = -lse3[(long)bh * NM + tid] * LOG2E;          // costs a sign flip per element on top of the multiply-add)
-    constexpr bool masked = MASKED;
-    s_mlm_[tid] = masked ? g.mlm[(long)b * NM + tid] : 1.f;
-    const int nblk = g.n_p / 32, stride = 4 * gridDim.x;
-    int rb = 4 * blockIdx.x + wave;
-    const bf16_t* kb = qkv + (long)b * g.n_p * 3 * D + D + hd * ND;
-    bf16x8 kn[4], vn[4];
-    if (rb < nblk) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) {
-            kn[ks] = frag_g(kb + (long)(32 * rb + c) * 3 * D, 16 * ks, lane);
-            vn[ks] = frag_g(kb + (long)(32 * rb + c) * 3 * D + D, 16 * ks, lane);
-        }
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (; rb < nblk; rb += stride) {
-        const long row = 32L * rb + c;
-        int opq = 0;                      // see nys_a1_fwd_kernel
-        asm volatile("" : "+v"(opq));
-        const bf16_t* s_ql = s_ql_ + opq;
-        const bf16_t* s_g = s_g_ + opq;
-        const float* s_lse = s_lse_ + opq;
-        const float* s_del = s_del_ + opq;
-        const float* s_mlm = s_mlm_ + opq;
-        const float mr = masked ? g.mrow[(long)b * g.n_p + row] : 1.f;
-        bf16x8 kf[4], vf[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) { kf[ks] = kn[ks]; vf[ks] = vn[ks]; }
-        if (rb + stride < nblk) {
-            const bf16_t* nr = kb + (32L * (rb + stride) + c) * 3 * D;
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) {
-                kn[ks] = frag_g(nr, 16 * ks, lane);
-                vn[ks] = frag_g(nr + D, 16 * ks, lane);
-            }
-        }
-        f32x16 adv[2] = {zero16(), zero16()}, adk[2] = {zero16(), zero16()};   // dv^T[d][key], dk^T[d][key]
-#pragma unroll
-        for (int blk = 0; blk < 8; blk++) {
-            f32x16 s = zero16(), dp = zero16();   // S3[landmark][key], dP3[landmark][key]
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) {
-                s = MFMA(frag_kc(s_ql, 32 * blk, 16 * ks, lane), kf[ks], s);
-                dp = MFMA(frag_kc(s_g, 32 * blk, 16 * ks, lane), vf[ks], dp);
-            }
-            if (masked) {
-                const f32x16 vr = rowvals16(s_mlm + 32 * blk, hl);
-                s = s * g.scale2;
-                mask_fill16(s, vr, mr);
-                s = s + rowvals16(s_lse + 32 * blk, hl);
-                exp2_16(s);
-                dp = s * (dp * g.scale + rowvals16(s_del + 32 * blk, hl));
-                mask_zero16(dp, vr, mr);
-            } else {
-                s = s * g.scale2 + rowvals16(s_lse + 32 * blk, hl);      // staged as -lse3 * log2(e)
-                exp2_16(s);
-                dp = s * (dp * g.scale + rowvals16(s_del + 32 * blk, hl));   // staged as -delta3 * scale
-            }
-            const bf16x8 p0 = pack8<0>(s), p1 = pack8<1>(s), d0 = pack8<0>(dp), d1 = pack8<1>(dp);
-#pragma unroll
-            for (int nb = 0; nb < 2; nb++) {
-                adv[nb] = MFMA(frag_tr(s_g, 32 * nb, 32 * blk, lane), p0, adv[nb]);
-                adv[nb] = MFMA(frag_tr(s_g, 32 * nb, 32 * blk + 16, lane), p1, adv[nb]);
-                adk[nb] = MFMA(frag_tr(s_ql, 32 * nb, 32 * blk, lane), d0, adk[nb]);
-                adk[nb] = MFMA(frag_tr(s_ql, 32 * nb, 32 * blk + 16, lane), d1, adk[nb]);
-            }
-        }
-        bf16_t* dkrow = dqkv + ((long)b * g.n_p + row) * 3 * D + D + hd * ND;
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++) {
-            store_row8(dkrow + 32 * nb, adk[nb], hl);
-            store_row8(dkrow + D + 32 * nb, adv[nb], hl);
-        }
-    }
-}
-
-// ============================================================================ attn3 backward, dq_l (L kernel)
-// grid (splits, B h).  dq_l[l, d] += sum_n dS3[l, n] k[n, d]   (f32 atomics into the q_l half of dlm)
-template <bool MASKED>
-__global__ __launch_bounds__(NT) void nys_a3_bwd_dql_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ lm,
-                                                            const float* __restrict__ delta3, const bf16_t* __restrict__ dav,
-                                                            const float* __restrict__ lse3, float* __restrict__ dlm, Geo g,
-                                                            int tiles_per_wg) {
-    __shared__ __attribute__((aligned(16))) bf16_t s_k[TR * NP];
-    __shared__ __attribute__((aligned(16))) bf16_t s_v[TR * NP];
-    __shared__ __attribute__((aligned(16))) float s_mr[TR];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 31, hl = lane >> 5;
-    const int bh = blockIdx.y, b = bh / g.h, hd = bh % g.h, D = g.D;
-    const long LD = g.lm_ld;
-    const int ntiles = g.n_p / TR;
-    const int t0 = blockIdx.x * tiles_per_wg, t1 = min(t0 + tiles_per_wg, ntiles);
-    if (t0 >= t1) return;
-    constexpr bool masked = MASKED;
-    float ml[2] = {1.f, 1.f};
-    if (masked) { ml[0] = g.mlm[(long)b * NM + 64 * wave + c]; ml[1] = g.mlm[(long)b * NM + 64 * wave + 32 + c]; }
-    const bf16_t* qlb = lm + (long)b * NM * LD + hd * ND;
-    bf16x8 qlf[2][4], gf[2][4];
-    float lsev[2], delv[2];
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        const int lq = 64 * wave + 32 * j + c;
-        const bf16_t* gr = dav + ((long)bh * NM + lq) * ND;
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) {
-            qlf[j][ks] = frag_g(qlb + (long)lq * LD, 16 * ks, lane);
-            gf[j][ks] = frag_g(gr, 16 * ks, lane);
-        }
-        delv[j] = delta3[(long)bh * NM + lq] * g.scale;
-        lsev[j] = lse3[(long)bh * NM + lq] * LOG2E;
-    }
-    const bf16_t* kb = qkv + (long)b * g.n_p * 3 * D + D + hd * ND;
-    const bf16_t* vb = kb + D;
-    f32x16 acc[2][2];   // dq_l[landmark (j block, registers)][d (nb block, lanes)]
-#pragma unroll
-    for (int nb = 0; nb < 2; nb++)
-#pragma unroll
-        for (int j = 0; j < 2; j++) acc[nb][j] = zero16();
-    u32x4 rk[TR * 8 / NT], rv[TR * 8 / NT];
-    tile_load<TR>(rk, kb + (long)t0 * TR * 3 * D, 3 * D, tid);
-    tile_load<TR>(rv, vb + (long)t0 * TR * 3 * D, 3 * D, tid);
-#pragma unroll 1
-    for (int t = t0; t < t1; t++) {
-        __syncthreads();
-        tile_store<TR>(rk, s_k, tid);
-        tile_store<TR>(rv, s_v, tid);
-        if (tid < TR) s_mr[tid] = masked ? g.mrow[(long)b * g.n_p + (long)t * TR + tid] : 1.f;
-        __syncthreads();
-        if (t + 1 < t1) {
-            tile_load<TR>(rk, kb + (long)(t + 1) * TR * 3 * D, 3 * D, tid);
-            tile_load<TR>(rv, vb + (long)(t + 1) * TR * 3 * D, 3 * D, tid);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                f32x16 s = zero16(), dp = zero16();   // S3^T[key][landmark], dP3^T[key][landmark]
-#pragma unroll
-                for (int ks = 0; ks < 4; ks++) {
-                    s = MFMA(frag_kc(s_k, 32 * i, 16 * ks, lane), qlf[j][ks], s);
-                    dp = MFMA(frag_kc(s_v, 32 * i, 16 * ks, lane), gf[j][ks], dp);
-                }
-                if (masked) {
-                    const f32x16 vr = rowvals16(s_mr + 32 * i, hl);
-                    s = s * g.scale2;
-                    mask_fill16(s, vr, ml[j]);
-                    s = fma_splat(s, 1.f, -lsev[j]);
-                    exp2_16(s);
-                    dp = s * fma_splat(dp, g.scale, -delv[j]);
-                    mask_zero16(dp, vr, ml[j]);
-                } else {
-                    s = fma_splat(s, g.scale2, -lsev[j]);
-                    exp2_16(s);
-                    dp = s * fma_splat(dp, g.scale, -delv[j]);
-                }
-                // dS3^T in the accumulator layout IS dS3 as an A operand (row = landmark = lane, k = keys): the product
-                // comes out as dq_l[landmark (registers)][d (lanes)], so the final atomics are 128-byte coalesced
-                const bf16x8 d0 = pack8<0>(dp), d1 = pack8<1>(dp);
-#pragma unroll
-                for (int nb = 0; nb < 2; nb++) {
-                    acc[nb][j] = MFMA(d0, frag_tr(s_k, 32 * nb, 32 * i, lane), acc[nb][j]);
-                    acc[nb][j] = MFMA(d1, frag_tr(s_k, 32 * nb, 32 * i + 16, lane), acc[nb][j]);
-                }
-            }
-    }
-    float* dqb = dlm + (long)b * NM * 2 * D + hd * ND;
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-        for (int nb = 0; nb < 2; nb++)
-            atomic_tile(dqb + (long)(64 * wave + 32 * j) * 2 * D + 32 * nb, 2 * D, acc[nb][j], hl, c);
-}
-
 // ============================================================================ attn3 backward in ONE pass (L kernel + LDS hand-over)
 // dk, dv (contraction over the landmarks) and dq_l (contraction over the keys) need the probabilities in two orientations; as two
 // kernels every logit, every dP and every exponential was computed twice (28 MFMAs per 32 x 32 tile instead of 20) and k / v were read
-// twice.  Here wave w owns landmarks [64 w, 64 w + 64) as in the dq_l kernel: S^T and dP^T [key][landmark] come out with the landmark
+// twice.  Here wave w owns landmarks [32 w, 32 w + 32): S^T and dP^T [key][landmark] come out with the landmark
 // on the lane, dS^T is at once the A operand of dq_l += dS k (registers), and P / dS ALSO go to two LDS images [landmark][key] (the
-// lane's own row, four consecutive keys per 8-byte store).  Behind a barrier the same four waves switch roles: wave w takes 32 of the
-// 64 keys and 32 of the 64 channels and contracts over ALL 256 landmarks,  dv^T = dav^T P,  dk^T = q_l^T dS,  both operands read with
+// lane's own row, four consecutive keys per 8-byte store).  Behind a barrier the eight waves switch roles: wave w takes 32 of the
+// 64 keys, 32 of the 64 channels and one of  dv^T = dav^T P,  dk^T = q_l^T dS  and contracts over ALL 256 landmarks,  both operands read with
 // the transposing fragments (contraction index = image row).  One workgroup per CU (157 KB of LDS), 64 keys per step, 2 barriers per step;
 // the v rows are A fragments straight from HBM / L2 (the image budget has no room for a v tile).
-// grid (splits, B h): range of 64-key steps per workgroup; dq_l leaves as f32 atomics into the q_l half of dlm (as nys_a3_bwd_dql_kernel).
+// grid (splits, B h): range of 64-key steps per workgroup; dq_l leaves as f32 atomics into the q_l half of dlm.
 constexpr int HT = 64;   // keys per step
 constexpr int NT8 = 512;  // 8 waves: two per SIMD, so one wave's softmax arithmetic / LDS traffic runs under the other's MFMAs
 // (first version: 4 waves of 64 landmarks, one per SIMD — 183 us alone against 192 for the two kernels, and 0.75 % SLOWER in the step)
@@ -1349,11 +936,11 @@ extern "C" int mh_nys_attn1_fwd_q8(const void* qkv, const void* lm, const void* 
     return MH_OK;
 }
 
-int pick_splits(int BH, int ntiles, int which);
+int pick_splits(int BH, int ntiles);
 
 extern "C" int64_t mh_nys_attn3_ws_floats(int B, int h, int n_p) {
     if (B <= 0 || h <= 0 || n_p < TR) return 0;
-    const int splits = pick_splits(B * h, n_p / TR, 0);
+    const int splits = pick_splits(B * h, n_p / TR);
     return splits > 1 ? (int64_t)B * h * splits * A3_PART : 0;
 }
 
@@ -1368,7 +955,7 @@ extern "C" int mh_nys_attn3_fwd(const void* qkv, const void* lm, float* av, floa
     if (B == 0) return MH_OK;
     const Geo g{h, n_p, h * ND, scale, scale * LOG2E, mrow, mlm, 0, lm_ld > 0 ? lm_ld : 2L * h * ND, rc_w, (bf16_t*)rc_out};
     const int ntiles = n_p / TR;
-    int splits = pick_splits(B * h, ntiles, 0);
+    int splits = pick_splits(B * h, ntiles);
     if (!workspace || ws_floats < (int64_t)B * h * splits * A3_PART) splits = 1;      // no room for partials: one workgroup per (b, h)
     const int tpw = (ntiles + splits - 1) / splits;
     splits = (ntiles + tpw - 1) / tpw;                                                 // no empty ranges
@@ -1390,11 +977,11 @@ extern "C" int mh_nys_attn3_fwd(const void* qkv, const void* lm, float* av, floa
     return MH_OK;
 }
 
-// splits: workgroups per (b, h) for the landmark-owner kernels (partials in a workspace, or f32 atomics)
-// which: 0 = attn3 forward (+ combine pass), 1 = attn1 backward dw2 / dk_l, 2 = attn3 backward dq_l (f32 atomics).
+// splits: workgroups per (b, h) for the landmark-owner kernels: attn3 forward (partials in a workspace + combine pass) and attn1
+// backward (dw2 / dk_l as f32 atomics).
 // One workgroup per CU in all (B h x splits ~ 256): measured in the step at B h = 128, 2 ranges per (b, h) beat 4 by 1.7 %
 // (half the partial tiles / atomics, and these launches run beside the half-chip chain) and 1 by 1.2 %.
-int pick_splits(int BH, int ntiles, int which) {
+int pick_splits(int BH, int ntiles) {
     int splits = 1;
     while (BH * splits < 256 && splits * 2 <= ntiles) splits *= 2;
     return splits;
@@ -1402,59 +989,34 @@ int pick_splits(int BH, int ntiles, int which) {
 
 extern "C" int mh_nys_attn1_bwd(const void* qkv, const void* lm, const void* w2, const void* dout, const float* lse1, const void* o1,
                                 float* delta1, void* dqkv, float* dw2, float* dlm, const float* mrow, const float* mlm, int B, int h,
-                                int n_p, int m, int dh, float scale, int64_t lm_ld, int which, mh_stream s) {
+                                int n_p, int m, int dh, float scale, int64_t lm_ld, mh_stream s) {
     if (int e = check_geo("mh_nys_attn1_bwd", B, h, n_p, m, dh)) return e;
     MH_REQUIRE(lm_ld == 0 || (lm_ld >= 2L * h * ND && lm_ld % 8 == 0), "mh_nys_attn1_bwd: lm_ld must be 0 or a multiple of 8 >= 2 D");
-    MH_REQUIRE(which >= 1 && which <= 3, "mh_nys_attn1_bwd: which = 1 (dw2, dk_l, delta1), 2 (dq from delta1) or 3 (all of them from the one-pass kernel)");
-    MH_REQUIRE(delta1 && (!(which & 1) || (o1 && dw2 && dlm && (((uintptr_t)o1) & 15) == 0)) && (!(which & 2) || dqkv),
-               "mh_nys_attn1_bwd: missing buffer for the requested part");
+    MH_REQUIRE(o1 && delta1 && dqkv && dw2 && dlm && (((uintptr_t)o1) & 15) == 0,
+               "mh_nys_attn1_bwd: o1 (16-byte aligned), delta1, dqkv, dw2 and dlm are all needed");
     if (B == 0) return MH_OK;
     const Geo g{h, n_p, h * ND, scale, scale * LOG2E, mrow, mlm, 0, lm_ld > 0 ? lm_ld : 2L * h * ND, nullptr, nullptr};
-    if (which == 3) {      // both parts: one pass over the rows
-        const int ntiles = n_p / TR, splits = pick_splits(B * h, ntiles, 1), tpw = (ntiles + splits - 1) / splits;
-        NYS_LAUNCH(nys_a1_bwd_one_kernel, dim3(splits, B * h), dim3(NTW), 0, (hipStream_t)s, (const bf16_t*)qkv, (const bf16_t*)lm,
-                           (const bf16_t*)w2, (const bf16_t*)dout, lse1, (const bf16_t*)o1, delta1, (bf16_t*)dqkv, dw2, dlm, g, tpw);
-        MH_LAUNCH_CHECK("mh_nys_attn1_bwd(one pass)");
-        return MH_OK;
-    }
-    if (which & 1) {
-        const int ntiles = n_p / TR, splits = pick_splits(B * h, ntiles, 1), tpw = (ntiles + splits - 1) / splits;
-        NYS_LAUNCH(nys_a1_bwd_dw_kernel, dim3(splits, B * h), dim3(NTW), 0, (hipStream_t)s, (const bf16_t*)qkv,
-                           (const bf16_t*)lm, (const bf16_t*)w2, (const bf16_t*)dout, lse1, (const bf16_t*)o1, delta1, dw2, dlm, g, tpw);
-        MH_LAUNCH_CHECK("mh_nys_attn1_bwd(dw)");
-    }
-    if (which & 2) {
-        NYS_LAUNCH(nys_a1_bwd_dq_kernel, dim3(pick_walkers(B * h, n_p), B * h), dim3(NT), 0, (hipStream_t)s, (const bf16_t*)qkv,
-                           (const bf16_t*)lm, (const bf16_t*)w2, (const bf16_t*)dout, lse1, (const float*)delta1, (bf16_t*)dqkv, g);
-        MH_LAUNCH_CHECK("mh_nys_attn1_bwd(dq)");
-    }
+    const int ntiles = n_p / TR, splits = pick_splits(B * h, ntiles), tpw = (ntiles + splits - 1) / splits;
+    NYS_LAUNCH(nys_a1_bwd_one_kernel, dim3(splits, B * h), dim3(NTW), 0, (hipStream_t)s, (const bf16_t*)qkv, (const bf16_t*)lm,
+                       (const bf16_t*)w2, (const bf16_t*)dout, lse1, (const bf16_t*)o1, delta1, (bf16_t*)dqkv, dw2, dlm, g, tpw);
+    MH_LAUNCH_CHECK("mh_nys_attn1_bwd");
     return MH_OK;
 }
 
 extern "C" int mh_nys_attn3_bwd(const void* qkv, const void* lm, const float* av, const void* dav, const float* lse3, float* delta3,
                                 void* dqkv, float* dlm, const float* mrow, const float* mlm, int B, int h, int n_p, int m, int dh,
-                                float scale, int64_t lm_ld, int one_pass, mh_stream s) {
+                                float scale, int64_t lm_ld, mh_stream s) {
     if (int e = check_geo("mh_nys_attn3_bwd", B, h, n_p, m, dh)) return e;
     MH_REQUIRE(lm_ld == 0 || (lm_ld >= 2L * h * ND && lm_ld % 8 == 0), "mh_nys_attn3_bwd: lm_ld must be 0 or a multiple of 8 >= 2 D");
     if (B == 0) return MH_OK;
     const Geo g{h, n_p, h * ND, scale, scale * LOG2E, mrow, mlm, 0, lm_ld > 0 ? lm_ld : 2L * h * ND, nullptr, nullptr};
     if (av) hipLaunchKernelGGL(nys_delta3_kernel, dim3(B * h), dim3(NM), 0, (hipStream_t)s, av, (const bf16_t*)dav, delta3);
-    if (one_pass) {
-        const int nsteps = n_p / HT;
-        int splits = 1;
-        while (B * h * splits < 256 && splits * 2 <= nsteps) splits *= 2;
-        const int spw = (nsteps + splits - 1) / splits;
-        NYS_LAUNCH(nys_a3_bwd_one_kernel, dim3((nsteps + spw - 1) / spw, B * h), dim3(NT8), 0, (hipStream_t)s, (const bf16_t*)qkv,
-                           (const bf16_t*)lm, (const float*)delta3, (const bf16_t*)dav, lse3, (bf16_t*)dqkv, dlm, g, spw);
-        MH_LAUNCH_CHECK("mh_nys_attn3_bwd(one pass)");
-        return MH_OK;
-    }
-    NYS_LAUNCH(nys_a3_bwd_dkv_kernel, dim3(pick_walkers(B * h, n_p), B * h), dim3(NT), 0, (hipStream_t)s, (const bf16_t*)qkv,
-                       (const bf16_t*)lm, (const float*)delta3, (const bf16_t*)dav, lse3, (bf16_t*)dqkv, g);
-    MH_LAUNCH_CHECK("mh_nys_attn3_bwd(dkv)");
-    const int ntiles = n_p / TR, splits = pick_splits(B * h, ntiles, 2), tpw = (ntiles + splits - 1) / splits;
-    NYS_LAUNCH(nys_a3_bwd_dql_kernel, dim3(splits, B * h), dim3(NT), 0, (hipStream_t)s, (const bf16_t*)qkv,
-                       (const bf16_t*)lm, (const float*)delta3, (const bf16_t*)dav, lse3, dlm, g, tpw);
-    MH_LAUNCH_CHECK("mh_nys_attn3_bwd(dql)");
+    const int nsteps = n_p / HT;
+    int splits = 1;
+    while (B * h * splits < 256 && splits * 2 <= nsteps) splits *= 2;
+    const int spw = (nsteps + splits - 1) / splits;
+    NYS_LAUNCH(nys_a3_bwd_one_kernel, dim3((nsteps + spw - 1) / spw, B * h), dim3(NT8), 0, (hipStream_t)s, (const bf16_t*)qkv,
+                       (const bf16_t*)lm, (const float*)delta3, (const bf16_t*)dav, lse3, (bf16_t*)dqkv, dlm, g, spw);
+    MH_LAUNCH_CHECK("mh_nys_attn3_bwd");
     return MH_OK;
 }

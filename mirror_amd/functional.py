@@ -1896,12 +1896,10 @@ def _pair(first: torch.Tensor, second: torch.Tensor) -> torch.Tensor:
 
 _SIM2_MASKED = True      # (test hook, round 5) the one-launch sim2 + softmax + maxima + panels also under a key-padding mask (config 4)
 _RC_FUSED = True      # (test hook) res_conv inside attn3's forward launch, its two gradients as one pass over dout (round 5)
-_A1_DQ_IN_WINDOW = False     # (test hook, round 5) attn1's dq kernel beside the pinv chain's backward: -0.35 % +- 0.02 when it was built, but
-                             # +0.80 % +- 0.20 (8 ABBA rounds) on the round's final tree — the one-pass attn3 backward and the other kernels that joined the
-                             # window since made its main side the longer one; dq stands in front of the fork again (profiles/r05_p_*)
 # (measured and deleted in round 4, see DESIGN.md section 6 round 3: nys_dz_dav on the chain's branch +0.32 %, attn3's delta out of
 #  nys_dz_dav +0.32 %, the chain branch joined in front of the landmark projection's backward +0.02 %, res_conv's weight gradient on
-#  the chain's stream +0.26 % or in front of the fork: neutral)
+#  the chain's stream +0.26 % or in front of the fork: neutral; measured in round 5 and deleted with the two-kernel attn1 backward:
+#  attn1's dq kernel beside the chain's backward -0.35 % +- 0.02 when built, +0.80 % +- 0.20 on round 5's final tree, profiles/r05_p_*)
 
 
 class NystromCoreFn(Function):
@@ -2111,9 +2109,8 @@ class NystromCoreFn(Function):
             dlm = zeros((Bn, m, 2 * D), qkv.device)
             delta1 = torch.empty_like(lse1)
             # dW2 and dk_l (+ delta1 from the saved rows of attn1) are all the chain's backward waits for; dq comes out of the same pass
-            # over the rows (round 6: one kernel in front of the fork).  Only the hook that moves dq beside the chain takes the parts apart
-            K.nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dW2, dlm, h, scale, kmask,
-                            which=1 if (chain and _A1_DQ_IN_WINDOW) else 3)
+            # over the rows (round 6: one kernel in front of the fork)
+            K.nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dW2, dlm, h, scale, kmask)
         else:
             dW2 = K.gemm(tr(a1), dO, mma=mma, out_dtype=f32)                             # [B,h,m,dh]
             dlm = torch.empty((Bn, m, 2 * D), device=qkv.device, dtype=f32)
@@ -2165,8 +2162,6 @@ class NystromCoreFn(Function):
                 sm_bwd(a2, dS2, mlm if kmask else None, mlm if kmask else None)
         if ctx.link is not None:
             ctx.link.run("wgrad")      # to_out's weight gradient (ToOutDropAddFn left it to us): beside the chain when there is one
-        if fused and chain and _A1_DQ_IN_WINDOW:
-            K.nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dW2, dlm, h, scale, kmask, which=2)     # dq: beside the chain
         rc_bwd_one = fused and _RC_FUSED and A == bf16      # both res_conv gradients in ONE pass over dout, behind attn3's backward
         if not rc_bwd_one:
             K.resconv_wgrad(qkv[..., 2 * D:], dout, dres, h)

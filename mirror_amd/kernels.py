@@ -1167,32 +1167,21 @@ def nys_attn3_fwd(qkv, lm, heads: int, scale: float, kmask=None, rc=None):
     return av, lse3
 
 
-def nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dw2, dlm, heads: int, scale: float, kmask=None, which: int = 3) -> None:
-    """attn1's backward (mh_nys_attn1_bwd): which = 1 — ADDS into dw2 and into the k_l half of dlm (both f32, zeroed by the
-    caller) and WRITES delta1 [B, h, n_p] from the forward's saved rows o1; which = 2 — writes the q block of dqkv from delta1;
-    which = 3 (default) — all of it from ONE kernel that walks the rows once (5 products per tile instead of 4 + 3)."""
+def nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dw2, dlm, heads: int, scale: float, kmask=None) -> None:
+    """attn1's backward (mh_nys_attn1_bwd), ONE kernel that walks the rows once (5 products per tile): ADDS into dw2 and into the k_l half
+    of dlm (both f32, zeroed by the caller), WRITES delta1 [B, h, n_p] from the forward's saved rows o1 and the q block of dqkv."""
     _chk(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dw2, dlm)
     B, n_p, _ = qkv.shape
-    ts = dict(qkv=qkv, lm=lm, w2=w2, dout=dout, lse1=lse1, delta1=delta1)
-    if which & 1:
-        ts.update(o1=o1, dw2=dw2, dlm=dlm)
-    if which & 2:
-        ts.update(dqkv=dqkv)
-    _nys_check("nys_attn1_bwd", B, heads, n_p, **ts)
-    prods = 5 if which == 3 else (4 if which & 1 else 0) + (3 if which & 2 else 0)
-    _nys_launch("nys_a1_bwd_kernels", prods * 2.0 * n_p * NYS_FUSED_M * NYS_FUSED_DH * B * heads,
+    _nys_check("nys_attn1_bwd", B, heads, n_p, qkv=qkv, lm=lm, w2=w2, dout=dout, lse1=lse1, delta1=delta1, o1=o1, dw2=dw2, dlm=dlm, dqkv=dqkv)
+    _nys_launch("nys_a1_bwd_kernels", 5 * 2.0 * n_p * NYS_FUSED_M * NYS_FUSED_DH * B * heads,
                 lambda: _lib.call("mh_nys_attn1_bwd", _p(qkv), _p(lm), _p(w2), _p(dout), _p(lse1), _p(o1), _p(delta1), _p(dqkv),
                                   _p(dw2), _p(dlm), *_nys_masks(kmask, B, n_p), B, heads, n_p, NYS_FUSED_M, NYS_FUSED_DH, scale,
-                                  _lm_ld(lm), int(which), stream=_stream()))
+                                  _lm_ld(lm), stream=_stream()))
 
 
-NYS_A3_BWD_ONE_PASS = True      # (test hook, round 5) attn3's backward as one kernel (-1.21 % +- 0.17 step time against the dk / dv + dq_l pair)
-
-
-def nys_attn3_bwd(qkv, lm, av, dav, lse3, dqkv, dlm, heads: int, scale: float, kmask=None, delta3=None, one_pass=None) -> None:
-    """Writes the k and v blocks of dqkv; ADDS into the q_l half of dlm.  delta3: sum_d dav av from nys_dz_dav (skips a launch).
-    one_pass: dk, dv, dq_l from one kernel (default) or the dk / dv kernel + the dq_l kernel."""
-    one_pass = NYS_A3_BWD_ONE_PASS if one_pass is None else bool(one_pass)
+def nys_attn3_bwd(qkv, lm, av, dav, lse3, dqkv, dlm, heads: int, scale: float, kmask=None, delta3=None) -> None:
+    """Writes the k and v blocks of dqkv; ADDS into the q_l half of dlm (all from one kernel).  delta3: sum_d dav av from nys_dz_dav
+    (skips a launch)."""
     _chk(qkv, lm, av, dav, lse3, dqkv, dlm, delta3)
     B, n_p, _ = qkv.shape
     _nys_check("nys_attn3_bwd", B, heads, n_p, qkv=qkv, lm=lm, av=av, dav=dav, lse3=lse3, dqkv=dqkv, dlm=dlm)
@@ -1203,7 +1192,7 @@ def nys_attn3_bwd(qkv, lm, av, dav, lse3, dqkv, dlm, heads: int, scale: float, k
         delta3 = torch.empty_like(lse3)
     _nys_launch("nys_a3_bwd_kernels", 7 * 2.0 * n_p * NYS_FUSED_M * NYS_FUSED_DH * B * heads,
                 lambda: _lib.call("mh_nys_attn3_bwd", _p(qkv), _p(lm), None if given else _p(av), _p(dav), _p(lse3), _p(delta3), _p(dqkv), _p(dlm),
-                                  *_nys_masks(kmask, B, n_p), B, heads, n_p, NYS_FUSED_M, NYS_FUSED_DH, scale, _lm_ld(lm), int(one_pass),
+                                  *_nys_masks(kmask, B, n_p), B, heads, n_p, NYS_FUSED_M, NYS_FUSED_DH, scale, _lm_ld(lm),
                                   stream=_stream()))
 
 

@@ -1527,29 +1527,27 @@ def test_nys_fused_attention_sides(B, h, l):
     dqkv = torch.full_like(qkv_d, float("nan"))
     dw2 = torch.zeros((B, h, m, dh), device=DEV)
     dlm = torch.zeros((B, m, 2 * D), device=DEV)
-    # round 5: part 1 (dw2, dk_l, delta1 = sum_d dO o1) first, then part 2 (dq from delta1) — as NystromCoreFn.backward issues them
+    # one kernel: dw2, dk_l, delta1 = sum_d dO o1 and dq — as NystromCoreFn.backward issues it
     delta1 = torch.full((B, h, n_p), float("nan"), device=DEV)
-    K.nys_attn1_bwd(qkv_d, lm_d, w2_d, dout_d, lse1, o1, delta1, dqkv, dw2, dlm, h, scale, which=1)
+    K.nys_attn1_bwd(qkv_d, lm_d, w2_d, dout_d, lse1, o1, delta1, dqkv, dw2, dlm, h, scale)
     p1 = torch.softmax(s1, -1)
     dp1 = heads(dout, 0, 1) @ w2.double().transpose(-1, -2)
     dref = (p1 * dp1).sum(-1)
     close(delta1, dref, 0.0, 2e-2 * float(dref.abs().max()), "delta1 = sum_l P dP from the saved rows")
-    K.nys_attn1_bwd(qkv_d, lm_d, w2_d, dout_d, lse1, o1, delta1, dqkv, dw2, dlm, h, scale, which=2)
     K.nys_attn3_bwd(qkv_d, lm_d, av, dav_d, lse3, dqkv, dlm, h, scale)
     for name, got, ref in (("dqkv", dqkv, qkv_r.grad), ("dw2", dw2, w2_r.grad), ("dlm", dlm, lm_r.grad)):
         close(got, ref, 0.0, 2e-2 * float(ref.abs().max()), name)
         rel = float((got.float().cpu().double() - ref).norm() / ref.norm())
         assert rel < 1e-2, (name, rel)
-    # both forms of attn3's backward (round 5: one pass by default; the dk / dv + dq_l pair stays behind the switch)
-    for one in (True, False):
-        dq3 = torch.full_like(qkv_d, float("nan"))
-        dl3 = torch.zeros_like(dlm)
-        K.nys_attn3_bwd(qkv_d, lm_d, av, dav_d, lse3, dq3, dl3, h, scale, one_pass=one)
-        ref_kv = qkv_r.grad[..., D:]
-        close(dq3[..., D:], ref_kv, 0.0, 2e-2 * float(ref_kv.abs().max()), f"dk | dv (one_pass={one})")
-        ref_ql = lm_r.grad[..., :D] - 0.0      # attn3's share of d q_l: attn1 adds nothing to the q_l half
-        close(dl3[..., :D], ref_ql, 0.0, 2e-2 * float(ref_ql.abs().max()), f"dq_l (one_pass={one})")
-        assert float(dl3[..., D:].abs().max()) == 0.0
+    # attn3's backward on buffers of its own: its share of the gradients alone
+    dq3 = torch.full_like(qkv_d, float("nan"))
+    dl3 = torch.zeros_like(dlm)
+    K.nys_attn3_bwd(qkv_d, lm_d, av, dav_d, lse3, dq3, dl3, h, scale)
+    ref_kv = qkv_r.grad[..., D:]
+    close(dq3[..., D:], ref_kv, 0.0, 2e-2 * float(ref_kv.abs().max()), "dk | dv")
+    ref_ql = lm_r.grad[..., :D] - 0.0      # attn3's share of d q_l: attn1 adds nothing to the q_l half
+    close(dl3[..., :D], ref_ql, 0.0, 2e-2 * float(ref_ql.abs().max()), "dq_l")
+    assert float(dl3[..., D:].abs().max()) == 0.0
     # delta3 handed in (what mh_nys_dz_dav leaves): the call skips its first launch and writes the same dk / dv
     dqkv2 = torch.full_like(qkv_d, float("nan"))
     K.nys_attn3_bwd(qkv_d, lm_d, av, dav_d, lse3, dqkv2, torch.zeros_like(dlm), h, scale, delta3=(dav_d.float().view(B, h, m, dh) * av).sum(-1))

@@ -57,7 +57,8 @@ fl = 2.0 * n_p * m * 64 * B * h
 timeit("nys_attn1_fwd", lambda: K.nys_attn1_fwd(qkv, lm, w2, out, h, 0.125), 2 * fl)
 timeit("nys_attn3_fwd", lambda: K.nys_attn3_fwd(qkv, lm, h, 0.125), 2 * fl)
 timeit("nys_attn1_bwd (one pass)", lambda: K.nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dw2, dlm, h, 0.125), 5 * fl)
-timeit("nys_attn3_bwd (2 kernels)", lambda: K.nys_attn3_bwd(qkv, lm, av, dav, lse3, dqkv, dlm, h, 0.125), 7 * fl)
+# 7: the count kernels.py books under "nys_a3_bwd_kernels" (the profiles key on it); the kernel itself issues 5 products per tile
+timeit("nys_attn3_bwd (one pass)", lambda: K.nys_attn3_bwd(qkv, lm, av, dav, lse3, dqkv, dlm, h, 0.125), 7 * fl)
 
 # ---- does the chain really overlap with the attn3 side?  (side stream vs same stream)
 side = torch.cuda.Stream()

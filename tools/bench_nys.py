@@ -43,10 +43,8 @@ t("attn1 fwd", lambda: K.nys_attn1_fwd(qkv, lm, w2, out, h, scale), 2)
 t("attn1 fwd (accumulate)", lambda: K.nys_attn1_fwd(qkv, lm, w2, out, h, scale, accumulate=True), 2)
 t("attn3 fwd", lambda: K.nys_attn3_fwd(qkv, lm, h, scale), 2)
 t("attn1 fwd (accumulate, + o1)", lambda: K.nys_attn1_fwd(qkv, lm, w2, out, h, scale, accumulate=True, o1=o1), 2)
-t("attn1 bwd part 1 (dw2, dk_l, delta)", lambda: K.nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dw2, dlm, h, scale, which=1), 4)
-t("attn1 bwd part 2 (dq)", lambda: K.nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dw2, dlm, h, scale, which=2), 3)
-t("attn3 bwd (delta+dkv+dql)", lambda: K.nys_attn3_bwd(qkv, lm, av, dav, lse3, dqkv, dlm, h, scale, one_pass=False), 7)
-t("attn3 bwd (delta + ONE pass)", lambda: K.nys_attn3_bwd(qkv, lm, av, dav, lse3, dqkv, dlm, h, scale, one_pass=True), 5)
+t("attn1 bwd (one pass: dw2, dk_l, delta, dq)", lambda: K.nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dw2, dlm, h, scale), 5)
+t("attn3 bwd (delta + one pass)", lambda: K.nys_attn3_bwd(qkv, lm, av, dav, lse3, dqkv, dlm, h, scale), 5)
 
 # res_conv: alone, inside attn3's forward, and its two gradients as one pass (round 5)
 w = (torch.randn(h, 1, 33, 1, device=dev, generator=g) * 0.2)
