@@ -781,6 +781,36 @@ int mh_cls_confusion(const void* input, int64_t ld, int dt_in, const void* label
  * (their pairs add nothing).  labels int64 [N].  O(N^2 C) pairs through LDS; 1 <= N <= 2^20, 2 <= C <= 1024. */
 int mh_auroc_counts(const float* scores, int64_t ld, const int64_t* labels, int N, int C, int64_t* counts, mh_stream s);
 
+/* ---------------------------------------------------------------- InfoNCE with explicit negative keys (losses/info_nce.py:126-143;
+ * the reference builds these logits and labels and forgets `F.cross_entropy(logits / temperature, labels)`).
+ * logits[i] = [q^[i].k^[i] | neg[i, :]] / t with label 0; q^, k^ [N x D] f32 are the normalised query / positive key (mh_l2norm_fwd).
+ * Every entry point is deterministic (fixed summation order, no atomics), allocates nothing and never waits on the host.
+ *
+ * Paired negatives n [N x M x D] (f32 / bf16 by dt_neg, contiguous, read in place: no normalised copy exists).
+ *   fwd: ONE read of n:  inv[i, j] = 1 / max(|n[i, j]|, eps),  cosv[i, j] = q^[i].n[i, j] * inv[i, j]   (both f32 [N x M]).
+ *   bwd: ONE read of n (+ ONE write of dneg): dl f32 [N x M] is d loss / d cosv (mh_infonce_rows_bwd);
+ *        dneg[i, j] = dl inv (q^[i] - cosv inv n[i, j]) in n's dtype (NULL: not written);
+ *        dq_part f32 [N x ceil(M / jc) x D] = per-chunk sums of dl inv n[i, j] over jc consecutive j (NULL: not formed), folded by
+ *        mh_infonce_fold.  N <= 65535, N * M < 2^31. */
+int mh_infonce_paired_fwd(const float* qn, const void* neg, float* cosv, float* inv, int N, int M, int D, float eps, int dt_neg,
+                          mh_stream s);
+int mh_infonce_paired_bwd(const float* qn, const void* neg, const float* cosv, const float* inv, const float* dl, void* dneg,
+                          float* dq_part, int N, int M, int D, int jc, int dt_neg, mh_stream s);
+/* The label-0 cross-entropy both modes share; neg f32 [N x M] with row stride ld holds the cosines (paired: cosv; unpaired: q^ n^T of
+ * mh_gemm).  fwd, with x0 = q^[i].k^[i] * inv_t: lse[i] = logsumexp([x0 | neg[i, :] * inv_t]), loss_rows[i] = lse[i] - x0,
+ * pneg[i] = 1 - softmax[i, 0] = sum_j exp(neg[i, j] inv_t - lse[i]) (all f32 [N], all written; a row whose positive dominates gets its
+ * loss as log1p of the negatives' sum, not as a difference of numbers near 1), out[0] = coef * sum_i loss_rows[i] (NULL: not formed).
+ * bwd: with u_i = gcoef * g[g_per_row ? i : 0] * inv_t:  dneg[i, j] = u_i exp(neg[i, j] inv_t - lse[i]) (f32 [N x M] contiguous),
+ * dpos[i] = -u_i pneg[i]. */
+int mh_infonce_rows_fwd(const float* qn, const float* kn, const float* neg, int64_t ld, int N, int M, int D, float inv_t, float coef,
+                        float* pneg, float* lse, float* loss_rows, float* out, mh_stream s);
+int mh_infonce_rows_bwd(const float* neg, int64_t ld, const float* pneg, const float* lse, const float* g, int g_per_row, float gcoef,
+                        float inv_t, int N, int M, float* dneg, float* dpos, mh_stream s);
+/* dq[i] = dpos[i] k^[i] + sum_p part[i, p, :] (p ascending; part f32 [N x nparts x D]: mh_infonce_paired_bwd's dq_part, or the
+ * unpaired dl n^ product with nparts = 1),  dk[i] = dpos[i] q^[i];  dq / dk NULL: not written. */
+int mh_infonce_fold(const float* dpos, const float* qn, const float* kn, const float* part, int nparts, float* dq, float* dk, int N,
+                    int D, mh_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,11 @@ _SIGS = {
     "mh_cls_ce_bwd": [P, L, P, I, I, I, F, L, P, I, P],
     "mh_cls_confusion": [P, L, I, P, I, I, I, P, P],
     "mh_auroc_counts": [P, L, P, I, I, P],
+    "mh_infonce_paired_fwd": [P, P, P, P, I, I, I, F, I],
+    "mh_infonce_paired_bwd": [P, P, P, P, P, P, P, I, I, I, I, I],
+    "mh_infonce_rows_fwd": [P, P, P, L, I, I, I, F, F, P, P, P, P],
+    "mh_infonce_rows_bwd": [P, L, P, P, P, I, F, F, I, I, P, P],
+    "mh_infonce_fold": [P, P, P, P, I, P, P, I, I],
 }
 EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "mh_gemm_select_pp", "mh_gemm_variant_name", "mh_device_ok", "mh_nys_attn3_ws_floats", "mh_rna_block_workspace_bytes",
                                  "mh_gemm_workspace_bytes", "mh_layernorm_bwd_workspace_bytes", "mh_nys_attn3_workspace_bytes",

@@ -2874,3 +2874,113 @@ class ClsCELossFn(Function):
         logits, labels = ctx.saved_tensors
         s, ignore_index, mode = ctx.cfg
         return K.cls_ce_bwd(logits, labels, s, ignore_index, g, mode), None, None, None, None
+
+
+# ------------------------------------------------------------------ InfoNCE with explicit negative keys (losses/info_nce.py:126-143)
+# Test tap: a list set here receives (entry point, what it wrote) for every launch the two Functions below issue.
+infonce_launches: Optional[list] = None
+
+
+def _nce_note(name: str, wrote: str) -> None:
+    if infonce_launches is not None:
+        infonce_launches.append((name, wrote))
+
+
+def _nce_out(rows, out, reduction):
+    return rows if reduction == "none" else out.reshape(())
+
+
+def _nce_tail_bwd(ctx, g, cosv):
+    """dl [N, M], dpos [N] of the shared label-0 cross-entropy for the upstream gradient g."""
+    _, _, pneg, lse = ctx.saved_tensors[:4]
+    N = cosv.shape[0]
+    gcoef = 1.0 / N if ctx.reduction == "mean" else 1.0
+    _nce_note("mh_infonce_rows_bwd", "dl[N,M]")
+    return K.infonce_rows_bwd(cosv, pneg, lse, g, gcoef, ctx.inv_t)
+
+
+class InfoNCEPairedFn(Function):
+    """CE([qn . kn | qn[i] . normalize(neg[i, j])] / t, 0) for normalised qn, kn [N, D] f32 and raw negatives [N, M, D] (f32 / bf16,
+    read in place).  One pass over neg per direction; saved: qn, kn, neg itself, the cosines and inverse norms [N, M], pneg, lse —
+    never a normalised [N, M, D].  Returns a 0-d tensor for "mean" / "sum", else [N]."""
+
+    @staticmethod
+    def forward(ctx, qn, kn, neg, inv_t, reduction):
+        neg = neg.contiguous()
+        N = qn.shape[0]
+        _nce_note("mh_infonce_paired_fwd", "cos[N,M],inv[N,M]")
+        cosv, inv = K.infonce_paired_fwd(qn, neg, 1e-12)
+        coef = 1.0 / N if reduction == "mean" else 1.0
+        _nce_note("mh_infonce_rows_fwd", "pneg[N],lse[N],rows[N]")
+        pneg, lse, rows, out = K.infonce_rows_fwd(qn, kn, cosv, inv_t, coef, reduction != "none")
+        ctx.save_for_backward(qn, kn, pneg, lse, neg, cosv, inv)
+        ctx.inv_t, ctx.reduction = inv_t, reduction
+        return _nce_out(rows, out, reduction)
+
+    @staticmethod
+    def backward(ctx, g):
+        qn, kn, pneg, lse, neg, cosv, inv = ctx.saved_tensors
+        need_q, need_k, need_n = ctx.needs_input_grad[:3]
+        if not (need_q or need_k or need_n):
+            return None, None, None, None, None
+        dl, dpos = _nce_tail_bwd(ctx, g, cosv)
+        dneg = part = None
+        if need_q or need_n:
+            _nce_note("mh_infonce_paired_bwd", ("dneg[N,M,D]," if need_n else "") + ("dq_part[N,chunks,D]" if need_q else ""))
+            dneg, part = K.infonce_paired_bwd(qn, neg, cosv, inv, dl, need_n, need_q)
+        dq = dk = None
+        if need_q or need_k:
+            _nce_note("mh_infonce_fold", "dq[N,D],dk[N,D]")
+            dq, dk = K.infonce_fold(dpos, qn, kn, part, need_q, need_k)
+        return dq, dk, dneg, None, None
+
+
+class InfoNCEUnpairedFn(Function):
+    """CE([qn . kn | qn normalize(bank)^T] / t, 0) for normalised qn, kn [N, D] f32 and a raw bank [M, D] (f32 / bf16, read in place).
+    The products are exact-f32 mh_gemm calls against the bank's normalised f32 copy; a bank that needs no gradient costs no
+    [M, D]-sized backward work.  Returns a 0-d tensor for "mean" / "sum", else [N]."""
+
+    @staticmethod
+    def forward(ctx, qn, kn, bank, inv_t, reduction):
+        bank = bank.contiguous()
+        N, D = qn.shape
+        M = bank.shape[0]
+        _nce_note("mh_l2norm_fwd", "n^[M,D],nrm[M]")
+        bn, nrm = K.l2norm_fwd(bank, M, D, D, 1e-12, f32)
+        _nce_note("mh_gemm", "cos[N,M]")
+        cosv = K.gemm(qn, bn.t(), mma=MH_F32)
+        coef = 1.0 / N if reduction == "mean" else 1.0
+        _nce_note("mh_infonce_rows_fwd", "pneg[N],lse[N],rows[N]")
+        pneg, lse, rows, out = K.infonce_rows_fwd(qn, kn, cosv, inv_t, coef, reduction != "none")
+        ctx.save_for_backward(qn, kn, pneg, lse, cosv, bn, nrm)
+        ctx.inv_t, ctx.reduction, ctx.bank_dtype = inv_t, reduction, bank.dtype
+        return _nce_out(rows, out, reduction)
+
+    @staticmethod
+    def backward(ctx, g):
+        qn, kn, pneg, lse, cosv, bn, nrm = ctx.saved_tensors
+        need_q, need_k, need_n = ctx.needs_input_grad[:3]
+        if not (need_q or need_k or need_n):
+            return None, None, None, None, None
+        dl, dpos = _nce_tail_bwd(ctx, g, cosv)
+        M, D = bn.shape
+        dq = dk = dbank = None
+        if need_q or need_k:
+            part = None
+            if need_q:
+                # dl n^ is a [N, D] result over K = M: a handful of workgroups walking the whole bank.  Split the bank into S
+                # slices as a batched product (exact f32 each) and let the fold add the S partial results in a fixed order.
+                N = qn.shape[0]
+                S = K.infonce_bank_split(M)
+                part = torch.empty((N, S, D), device=bn.device, dtype=f32)
+                _nce_note("mh_gemm", "dq_part[N,S,D]")
+                K.gemm(dl.view(N, S, M // S).permute(1, 0, 2), bn.view(S, M // S, D), out=part.permute(1, 0, 2), mma=MH_F32)
+            _nce_note("mh_infonce_fold", "dq[N,D],dk[N,D]")
+            dq, dk = K.infonce_fold(dpos, qn, kn, part, need_q, need_k)
+        if need_n:
+            _nce_note("mh_gemm", "dn^[M,D]")
+            dbn = K.gemm(dl.t(), qn, mma=MH_F32)
+            dbank = torch.empty((M, D), device=bn.device, dtype=ctx.bank_dtype)
+            _nce_note("mh_l2norm_bwd", "dbank[M,D]")
+            K.l2norm_bwd(bn, nrm, dbn, dbank, M, D, D, accumulate=False)
+        return dq, dk, dbank, None, None

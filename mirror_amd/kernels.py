@@ -2005,3 +2005,119 @@ def auroc_counts(scores: torch.Tensor, labels_i64: torch.Tensor) -> torch.Tensor
     counts = torch.empty((C, 4), device=scores.device, dtype=torch.int64)
     _lib.call("mh_auroc_counts", _p(scores), _ld(scores), _p(labels_i64), N, C, _p(counts), stream=_stream())
     return counts
+
+
+# ----------------------------------------------------------------------------- InfoNCE with explicit negative keys (csrc/infonce.hip)
+def _nce_f32(t: torch.Tensor, shape, name: str) -> torch.Tensor:
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise MirrorHipError(f"infonce: {name} must be contiguous f32 {tuple(shape)}, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    return t
+
+
+def _nce_paired(qn: torch.Tensor, neg: torch.Tensor):
+    _chk(qn, neg)
+    if neg.dim() != 3 or not neg.is_contiguous():
+        raise MirrorHipError(f"infonce: paired negative_keys must be contiguous [N, M, D], got {tuple(neg.shape)} strides {neg.stride()}")
+    N, M, D = neg.shape
+    _nce_f32(qn, (N, D), "the normalised query")
+    if N < 1 or M < 1 or D < 1 or N > 65535 or N * M >= (1 << 31):
+        raise MirrorHipError(f"infonce: paired negative_keys {tuple(neg.shape)}: need 1 <= N <= 65535, M, D >= 1 and N * M < 2^31")
+    return N, M, D
+
+
+def infonce_paired_fwd(qn: torch.Tensor, neg: torch.Tensor, eps: float):
+    """(cos, inv) f32 [N, M]: cos[i, j] = qn[i] . neg[i, j] / max(|neg[i, j]|, eps), inv = 1 / max(|neg[i, j]|, eps); neg is read once,
+    in its own dtype."""
+    N, M, D = _nce_paired(qn, neg)
+    cosv = torch.empty((N, M), device=neg.device, dtype=torch.float32)
+    inv = torch.empty((N, M), device=neg.device, dtype=torch.float32)
+    _lib.call("mh_infonce_paired_fwd", _p(qn), _p(neg), _p(cosv), _p(inv), N, M, D, eps, dt(neg), stream=_stream())
+    return cosv, inv
+
+
+def infonce_paired_chunk(N: int, M: int, D: int) -> int:
+    """Rows j one workgroup of the paired backward walks: 16..256, small enough for ~2048 workgroups where the shape allows it
+    (every chunk costs one [D] partial row of the query gradient)."""
+    jc = 256
+    while jc > 16 and N * -(-M // jc) < 2048:
+        jc //= 2
+    return jc
+
+
+def infonce_paired_bwd(qn, neg, cosv, inv, dl, want_dneg: bool, want_dq: bool):
+    """(dneg or None, dq_part or None): dneg like neg; dq_part f32 [N, chunks, D] for infonce_fold.  neg is read once."""
+    N, M, D = _nce_paired(qn, neg)
+    for t, nm in ((cosv, "cos"), (inv, "inv"), (dl, "dl")):
+        _chk(t)
+        _nce_f32(t, (N, M), nm)
+    if not (want_dneg or want_dq):
+        raise MirrorHipError("infonce_paired_bwd: nothing to compute")
+    jc = infonce_paired_chunk(N, M, D)
+    dneg = torch.empty_like(neg) if want_dneg else None
+    part = torch.empty((N, -(-M // jc), D), device=neg.device, dtype=torch.float32) if want_dq else None
+    _lib.call("mh_infonce_paired_bwd", _p(qn), _p(neg), _p(cosv), _p(inv), _p(dl), _p(dneg), _p(part), N, M, D, jc, dt(neg),
+              stream=_stream())
+    return dneg, part
+
+
+def infonce_bank_split(M: int) -> int:
+    """Slices S (a power of two <= 64 that divides M, slices of >= 256 rows) the unpaired query gradient dl @ bank is split into."""
+    S = 1
+    while S < 64 and M % (2 * S) == 0 and M // (2 * S) >= 256:
+        S *= 2
+    return S
+
+
+def infonce_rows_fwd(qn, kn, neg, inv_t: float, coef: float, reduce: bool):
+    """Label-0 cross-entropy of [qn . kn | neg] * inv_t.  neg f32 [N, M] (unit column stride).  Returns (pneg, lse, rows, out): f32 [N]
+    each (pneg = 1 - softmax[:, 0]), out f32 [1] = coef * sum(rows) (None unless reduce)."""
+    _chk(qn, kn, neg)
+    if neg.dim() != 2 or neg.dtype != torch.float32 or (neg.stride(1) != 1 and neg.shape[1] > 1):
+        raise MirrorHipError(f"infonce: cosines must be f32 [N, M] with unit column stride, got {neg.dtype} {tuple(neg.shape)}")
+    N, M = neg.shape
+    D = qn.shape[1]
+    _nce_f32(qn, (N, D), "the normalised query")
+    _nce_f32(kn, (N, D), "the normalised positive key")
+    if N < 1 or M < 1 or D < 1:
+        raise MirrorHipError(f"infonce: empty operand N={N} M={M} D={D}")
+    pneg, lse, rows = (torch.empty((N,), device=neg.device, dtype=torch.float32) for _ in range(3))
+    out = torch.empty((1,), device=neg.device, dtype=torch.float32) if reduce else None
+    _lib.call("mh_infonce_rows_fwd", _p(qn), _p(kn), _p(neg), _ld(neg), N, M, D, inv_t, coef, _p(pneg), _p(lse), _p(rows), _p(out),
+              stream=_stream())
+    return pneg, lse, rows, out
+
+
+def infonce_rows_bwd(neg, pneg, lse, g, gcoef: float, inv_t: float):
+    """(dl f32 [N, M], dpos f32 [N]) for the upstream gcoef * g (g: one element, or one per row)."""
+    _chk(neg, pneg, lse, g)
+    N, M = neg.shape
+    if N > 65535:
+        raise MirrorHipError(f"infonce: N = {N} exceeds 65535 rows")
+    _nce_f32(pneg, (N,), "pneg")
+    _nce_f32(lse, (N,), "lse")
+    g = g.reshape(-1).contiguous().float()
+    if g.numel() not in (1, N):
+        raise MirrorHipError(f"infonce: upstream gradient must have 1 or {N} elements, got {g.numel()}")
+    dl = torch.empty((N, M), device=neg.device, dtype=torch.float32)
+    dpos = torch.empty((N,), device=neg.device, dtype=torch.float32)
+    _lib.call("mh_infonce_rows_bwd", _p(neg), _ld(neg), _p(pneg), _p(lse), _p(g), int(g.numel() == N and N > 1), gcoef, inv_t, N, M,
+              _p(dl), _p(dpos), stream=_stream())
+    return dl, dpos
+
+
+def infonce_fold(dpos, qn, kn, part: Optional[torch.Tensor], want_dq: bool, want_dk: bool):
+    """(dq, dk) f32 [N, D] (None where not wanted): dq = dpos[:, None] * kn + part.sum(1), dk = dpos[:, None] * qn."""
+    _chk(dpos, qn, kn, part)
+    N, D = qn.shape
+    _nce_f32(kn, (N, D), "the normalised positive key")
+    _nce_f32(dpos, (N,), "dpos")
+    nparts = 0
+    if want_dq:
+        if part is None or part.dim() != 3 or part.shape[0] != N or part.shape[2] != D:
+            raise MirrorHipError("infonce_fold: the query gradient needs its partial sums [N, parts, D]")
+        nparts = part.shape[1]
+        _nce_f32(part, (N, nparts, D), "part")
+    dq = torch.empty((N, D), device=qn.device, dtype=torch.float32) if want_dq else None
+    dk = torch.empty((N, D), device=qn.device, dtype=torch.float32) if want_dk else None
+    _lib.call("mh_infonce_fold", _p(dpos), _p(qn), _p(kn), _p(part) if want_dq else None, nparts, _p(dq), _p(dk), N, D, stream=_stream())
+    return dq, dk

@@ -1,8 +1,17 @@
 """InfoNCE on HIP kernels — host-side mirror of the reference's `losses/info_nce.py` (same kwargs and checks).
 
-Only the `negative_keys=None` branch is functional in the reference (losses/info_nce.py:144-164): its
-explicit-negatives branch builds logits/labels but never assigns `loss`, so `return loss` raises
-UnboundLocalError.  That branch has no oracle; it raises NotImplementedError here.
+`negative_keys=None` (losses/info_nce.py:144-164): the other samples' positive keys are the negatives; `symmetric` adds the
+transposed term.
+
+Explicit `negative_keys` (losses/info_nce.py:126-143): the reference builds `logits = cat([pos, neg], 1)` and `labels = 0` and never
+assigns `loss`, so its `return loss` raises UnboundLocalError.  The line it forgets is the
+`F.cross_entropy(logits / temperature, labels, reduction=reduction)` of the info-nce-pytorch package the file was copied from, and
+that is what runs here:  with q^, k^, n^ = F.normalize(.., dim=-1),
+    pos[i] = q^[i].k^[i];   neg[i, j] = q^[i].n^[j] ("unpaired", negative_keys [M, D]) or q^[i].n^[i, j] ("paired", [N, M, D]);
+    row[i] = logsumexp([pos[i] | neg[i, :]] / temperature) - pos[i] / temperature;   reduction "mean" / "sum" -> 0-d, "none" -> [N].
+`symmetric` is ignored when `negative_keys` is given: the reference reads that flag only inside its implicit-negatives branch
+(:153-164).  `negative_keys` may be f32 or bf16 and is read in place in its own dtype (its gradient comes back in that dtype);
+norms, products and the log-sum-exp are f32.  A `negative_keys` that does not require grad costs no backward pass over it.
 """
 from __future__ import annotations
 
@@ -10,6 +19,7 @@ import torch
 from torch import nn
 
 from .. import functional as Fn
+from .. import kernels as K
 
 __all__ = ["InfoNCE"]
 f32 = torch.float32
@@ -49,10 +59,10 @@ class InfoNCE(nn.Module):
         if negative_keys is not None:
             if query.shape[-1] != negative_keys.shape[-1]:
                 raise ValueError("Vectors of <query> and <negative_keys> should have the same number of components.")
-            raise NotImplementedError("explicit negative_keys: the reference's own branch is non-functional "
-                                      "(UnboundLocalError at losses/info_nce.py:166); no oracle to match")
         if reduction not in ("mean", "sum", "none"):
             raise ValueError(f"{reduction} is not a valid value for reduction")
+        if negative_keys is not None:
+            return self._explicit_negatives(query, positive_key, negative_keys, temperature, reduction, negative_mode)
         n = query.shape[0]
         q = Fn.L2NormRowFn.apply(query.float(), 1e-12, f32)          # F.normalize(dim=-1), losses/info_nce.py:171-172
         k = Fn.L2NormRowFn.apply(positive_key.float(), 1e-12, f32)
@@ -63,6 +73,18 @@ class InfoNCE(nn.Module):
         if symmetric:
             loss = loss + Fn.CERowsFn.apply(Fn.MatmulNTFn.apply(k, q), None, 1.0 / temperature, 0, coef * half, per_row)
         return loss if per_row else loss.reshape(())
+
+    def _explicit_negatives(self, query, positive_key, negative_keys, temperature, reduction, negative_mode):
+        # CE(cat([pos, neg], 1) / temperature, 0): losses/info_nce.py:126-143 with the missing cross-entropy supplied
+        if negative_mode not in ("unpaired", "paired"):
+            raise ValueError(f"{negative_mode} is not a valid value for negative_mode")
+        if negative_keys.shape[-2] == 0:
+            raise ValueError("<negative_keys> must hold at least one negative key.")
+        K._chk(query, positive_key, negative_keys)
+        q = Fn.L2NormRowFn.apply(query.float(), 1e-12, f32)          # F.normalize(dim=-1), losses/info_nce.py:171-172
+        k = Fn.L2NormRowFn.apply(positive_key.float(), 1e-12, f32)
+        fn = Fn.InfoNCEPairedFn if negative_mode == "paired" else Fn.InfoNCEUnpairedFn
+        return fn.apply(q, k, negative_keys, 1.0 / temperature, reduction)
 
     def transpose(self, x):
         return x.transpose(-2, -1)
