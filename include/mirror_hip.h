@@ -709,6 +709,37 @@ int mh_adam_ema(float* p, const float* g, float* m, float* v, void* shadow_bf16,
 int mh_ema_update_many(float* ema, const int64_t* table, int nseg, float weight, const float* dev_state, const mh_ema_cfg* cfg,
                        mh_stream s);
 
+/* ---------------------------------------------------------------- the arena optimizer with weight decay (optim.hip; added to v121)
+ * train_mirror.py:742-746 `create_optimizer_v2(model, **optimizer_kwargs(cfg=args))` (the same in train_subtyping.py and
+ * train_survival.py) for --opt adam / adamw / sgd / nesterov / momentum with --weight-decay, --momentum, --opt-eps, --opt-betas.
+ * Each rule follows torch's single-tensor path; grad_scale * dev_state[4] scales the gradient BEFORE any weight decay:
+ *   MH_OPT_ADAM   g' = gs g + wd p, then Adam on g'                                   torch.optim.Adam(weight_decay=wd)
+ *   MH_OPT_ADAMW  p *= 1 - lr wd, then Adam on gs g                                   torch.optim.AdamW
+ *   MH_OPT_SGD    g' = gs g + wd p; buf = momentum buf + g'; p -= lr (nesterov ? g' + momentum buf : buf)
+ *                 torch.optim.SGD(momentum, dampening=0, nesterov); a zero buffer gives torch's first-step buf = g'.
+ *                 momentum == 0: p -= lr g', m is not read (may be NULL).  v is never read by SGD (may be NULL).
+ * m: exp_avg / momentum_buffer, v: exp_avg_sq.  Weight decay is per parameter: group_map (nullable = no decay anywhere) holds one
+ * byte per 8-element block of the arena, (n + 7) / 8 bytes — every parameter starts on such a block — naming the block's decay
+ * group, and group_wd[n_groups <= 256] (device f32) that group's weight decay (timm's param_groups_weight_decay: 1-D and `.bias`
+ * parameters in a weight_decay = 0 group).  For a sub-range launch pass the map from the range's first block.
+ * dev_state (required), clamp_index / clamp_lo / clamp_hi, counter / counter_add, tick (0, 1, 2) and hole_lo / hole_hi are mh_adam's;
+ * lr is dev_state[3]; the tick advances t for SGD too (the EMA decay and fp8 delayed scaling read it) and leaves dev_state[1..2]
+ * alone there.  ema (nullable) + ema_cfg: mh_adam_ema's lerp of each element's final value, in the same pass.
+ * Deterministic (no atomics), graph capturable; the settings travel as host structs read at launch. */
+#define MH_OPT_ADAM 0
+#define MH_OPT_ADAMW 1
+#define MH_OPT_SGD 2
+typedef struct {
+    int rule;                 /* MH_OPT_* */
+    float beta1, beta2, eps;  /* the Adam rules */
+    float momentum;           /* MH_OPT_SGD */
+    int nesterov;
+} mh_optim_cfg;
+int mh_optim_step(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, const mh_optim_cfg* opt,
+                  const uint8_t* group_map, const float* group_wd, int n_groups, float grad_scale, float* dev_state,
+                  int64_t clamp_index, float clamp_lo, float clamp_hi, int64_t* counter, int64_t counter_add, int tick,
+                  int64_t hole_lo, int64_t hole_hi, float* ema, const mh_ema_cfg* ema_cfg, mh_stream s);
+
 /* clip-grad "norm" mode (train_mirror.py:1206-1230): dev_state[5] = ||grad_scale * g||_2, dev_state[4] =
  * min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0); scratch1 = one device float. */
 int mh_grad_clip(const float* g, int64_t n, float grad_scale, float max_norm, float* scratch1, float* dev_state, mh_stream s);

@@ -65,6 +65,15 @@ class EmaCfg(C.Structure):
                 ("update_after_step", C.c_int64), ("use_warmup", C.c_int32)]
 
 
+class OptimCfg(C.Structure):
+    """mh_optim_cfg of include/mirror_hip.h (field order = the header's)."""
+    _fields_ = [("rule", C.c_int32), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("momentum", C.c_float),
+                ("nesterov", C.c_int32)]
+
+
+OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
+
+
 class LossTermsDesc(C.Structure):
     """mh_loss_terms of include/mirror_hip.h (field order = the header's)."""
     _fields_ = [
@@ -190,6 +199,7 @@ _SIGS = {
     "mh_adam": [P, P, P, P, P, L, F, F, F, F, F, F, F, P, L, F, F, P, L, I, L, L],
     "mh_adam_ema": [P, P, P, P, P, L, F, F, F, F, F, F, F, P, L, F, F, P, L, I, L, L, P, P],
     "mh_ema_update_many": [P, P, I, F, P, P],
+    "mh_optim_step": [P, P, P, P, P, L, P, P, P, I, F, P, L, F, F, P, L, I, L, L, P, P],
     "mh_grad_clip": [P, L, F, F, P, P],
     "mh_rna_block_fwd": [C.POINTER(RnaBlockDesc)],
     "mh_rna_block_bwd": [C.POINTER(RnaBlockDesc)],

@@ -1,0 +1,160 @@
+// The arena optimizer with weight decay: torch.optim.Adam(weight_decay), torch.optim.AdamW and torch.optim.SGD(momentum, nesterov) over
+// the flat f32 arenas of TrainEngine (what timm's create_optimizer_v2 builds for --opt adam / adamw / sgd / nesterov / momentum,
+// train_mirror.py:742-746).  mh_adam (loss.hip) stays the wd = 0 Adam of the template configuration; everything it carries rides
+// here too: the device step state, the hole of a two-launch step, the clamped element, the dropout counter, the bf16 shadow, the EMA.
+//
+// HBM-bound, 4 elements per thread, 16-B accesses.  Bytes per parameter (f32 p r/w, g r, moments r/w, bf16 shadow w):
+//   adam / adamw  8 + 4 + 8 + 8 + 2 = 30      sgd (momentum)  8 + 4 + 8 + 2 = 22      sgd (momentum = 0)  8 + 4 + 2 = 14
+// plus 1/8 B for the decay-group byte of each 8-element block (every parameter starts on one), plus 8 B with the EMA.
+#include "common.h"
+
+// one update of one element; `wd` is the element's own weight decay, `c` what is uniform over the launch
+struct optim_consts {
+    float lr, b1, b2, eps, step, isq, mu, gscale;
+    int nesterov;
+};
+
+// The Adam rules with no decay must give mh_adam's bits (tests pin that), so the two moment updates are written with explicit fmaf in
+// the forms the compiler contracts adam_body's `b1 * m + (1 - b1) * gr` and `b2 * v + (1 - b2) * gr * gr` to: in its quad loop
+// m = fma(1 - b1, gr, b1 m), in its scalar tail (TAIL) m = fma(b1, m, (1 - b1) gr); v = fma((1 - b2) gr, gr, b2 v) in both.
+template <int RULE, bool MOM, bool TAIL = false>
+__device__ __forceinline__ void optim_elem(float& p, const float g, float& m, float& v, const float wd, const optim_consts& c) {
+    if constexpr (RULE == MH_OPT_SGD) {
+        const float gr = g * c.gscale + wd * p;          // grad.add(param, alpha=weight_decay)
+        float st = gr;
+        if constexpr (MOM) {
+            m = c.mu * m + gr;                           // buf.mul_(momentum).add_(grad): a zero buffer gives torch's first-step buf = grad
+            st = c.nesterov ? gr + c.mu * m : m;
+        }
+        p -= c.lr * st;
+    } else {
+        float gr = g * c.gscale;
+        if constexpr (RULE == MH_OPT_ADAM) gr += wd * p;             // L2: the decay goes through the moments
+        if constexpr (RULE == MH_OPT_ADAMW) p *= 1.f - c.lr * wd;    // decoupled: param.mul_(1 - lr * weight_decay) first
+        m = TAIL ? fmaf(c.b1, m, (1.f - c.b1) * gr) : fmaf(1.f - c.b1, gr, c.b1 * m);
+        v = fmaf((1.f - c.b2) * gr, gr, c.b2 * v);
+        p -= c.step * m / (sqrtf(v) * c.isq + c.eps);
+    }
+}
+
+// gmap: one byte per 8-element block = the block's decay group, group_wd[byte] its weight decay (NULL: no decay anywhere).
+// Quads [hole_lo4, hole_hi4) are left alone (the range the other launch of a two-launch step updates), as in mh_adam.
+template <int RULE, bool EMA, bool MOM>
+__global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, bf16_t* __restrict__ shadow, long n, mh_optim_cfg o,
+                                                    const uint8_t* __restrict__ gmap, const float* __restrict__ group_wd, int n_groups,
+                                                    float gscale, const float* __restrict__ state, long clamp_i, float clamp_lo,
+                                                    float clamp_hi, long hole_lo4, long hole_hi4, float* __restrict__ ema, mh_ema_cfg ecfg) {
+    __shared__ float wd_s[256];
+    __shared__ float ew_s;
+    if (gmap && (int)threadIdx.x < n_groups) wd_s[threadIdx.x] = group_wd[threadIdx.x];
+    if (EMA && threadIdx.x == 0) ew_s = ema_weight(ecfg, (double)state[0]);
+    __syncthreads();
+    const float ew = EMA ? ew_s : 0.f;
+    // device-resident step state {t, 1 - b1^t, 1 - b2^t, lr, clip, |g|}: nothing step-dependent is a launch argument
+    optim_consts c;
+    c.lr = state[3];
+    c.b1 = o.beta1; c.b2 = o.beta2; c.eps = o.eps; c.mu = o.momentum; c.nesterov = o.nesterov;
+    c.gscale = gscale * state[4];        // the gradient is scaled (average, clip factor) BEFORE any weight decay
+    c.step = RULE == MH_OPT_SGD ? 0.f : c.lr / state[1];
+    c.isq = RULE == MH_OPT_SGD ? 0.f : rsqrtf(state[2]);
+    const long n4 = n / 4;
+    const long hole = hole_hi4 - hole_lo4, live4 = n4 - hole;
+    for (long q0 = (long)blockIdx.x * 256 + threadIdx.x; q0 < live4; q0 += (long)gridDim.x * 256) {
+        const long q = q0 < hole_lo4 ? q0 : q0 + hole;       // the live quads are numbered densely: no idle threads over the hole
+        const float wd = gmap ? wd_s[gmap[q >> 1]] : 0.f;
+        float4 pp = reinterpret_cast<float4*>(p)[q];
+        const float4 gg = reinterpret_cast<const float4*>(g)[q];
+        float4 mm = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (MOM) mm = reinterpret_cast<float4*>(m)[q];
+        if constexpr (RULE != MH_OPT_SGD) vv = reinterpret_cast<float4*>(v)[q];
+        float* pa = &pp.x; const float* ga = &gg.x; float* ma = &mm.x; float* va = &vv.x;
+#pragma unroll
+        for (int e = 0; e < 4; e++) optim_elem<RULE, MOM>(pa[e], ga[e], ma[e], va[e], wd, c);
+        // one element (logit_scale, train_mirror.py:1255) is clamped right behind its update: master, shadow and EMA get the clamped value
+        if ((clamp_i >> 2) == q && clamp_i >= 0) pa[clamp_i & 3] = fminf(fmaxf(pa[clamp_i & 3], clamp_lo), clamp_hi);
+        reinterpret_cast<float4*>(p)[q] = pp;
+        if constexpr (MOM) reinterpret_cast<float4*>(m)[q] = mm;
+        if constexpr (RULE != MH_OPT_SGD) reinterpret_cast<float4*>(v)[q] = vv;
+        if constexpr (EMA) {
+            float4 ee = reinterpret_cast<float4*>(ema)[q];
+            ee.x = ema_lerp(ee.x, pp.x, ew);
+            ee.y = ema_lerp(ee.y, pp.y, ew);
+            ee.z = ema_lerp(ee.z, pp.z, ew);
+            ee.w = ema_lerp(ee.w, pp.w, ew);
+            reinterpret_cast<float4*>(ema)[q] = ee;
+        }
+        if (shadow) {
+            uint2 sh;
+            sh.x = pack_bf2(pa[0], pa[1]);
+            sh.y = pack_bf2(pa[2], pa[3]);
+            reinterpret_cast<uint2*>(shadow)[q] = sh;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = n4 * 4 + threadIdx.x;
+        const float wd = gmap ? wd_s[gmap[i >> 3]] : 0.f;
+        float pn = p[i], mi = 0.f, vi = 0.f;
+        if constexpr (MOM) mi = m[i];
+        if constexpr (RULE != MH_OPT_SGD) vi = v[i];
+        optim_elem<RULE, MOM, true>(pn, g[i], mi, vi, wd, c);
+        if (i == clamp_i) pn = fminf(fmaxf(pn, clamp_lo), clamp_hi);
+        p[i] = pn;
+        if constexpr (MOM) m[i] = mi;
+        if constexpr (RULE != MH_OPT_SGD) v[i] = vi;
+        if (shadow) shadow[i] = f2bf(pn);
+        if constexpr (EMA) ema[i] = ema_lerp(ema[i], pn, ew);
+    }
+}
+
+// t += 1 on the device (SGD too: the EMA decay and the fp8 delayed scaling read t); the Adam rules refresh their bias corrections
+__global__ void optim_tick_kernel(float* state, int adam, float b1, float b2, long long* counter, long long counter_add) {
+    if (counter) *counter += counter_add;      // the dropout streams' device-side base (functional.dropout_step_end) rides along
+    if (!state) return;
+    const float t = state[0] + 1.f;
+    state[0] = t;
+    if (adam) {
+        state[1] = 1.f - powf(b1, t);
+        state[2] = 1.f - powf(b2, t);
+    }
+}
+
+extern "C" int mh_optim_step(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, const mh_optim_cfg* opt,
+                             const uint8_t* group_map, const float* group_wd, int n_groups, float gscale, float* dev_state,
+                             int64_t clamp_index, float clamp_lo, float clamp_hi, int64_t* counter, int64_t counter_add, int tick,
+                             int64_t hole_lo, int64_t hole_hi, float* ema, const mh_ema_cfg* ema_cfg, mh_stream s) {
+    if (n == 0) return MH_OK;
+    MH_REQUIRE(opt && (opt->rule == MH_OPT_ADAM || opt->rule == MH_OPT_ADAMW || opt->rule == MH_OPT_SGD), "mh_optim_step: no settings, or an unknown rule");
+    const bool sgd = opt->rule == MH_OPT_SGD, mom = !sgd || opt->momentum != 0.f;
+    MH_REQUIRE(dev_state, "mh_optim_step: lr, the step and the clip factor are read from dev_state: it is required");
+    MH_REQUIRE(p && g && (m || !mom) && (v || sgd), "mh_optim_step: a buffer the rule reads is NULL");
+    MH_REQUIRE(((uintptr_t)p & 15) == 0 && ((uintptr_t)g & 15) == 0 && ((uintptr_t)m & 15) == 0 && ((uintptr_t)v & 15) == 0 &&
+                   ((uintptr_t)shadow & 7) == 0 && ((uintptr_t)ema & 15) == 0, "mh_optim_step: buffers must be 16-byte aligned");
+    MH_REQUIRE(!sgd || !opt->nesterov || opt->momentum > 0.f, "mh_optim_step: Nesterov momentum requires a momentum");
+    MH_REQUIRE(!group_map || (group_wd && n_groups >= 1 && n_groups <= 256), "mh_optim_step: a group map needs 1..256 group decays");
+    MH_REQUIRE(!ema || (ema_cfg && ema_cfg->warmup_gamma > 0.0), "mh_optim_step: the EMA needs settings with warmup_gamma > 0");
+    MH_REQUIRE(clamp_index < n, "mh_optim_step: clamp_index %ld outside the %ld parameters", (long)clamp_index, (long)n);
+    MH_REQUIRE(hole_lo >= 0 && hole_lo <= hole_hi && hole_hi <= n && hole_lo % 4 == 0 && (hole_hi % 4 == 0 || hole_hi == hole_lo) &&
+                   (clamp_index < hole_lo || clamp_index >= hole_hi || hole_lo == hole_hi),
+               "mh_optim_step: hole [%ld, %ld) must be quad-aligned, inside the %ld parameters and not hold the clamped one", (long)hole_lo, (long)hole_hi, (long)n);
+    if (tick || counter)
+        hipLaunchKernelGGL(optim_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, tick ? dev_state : nullptr, sgd ? 0 : 1, opt->beta1,
+                           opt->beta2, (long long*)counter, (long long)counter_add);
+    const long live = n - (hole_hi - hole_lo);
+    if (live == 0) return MH_OK;
+    const mh_ema_cfg ec = ema ? *ema_cfg : mh_ema_cfg{0.0, 0.0, 1.0, 0.0, 0, 0};
+#define OPTIM_LAUNCH_(RULE, EMA, MOM)                                                                                                     \
+    hipLaunchKernelGGL((optim_kernel<RULE, EMA, MOM>), dim3((unsigned)min((long)mh_cdiv(mh_cdiv(live, 4), 256), 8192L)), dim3(256), 0,   \
+                       (hipStream_t)s, p, g, m, v, (bf16_t*)shadow, (long)n, *opt, group_map, group_wd, n_groups, gscale,                 \
+                       (const float*)dev_state, clamp_index < 0 ? -1L : (long)clamp_index, clamp_lo, clamp_hi, (long)(hole_lo / 4),       \
+                       (long)(hole_hi / 4), ema, ec)
+#define OPTIM_RULE_(RULE, MOM) do { if (ema) OPTIM_LAUNCH_(RULE, true, MOM); else OPTIM_LAUNCH_(RULE, false, MOM); } while (0)
+    if (opt->rule == MH_OPT_ADAM) OPTIM_RULE_(MH_OPT_ADAM, true);
+    else if (opt->rule == MH_OPT_ADAMW) OPTIM_RULE_(MH_OPT_ADAMW, true);
+    else if (mom) OPTIM_RULE_(MH_OPT_SGD, true);
+    else OPTIM_RULE_(MH_OPT_SGD, false);
+#undef OPTIM_RULE_
+#undef OPTIM_LAUNCH_
+    MH_LAUNCH_CHECK("mh_optim_step");
+    return MH_OK;
+}

@@ -46,6 +46,23 @@ def plan_buckets(sizes: Sequence[int], cap_elems: int, align: int = _ALIGN):
     return buckets, owner
 
 
+# timm's --opt values that create_optimizer_v2 maps to the three rules of mh_optim_step: name -> (rule, nesterov)
+_OPTS = {"adam": ("adam", False), "adamw": ("adamw", False), "sgd": ("sgd", True), "nesterov": ("sgd", True), "momentum": ("sgd", False)}
+
+
+def decay_groups(model: torch.nn.Module, weight_decay: float, filter_bias_and_bn: bool = True):
+    """The parameter groups timm's create_optimizer_v2 hands to torch.optim (train_mirror.py:742-746), as [(weight_decay, [(name,
+    parameter), ...]), ...] over the trainable parameters in model.parameters() order.  With weight_decay > 0 and the filter on:
+    param_groups_weight_decay's [no_decay, decay], no_decay = `p.ndim <= 1 or name.endswith(".bias")` at weight_decay 0 (neither
+    model defines no_weight_decay()); otherwise one group that carries weight_decay."""
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    if not (weight_decay and filter_bias_and_bn):
+        return [(weight_decay, named)]
+    no_decay = [(n, p) for n, p in named if p.ndim <= 1 or n.endswith(".bias")]
+    decay = [(n, p) for n, p in named if not (p.ndim <= 1 or n.endswith(".bias"))]
+    return [(0.0, no_decay), (weight_decay, decay)]
+
+
 _EARLY_ADAM = True      # (test hook, round 5) the RNA encoder's share of the optimizer step on its branch's stream, beside the WSI backward
 
 
@@ -54,7 +71,8 @@ class TrainEngine:
                  precision: str = "bf16", wsi_mask_ratio: float = 0.75, rna_mask_ratio: float = 0.75,
                  bucket_mb: float = 25.0, process_group=None, graph: Optional[bool] = None,
                  clip_grad: Optional[float] = None, clip_mode: str = "norm", accum_steps: int = 1, seed: Optional[int] = None,
-                 snapshot_grads: bool = False, grad_reduce_dtype: str = "f32", model_ema=None):
+                 snapshot_grads: bool = False, grad_reduce_dtype: str = "f32", model_ema=None, opt: str = "adam",
+                 weight_decay: float = 0.0, momentum: float = 0.9, filter_bias_and_bn: bool = True):
         """grad_reduce_dtype: "f32" (default: the f32 arena slices are all-reduced in place) or "bf16" (BASELINE config 5 /
         SURVEY.md §8e "bf16 grads optional": each bucket is rounded to bf16 for the wire — half the xGMI bytes — summed by
         RCCL in bf16 and widened back into the f32 arena; Adam still reads f32).
@@ -65,7 +83,22 @@ class TrainEngine:
         model_ema: a mirror_amd.ema.ModelEmaV3 of `model` (train_mirror.py:787-799, :1283-1284).  Its arena takes the master arena's
         layout and every update step lerps it inside the Adam launches (mh_adam_ema, decay from the device step t = the reference's
         num_updates); parameters outside the arena (frozen ones) and f32 buffers follow in one mh_ema_update_many launch.  Its
-        `update(model, step=num_updates)` is then a checked no-op.  Not under the fp8 policy."""
+        `update(model, step=num_updates)` is then a checked no-op.  Not under the fp8 policy.
+        opt, weight_decay, momentum, filter_bias_and_bn: timm's optimizer_kwargs (create_optimizer_v2, train_mirror.py:742-746).
+        opt: "adam" (torch.optim.Adam; L2 decay), "adamw", "sgd" / "nesterov" (torch.optim.SGD with Nesterov momentum, as timm maps
+        both) or "momentum" (SGD without); lr / betas / eps are --lr / --opt-betas / --opt-eps.  With weight_decay > 0 and the filter
+        on, 1-D and `.bias` parameters do not decay (decay_groups).  "adam" with weight_decay 0 is the template's step (mh_adam);
+        everything else runs mh_optim_step over the same arenas (SGD allocates no second-moment arena, and no buffer at momentum 0)."""
+        if opt not in _OPTS:
+            raise NotImplementedError(f"opt {opt!r}: only {', '.join(map(repr, _OPTS))} are implemented (timm's other optimizers are not)")
+        self.opt = opt
+        self._rule, self.nesterov = _OPTS[opt]
+        self.weight_decay, self.momentum, self.filter_bias_and_bn = weight_decay, float(momentum), bool(filter_bias_and_bn)
+        if weight_decay < 0.0 or momentum < 0.0:
+            raise ValueError(f"weight_decay {weight_decay} and momentum {momentum} must not be negative")
+        if self._rule == "sgd" and self.nesterov and self.momentum <= 0.0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")        # torch.optim.SGD's own refusal
+        self._template_adam = self._rule == "adam" and not weight_decay          # the step as it always was: mh_adam / mh_adam_ema
         if precision not in POLICIES:
             raise ValueError(f"unknown precision {precision!r}")
         # timm's dispatch_clip_grad modes (train_mirror.py:1219-1229, --clip-mode): "norm" (the template's default: one fused
@@ -114,8 +147,9 @@ class TrainEngine:
         self.numel = total
         self.master = torch.zeros(total, device=self.device, dtype=f32)
         self.grad = torch.zeros(total, device=self.device, dtype=f32)
-        self.m = torch.zeros(total, device=self.device, dtype=f32)
-        self.v = torch.zeros(total, device=self.device, dtype=f32)
+        # exp_avg / momentum_buffer and exp_avg_sq: SGD has no second moment, and no buffer at all without momentum
+        self.m = torch.zeros(total, device=self.device, dtype=f32) if self._rule != "sgd" or self.momentum > 0.0 else None
+        self.v = torch.zeros(total, device=self.device, dtype=f32) if self._rule != "sgd" else None
         # bf16 copies of the master arena, and W^T of the 2-D weights (skinny data-gradient kernels stream them like forward weights)
         bf = self._bf = Fn.ArenaShadows(self.master, zip(order, offs)) if POLICIES[precision].act == bf16 else None
         self.shadow, self.shadow_t, self._t_params = (bf.flat, bf.flat_t, bf.t_params) if bf is not None else (None, None, [])
@@ -137,6 +171,23 @@ class TrainEngine:
         self._zero_pending = False
         self._t_stale = False
         self.sync_shadows()
+        self._opt_cfg = self._group_map = self._group_wd = None
+        if not self._template_adam:
+            from ._lib import OPT_ADAM, OPT_ADAMW, OPT_SGD, OptimCfg
+            rule = {"adam": OPT_ADAM, "adamw": OPT_ADAMW, "sgd": OPT_SGD}[self._rule]
+            self._opt_cfg = OptimCfg(rule, betas[0], betas[1], eps, self.momentum, int(self.nesterov))
+            if weight_decay:
+                # one byte per _ALIGN-element block of the arena names its decay group (a parameter's padding shares its last block
+                # and stays zero: p = g = m = 0 there); the kernel looks the group's weight decay up in a device table
+                groups = self._groups()
+                gmap = torch.zeros(total // _ALIGN, dtype=torch.uint8)
+                off = {id(p): o for p, o in zip(order, offs)}
+                for gi, (_, members) in enumerate(groups):
+                    for _, p in members:
+                        o = off[id(p)]
+                        gmap[o // _ALIGN:(o + p.numel() + _ALIGN - 1) // _ALIGN] = gi
+                self._group_map = gmap.to(self.device)
+                self._group_wd = torch.tensor([float(wd) for wd, _ in groups], dtype=f32).to(self.device)
         # gradient sink: Functions accumulate weight gradients straight into the arena (mirror_amd.functional._gbuf)
         self._slot_of = {p.data_ptr(): i for i, p in enumerate(order)}
         self._uses = [0] * len(order)        # sink writes per parameter per step, learnt during the first step
@@ -499,12 +550,7 @@ class TrainEngine:
                         # every gradient of rna_encoder.* was written on this stream (the branch's forward ran here, so did its backward
                         # nodes and the flush above): its share of the optimizer step runs now, beside the WSI encoder's backward,
                         # instead of behind it — the step's tail keeps only the WSI / heads share of mh_adam's 28 B per parameter
-                        b1, b2 = self.betas
-                        lo, hi = early
-                        K.adam(self.master[lo:hi], self.grad[lo:hi], self.m[lo:hi], self.v[lo:hi],
-                               None if self.shadow is None else self.shadow[lo:hi], self.lr, b1, b2, self.eps, 1.0, 1.0,
-                               grad_scale=1.0, dev_state=self._state, tick="early",
-                               **({} if self.model_ema is None else {"ema": self._ema_arena[lo:hi], "ema_cfg": self._ema_cfg}))
+                        self._update(1.0, tick="early", rng=early)
         finally:
             Fn._wgrad_queue = None
             Fn.set_grad_sink(None)
@@ -525,7 +571,6 @@ class TrainEngine:
         if self._snapshot_grads:
             self.grad_snap.copy_(self.grad)
         self.step_count += 1
-        b1, b2 = self.betas
         # buckets are SUM-reduced, micro-batch losses are means.  A window that force_update closed early is averaged over the
         # micro-steps it holds: the reference switches its divisor to `last_accum_steps` for the tail batches of an epoch
         # (train_mirror.py:1117-1131, :1192)
@@ -543,12 +588,9 @@ class TrainEngine:
         if self._logit is not None and self._logit.requires_grad:
             clamp = (self.offsets[self._index_of[id(self._logit)]], 0.0, math.log(100.0))
         base, used = Fn.dropout_step_take()
-        K.adam(self.master, self.grad, self.m, self.v, self.shadow, self.lr, b1, b2, self.eps, 1.0, 1.0,
-               grad_scale=gs,                  # the DDP / accumulation average is folded into Adam
-               dev_state=self._state,          # t, bias corrections, lr and the clip factor live on the device
-               clamp=clamp, counter=base, counter_add=used,
-               tick=early is None, hole=early,     # the RNA encoder's range was updated (and t advanced) beside the WSI backward
-               **({} if self.model_ema is None else {"ema": self._ema_arena[:self.numel], "ema_cfg": self._ema_cfg}))
+        self._update(gs,                       # the DDP / accumulation average is folded into the update
+                     clamp=clamp, counter=base, counter_add=used,
+                     tick=early is None, hole=early)     # the RNA encoder's range was updated (and t advanced) beside the WSI backward
         self._t_stale = self.shadow_t is not None
         if self._logit is not None and clamp is None:          # a frozen logit_scale is not in the arena
             K.clamp_(self._logit.data.reshape(1), 0.0, math.log(100.0))
@@ -558,6 +600,25 @@ class TrainEngine:
             self._ema_step()          # behind the clamp, as model_ema.update (:1284) follows it (:1255)
         self._zero_pending = True        # cleared by the next step, beside its forward (nobody reads the arena in between)
         return self._loss_out(losses)
+
+    def _update(self, gs: float, tick, rng: Optional[Tuple[int, int]] = None, **kw) -> None:
+        """The optimizer launch over the arena, or over its range `rng` (the early launch of a two-launch step).  t, the bias
+        corrections, lr and the clip factor live on the device (self._state); the bf16 shadow and the EMA are written in the same pass."""
+        lo, hi = (0, self.numel) if rng is None else rng
+
+        def cut(t):
+            return t if t is None or rng is None else t[lo:hi]
+        if self.model_ema is not None:
+            kw.update(ema=self._ema_arena[lo:hi], ema_cfg=self._ema_cfg)
+        if self._template_adam:
+            b1, b2 = self.betas
+            K.adam(cut(self.master), cut(self.grad), cut(self.m), cut(self.v), cut(self.shadow), self.lr, b1, b2, self.eps, 1.0, 1.0,
+                   grad_scale=gs, dev_state=self._state, tick=tick, **kw)
+            return
+        gmap = self._group_map
+        K.optim_step(cut(self.master), cut(self.grad), cut(self.m), cut(self.v), cut(self.shadow), self._opt_cfg, self._state,
+                     grad_scale=gs, group_map=None if gmap is None else gmap[lo // _ALIGN:hi // _ALIGN], group_wd=self._group_wd,
+                     tick=tick, **kw)
 
     @staticmethod
     def _loss_out(losses):
@@ -619,34 +680,77 @@ class TrainEngine:
         off = {id(p): o for p, o in zip(self.params, self.offsets)}
         return [(p, off[id(p)]) for p in self.model.parameters() if id(p) in off]
 
+    def _groups(self):
+        """decay_groups over the arena's parameters: the torch.optim param groups, in timm's order."""
+        off = {id(p) for p in self.params}
+        return [(wd, [(n, p) for n, p in members if id(p) in off])
+                for wd, members in decay_groups(self.model, self.weight_decay, self.filter_bias_and_bn)]
+
     def state_dict(self) -> dict:
-        """torch.optim.Adam-shaped state (what the reference checkpoints and `resume_checkpoint` reloads): per parameter, in
-        model.parameters() order, {step, exp_avg, exp_avg_sq} on the CPU."""
+        """The state of the matching torch.optim optimizer built as timm builds it (what the reference checkpoints and
+        `resume_checkpoint` reloads), on the CPU: param groups in decay_groups order, state indices running through them.
+        Adam / AdamW: {step, exp_avg, exp_avg_sq} per parameter; SGD: {momentum_buffer}, no state without momentum.  SGD keeps no
+        step: the engine's (the EMA decay and fp8 delayed scaling read it) travels as the extra top-level entry "step", which
+        torch.optim.SGD.load_state_dict ignores."""
         t = float(self._state[0].item())
-        state = {}
-        for i, (p, o) in enumerate(self._opt_order()):
-            n = p.numel()
-            state[i] = {"step": torch.tensor(t), "exp_avg": self.m[o:o + n].view(p.shape).cpu().clone(),
-                        "exp_avg_sq": self.v[o:o + n].view(p.shape).cpu().clone()}
-        group = {"lr": float(self.lr), "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False,
-                 "params": list(range(len(state)))}
-        return {"state": state, "param_groups": [group]}
+        off = {id(p): o for p, o in zip(self.params, self.offsets)}
+        if self._template_adam:
+            groups = [(0, [(None, p) for p, _ in self._opt_order()])]
+        else:
+            groups = self._groups()
+        state, out_groups, i = {}, [], 0
+        for wd, members in groups:
+            first = i
+            for _, p in members:
+                o, n = off[id(p)], p.numel()
+                if self._rule != "sgd":
+                    state[i] = {"step": torch.tensor(t), "exp_avg": self.m[o:o + n].view(p.shape).cpu().clone(),
+                                "exp_avg_sq": self.v[o:o + n].view(p.shape).cpu().clone()}
+                elif self.m is not None and t > 0:          # torch creates the buffer at a parameter's first step
+                    state[i] = {"momentum_buffer": self.m[o:o + n].view(p.shape).cpu().clone()}
+                i += 1
+            if self._rule != "sgd":
+                group = {"lr": float(self.lr), "betas": tuple(self.betas), "eps": self.eps, "weight_decay": wd, "amsgrad": False}
+            else:
+                group = {"lr": float(self.lr), "momentum": self.momentum, "dampening": 0, "weight_decay": wd, "nesterov": self.nesterov}
+            group["params"] = list(range(first, i))
+            out_groups.append(group)
+        sd = {"state": state, "param_groups": out_groups}
+        if self._rule == "sgd":
+            sd["step"] = t
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
-        order = self._opt_order()
+        groups = [(0, [(None, p) for p, _ in self._opt_order()])] if self._template_adam else self._groups()
+        order = [p for _, members in groups for _, p in members]
+        off = {id(p): o for p, o in zip(self.params, self.offsets)}
+        pg = sd.get("param_groups") or []
+        want = "momentum" if self._rule == "sgd" else "betas"
+        if pg and any(want not in g for g in pg):
+            raise ValueError(f"optimizer state of another rule: TrainEngine(opt={self.opt!r}) loads param groups that hold "
+                             f"{want!r}, these hold {sorted(k for k in pg[0] if k != 'params')}")
+        if pg and [len(g["params"]) for g in pg] != [len(members) for _, members in groups]:
+            raise ValueError(f"optimizer state has param groups of {[len(g['params']) for g in pg]} parameters, this engine's "
+                             f"(opt={self.opt!r}, weight_decay={self.weight_decay}) have {[len(m) for _, m in groups]}")
         if len(sd["state"]) not in (0, len(order)):
             raise ValueError(f"optimizer state has {len(sd['state'])} entries, the model has {len(order)} parameters")
-        t = 0.0
-        for i, (p, o) in enumerate(order):
+        t = float(sd.get("step", 0.0)) if self._rule == "sgd" else 0.0
+        for i, p in enumerate(order):
             st = sd["state"].get(i)
             if st is None:
                 continue
-            n = p.numel()
+            o, n = off[id(p)], p.numel()
+            if self._rule == "sgd":
+                if self.m is not None:
+                    self.m[o:o + n].copy_(st["momentum_buffer"].reshape(-1))
+                continue
+            if "exp_avg" not in st:
+                raise ValueError(f"optimizer state of another rule: entry {i} holds {sorted(st)}, not Adam's exp_avg / exp_avg_sq")
             self.m[o:o + n].copy_(st["exp_avg"].reshape(-1))
             self.v[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
             t = float(st["step"])
-        if sd.get("param_groups"):
-            self.lr = float(sd["param_groups"][0].get("lr", self.lr))
+        if pg:
+            self.lr = float(pg[0].get("lr", self.lr))
         b1, b2 = self.betas
         self._state[:4].copy_(torch.tensor([t, 1.0 - b1 ** t, 1.0 - b2 ** t, float(self.lr)]))
         self._state_lr = float(self.lr)

@@ -1816,6 +1816,42 @@ def adam(p, g, m, v, shadow, lr, b1, b2, eps, bc1, bc2, grad_scale=1.0, dev_stat
     _lib.call("mh_adam_ema", *args, _p(ema), C.addressof(ema_cfg), stream=_stream())
 
 
+def optim_step(p, g, m, v, shadow, opt_cfg, dev_state: torch.Tensor, grad_scale=1.0, group_map: Optional[torch.Tensor] = None,
+               group_wd: Optional[torch.Tensor] = None, clamp: Optional[tuple] = None, counter: Optional[torch.Tensor] = None,
+               counter_add: int = 0, tick=True, hole: Optional[tuple] = None, ema: Optional[torch.Tensor] = None, ema_cfg=None) -> None:
+    """mh_optim_step: torch.optim.Adam(weight_decay) / AdamW / SGD(momentum, nesterov) over flat f32 arenas, by opt_cfg
+    (_lib.OptimCfg).  m: exp_avg / momentum_buffer (None for SGD without momentum), v: exp_avg_sq (None for SGD).  group_map (uint8,
+    one entry per 8-element block of p) + group_wd (f32, one weight decay per group): per-parameter decay; None = no decay.
+    dev_state, clamp, counter, tick, hole, ema / ema_cfg: as in adam(); lr is dev_state[3]."""
+    _chk(p, g, m, v, shadow, dev_state, counter, ema, group_map, group_wd)
+    assert counter is None or (counter.dtype == torch.int64 and counter.numel() == 1)
+    n = p.numel()
+    ci, clo, chi = (-1, 0.0, 0.0) if clamp is None else (int(clamp[0]), float(clamp[1]), float(clamp[2]))
+    if ci >= n:
+        raise MirrorHipError("optim_step: clamp index outside the arena")
+    sgd = opt_cfg.rule == _lib.OPT_SGD
+    need = [p, g] + ([] if sgd and opt_cfg.momentum == 0.0 else [m]) + ([] if sgd else [v])
+    for t in need:
+        if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise MirrorHipError("optim_step: p, g and the moments the rule reads are contiguous f32 tensors of one size")
+    if shadow is not None and (shadow.dtype != torch.bfloat16 or not shadow.is_contiguous() or shadow.numel() != n):
+        raise MirrorHipError("optim_step: the shadow is a contiguous bf16 tensor of p's size")
+    if dev_state is None or dev_state.dtype != torch.float32 or dev_state.numel() != 6 or not dev_state.is_contiguous():
+        raise MirrorHipError("optim_step: dev_state is the f32[6] device step state")
+    ng = 0
+    if group_map is not None:
+        ng = 0 if group_wd is None else group_wd.numel()
+        if (group_map.dtype != torch.uint8 or not group_map.is_contiguous() or group_map.numel() < (n + 7) // 8
+                or group_wd is None or group_wd.dtype != torch.float32 or not group_wd.is_contiguous() or not 1 <= ng <= 256):
+            raise MirrorHipError("optim_step: group_map is uint8 with one entry per 8 elements, group_wd f32 with 1..256 decays")
+    if ema is not None and (ema.dtype != torch.float32 or not ema.is_contiguous() or ema.numel() != n or ema_cfg is None):
+        raise MirrorHipError("optim_step: the EMA buffer must be a contiguous f32 tensor of p's size, with ema_cfg")
+    _lib.call("mh_optim_step", _p(p), _p(g), _p(m), _p(v), _p(shadow), n, C.addressof(opt_cfg), _p(group_map),
+              _p(group_wd) if group_map is not None else None, ng, grad_scale, _p(dev_state), ci, clo, chi, _p(counter),
+              int(counter_add), 2 if tick == "early" else int(bool(tick)), *((0, 0) if hole is None else (int(hole[0]), int(hole[1]))),
+              _p(ema), None if ema is None else C.addressof(ema_cfg), stream=_stream())
+
+
 def ema_update_many(ema: torch.Tensor, table: torch.Tensor, nseg: int, weight: float = 1.0, dev_state: Optional[torch.Tensor] = None,
                     ema_cfg=None) -> None:
     """ema[o_i : o_i + n_i] = lerp(ema[o_i : o_i + n_i], src_i, w) for the rows {o_i, src_i address, n_i} of `table` (int64 [nseg, 3]
