@@ -665,7 +665,8 @@ int mh_loss_terms_bwd(const mh_loss_terms* d, mh_stream s);
  * contiguous) receives the bf16 copy of the result in the same pass */
 int mh_rownorm_(float* w, void* shadow_bf16, int rows, int D, float eps, mh_stream s);
 int mh_clamp_(float* x, int64_t n, float lo, float hi, mh_stream s);
-/* torch.optim.Adam (wd=0): flat f32 params/grads/moments; optional bf16 shadow copy of the params.
+/* torch.optim.Adam (wd=0): flat f32 params/grads/moments; optional bf16 shadow copy of the params.  This is mh_optim_step's rule
+ * MH_OPT_ADAM without a group map behind an older argument list: one device body (optim.hip) serves both, bit for bit.
  * dev_state (nullable, 6 device floats {t, 1-b1^t, 1-b2^t, lr, clip, |g|}): when given, t is advanced and the bias
  * corrections are refreshed ON THE DEVICE before the update, lr / bias_c1 / bias_c2 arguments are ignored and the
  * gradient is additionally scaled by dev_state[4] (1, or the factor mh_grad_clip left there) — nothing step-dependent
@@ -677,7 +678,10 @@ int mh_clamp_(float* x, int64_t n, float lo, float hi, mh_stream s);
  * step's last one): tick = 0 reads dev_state without advancing it (the other launch of the step did), and elements [hole_lo, hole_hi)
  * (quad-aligned, not holding clamp_index) are left untouched — the range the other launch updates.  tick = 1, hole_lo = hole_hi = 0:
  * the whole arena in one launch, as before.  tick = 2: like 1, for the EARLY launch of such a pair (it runs as `adam_range_kernel`, so that
- * profiling tools that cut a kernel trace into steps at `adam_kernel` keep working). */
+ * profiling tools that cut a kernel trace into steps at `adam_kernel` keep working).
+ * The kernel's name follows what is launched, not the entry point: rule Adam with no group map and no EMA runs as `adam_kernel` /
+ * `adam_range_kernel` from mh_optim_step too; every other launch runs as an `optim_kernel<rule, EMA, momentum>` instance.
+ * With dev_state == NULL (this entry point only) lr / bias_c1 / bias_c2 are the arguments and no clip factor is applied. */
 int mh_adam(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, float beta1,
             float beta2, float eps, float bias_c1, float bias_c2, float grad_scale, float* dev_state, int64_t clamp_index,
             float clamp_lo, float clamp_hi, int64_t* counter, int64_t counter_add, int tick, int64_t hole_lo, int64_t hole_hi,
@@ -691,7 +695,8 @@ int mh_adam(float* p, const float* g, float* m, float* v, void* shadow_bf16, int
  * torch.lerp's form (w < 0.5 ? e + w (p - e) : p - (p - e)(1 - w)); w = 1 is an exact copy.
  * mh_adam_ema: mh_adam (every argument keeps its meaning) plus ema (f32, laid out like p, 16-B aligned): each updated element's
  * final value (after the clamp) is lerped into ema in the same pass (+8 B per parameter), with t = dev_state[0] after the tick
- * (dev_state is required).  Both launches of a two-launch step run as `adam_ema_kernel`.
+ * (dev_state is required).  It is mh_optim_step's rule MH_OPT_ADAM with ema set and no group map; both launches of a two-launch step
+ * run as `optim_kernel<MH_OPT_ADAM, true, true>`, so tools that cut a trace at `adam_kernel` see no EMA step.
  * The settings travel as a host struct, read at launch (kernel arguments: a captured graph keeps them). */
 typedef struct {
     double decay, min_decay, warmup_gamma, warmup_power;   /* timm's ModelEmaV3 settings (warmup_gamma > 0) */
@@ -709,7 +714,8 @@ int mh_adam_ema(float* p, const float* g, float* m, float* v, void* shadow_bf16,
 int mh_ema_update_many(float* ema, const int64_t* table, int nseg, float weight, const float* dev_state, const mh_ema_cfg* cfg,
                        mh_stream s);
 
-/* ---------------------------------------------------------------- the arena optimizer with weight decay (optim.hip; added to v121)
+/* ---------------------------------------------------------------- the arena optimizer (optim.hip; added to v121)
+ * TrainEngine's update for every rule; mh_adam and mh_adam_ema above are its rule MH_OPT_ADAM without decay.
  * train_mirror.py:742-746 `create_optimizer_v2(model, **optimizer_kwargs(cfg=args))` (the same in train_subtyping.py and
  * train_survival.py) for --opt adam / adamw / sgd / nesterov / momentum with --weight-decay, --momentum, --opt-eps, --opt-betas.
  * Each rule follows torch's single-tensor path; grad_scale * dev_state[4] scales the gradient BEFORE any weight decay:
@@ -725,6 +731,7 @@ int mh_ema_update_many(float* ema, const int64_t* table, int nseg, float weight,
  * dev_state (required), clamp_index / clamp_lo / clamp_hi, counter / counter_add, tick (0, 1, 2) and hole_lo / hole_hi are mh_adam's;
  * lr is dev_state[3]; the tick advances t for SGD too (the EMA decay and fp8 delayed scaling read it) and leaves dev_state[1..2]
  * alone there.  ema (nullable) + ema_cfg: mh_adam_ema's lerp of each element's final value, in the same pass.
+ * Kernel names: see mh_adam.
  * Deterministic (no atomics), graph capturable; the settings travel as host structs read at launch. */
 #define MH_OPT_ADAM 0
 #define MH_OPT_ADAMW 1

@@ -153,8 +153,8 @@ static inline int mh_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
     if ((dt) == MH_F32) { using T = float; __VA_ARGS__; }       \
     else { using T = bf16_t; __VA_ARGS__; }
 
-// ---- model EMA (timm ModelEmaV3, train_mirror.py:787-799, :1284): the decay schedule and the lerp, shared by mh_adam_ema and
-// mh_ema_update_many.  ema_weight restates ModelEmaV3.get_decay(step) in double and returns the lerp weight 1 - decay rounded to
+// ---- model EMA (timm ModelEmaV3, train_mirror.py:787-799, :1284): the decay schedule and the lerp, shared by the arena optimizer
+// (optim.hip) and mh_ema_update_many.  ema_weight restates ModelEmaV3.get_decay(step) in double and returns the lerp weight 1 - decay rounded to
 // f32 once, as torch rounds the Python scalar that timm hands to _foreach_lerp_.
 __device__ inline float ema_weight(const mh_ema_cfg& c, double t) {
     const double step = fmax(0.0, t - (double)c.update_after_step - 1.0);

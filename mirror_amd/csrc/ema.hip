@@ -1,6 +1,6 @@
 // Model EMA over scattered source tensors (timm ModelEmaV3.update, train_mirror.py:1283-1284; train_subtyping.py:1293;
 // train_survival.py:1322): the standalone path, for an EMA whose parameters are not one optimizer arena (a plain torch.optim model,
-// frozen parameters, floating-point buffers).  The arena path is mh_adam_ema (loss.hip), which lerps inside the Adam pass.
+// frozen parameters, floating-point buffers).  The arena path is the optimizer's own pass (optim.hip), which lerps each element behind its update.
 #include "common.h"
 
 // One workgroup per table row {ema offset (elements), source address, n}: 16-B accesses where source and destination share their

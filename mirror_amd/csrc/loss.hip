@@ -470,177 +470,3 @@ extern "C" int mh_clamp_(float* x, int64_t n, float lo, float hi, mh_stream s) {
     MH_LAUNCH_CHECK("mh_clamp_");
     return MH_OK;
 }
-
-// torch.optim.Adam semantics (no weight decay, no amsgrad): 4 floats per thread, 16-B accesses (HBM-bound: 28 B/param).
-// EMA = true: the final parameter value (after the clamp) is also lerped into `ema` with weight `ew` (+8 B/param: mh_adam_ema)
-template <bool EMA = false>
-__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, bf16_t* __restrict__ shadow, long n, float lr, float b1,
-                                                   float b2, float eps, float bc1, float bc2, float gscale,
-                                                   const float* __restrict__ state, long clamp_i, float clamp_lo, float clamp_hi,
-                                                   long hole_lo4, long hole_hi4, float* __restrict__ ema = nullptr, float ew = 0.f) {
-    // quads [hole_lo4, hole_hi4) are left alone: a range another launch of the same step has already updated (the RNA encoder's
-    // parameters, whose gradients are complete 2 ms before the step's last one: TrainEngine's early update)
-    if (state) {   // device-resident step state {t, 1 - b1^t, 1 - b2^t, lr, clip}: nothing step-dependent is a launch argument
-        bc1 = state[1];
-        bc2 = state[2];
-        lr = state[3];
-        gscale *= state[4];     // gradient-clipping factor written by mh_grad_clip (1 when clipping is off)
-    }
-    const float step = lr / bc1;
-    const float isq = rsqrtf(bc2);
-    const long n4 = n / 4;
-    const long hole = hole_hi4 - hole_lo4, live4 = n4 - hole;
-    for (long q0 = (long)blockIdx.x * 256 + threadIdx.x; q0 < live4; q0 += (long)gridDim.x * 256) {
-        const long q = q0 < hole_lo4 ? q0 : q0 + hole;       // the live quads are numbered densely: no idle threads over the hole
-        float4 pp = reinterpret_cast<float4*>(p)[q];
-        const float4 gg = reinterpret_cast<const float4*>(g)[q];
-        float4 mm = reinterpret_cast<float4*>(m)[q];
-        float4 vv = reinterpret_cast<float4*>(v)[q];
-        float* pa = &pp.x; const float* ga = &gg.x; float* ma = &mm.x; float* va = &vv.x;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const float gr = ga[e] * gscale;
-            ma[e] = b1 * ma[e] + (1.f - b1) * gr;
-            va[e] = b2 * va[e] + (1.f - b2) * gr * gr;
-            pa[e] -= step * ma[e] / (sqrtf(va[e]) * isq + eps);
-        }
-        // one element (logit_scale, train_mirror.py:1255) is clamped right behind its update: master and shadow get the clamped value
-        if ((clamp_i >> 2) == q && clamp_i >= 0) pa[clamp_i & 3] = fminf(fmaxf(pa[clamp_i & 3], clamp_lo), clamp_hi);
-        reinterpret_cast<float4*>(p)[q] = pp;
-        reinterpret_cast<float4*>(m)[q] = mm;
-        reinterpret_cast<float4*>(v)[q] = vv;
-        if constexpr (EMA) {
-            float4 ee = reinterpret_cast<float4*>(ema)[q];
-            ee.x = ema_lerp(ee.x, pp.x, ew);
-            ee.y = ema_lerp(ee.y, pp.y, ew);
-            ee.z = ema_lerp(ee.z, pp.z, ew);
-            ee.w = ema_lerp(ee.w, pp.w, ew);
-            reinterpret_cast<float4*>(ema)[q] = ee;
-        }
-        if (shadow) {
-            uint2 sh;
-            sh.x = pack_bf2(pa[0], pa[1]);
-            sh.y = pack_bf2(pa[2], pa[3]);
-            reinterpret_cast<uint2*>(shadow)[q] = sh;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const long i = n4 * 4 + threadIdx.x;
-        const float gr = g[i] * gscale;
-        m[i] = b1 * m[i] + (1.f - b1) * gr;
-        v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
-        float pn = p[i] - step * m[i] / (sqrtf(v[i]) * isq + eps);
-        if (i == clamp_i) pn = fminf(fmaxf(pn, clamp_lo), clamp_hi);
-        p[i] = pn;
-        if (shadow) shadow[i] = f2bf(pn);
-        if constexpr (EMA) ema[i] = ema_lerp(ema[i], pn, ew);
-    }
-}
-
-#define ADAM_ARGS_ float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, bf16_t *__restrict__ shadow, \
-                   long n, float lr, float b1, float b2, float eps, float bc1, float bc2, float gscale, const float *__restrict__ state, \
-                   long clamp_i, float clamp_lo, float clamp_hi, long hole_lo4, long hole_hi4
-// the launch that ENDS a step (the whole arena, or everything around the hole): profiling tools cut a trace into steps at this name
-__global__ __launch_bounds__(256) void adam_kernel(ADAM_ARGS_) {
-    adam_body(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2, gscale, state, clamp_i, clamp_lo, clamp_hi, hole_lo4, hole_hi4);
-}
-// the early launch of a two-launch step (a sub-range, beside the backward): same arithmetic under another name
-__global__ __launch_bounds__(256) void adam_range_kernel(ADAM_ARGS_) {
-    adam_body(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2, gscale, state, clamp_i, clamp_lo, clamp_hi, hole_lo4, hole_hi4);
-}
-// Adam + model EMA in one pass (timm ModelEmaV3.update right behind optimizer.step, train_mirror.py:1254-1284): the EMA weight
-// 1 - decay(t) comes from the device step t = state[0] that the tick has just advanced, once per workgroup — nothing
-// step-dependent is a launch argument.  Launched under one name for both launches of a two-launch step (profiling tools that cut
-// traces at `adam_kernel` see no EMA step, which is never on the benched path)
-__global__ __launch_bounds__(256) void adam_ema_kernel(ADAM_ARGS_, float* __restrict__ ema, mh_ema_cfg cfg) {
-    __shared__ float ew_s;
-    if (threadIdx.x == 0) ew_s = ema_weight(cfg, (double)state[0]);
-    __syncthreads();
-    adam_body<true>(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2, gscale, state, clamp_i, clamp_lo, clamp_hi, hole_lo4, hole_hi4,
-                    ema, ew_s);
-}
-#undef ADAM_ARGS_
-
-// state = {t, 1 - b1^t, 1 - b2^t, lr, clip, |g|}: t += 1 and the bias corrections are refreshed on the device, so a
-// captured HIP graph of the whole step replays with the right Adam step every time
-__global__ void adam_tick_kernel(float* state, float b1, float b2, long long* counter, long long counter_add) {
-    if (counter) *counter += counter_add;      // the dropout streams' device-side base (functional.dropout_step_end) rides along
-    if (!state) return;
-    const float t = state[0] + 1.f;
-    state[0] = t;
-    state[1] = 1.f - powf(b1, t);
-    state[2] = 1.f - powf(b2, t);
-}
-
-// ---- gradient clipping by global L2 norm (timm's clip_grad "norm" mode, train_mirror.py:1206-1230): the factor stays on
-// the device (state[4]) and mh_adam multiplies it into its gradient scale — no host round trip, graph-capturable
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, long n, float* __restrict__ acc) {
-    __shared__ float red[4];
-    float s = 0.f;
-    const long n4 = n / 4;
-    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long)gridDim.x * 256) {
-        const float4 v = reinterpret_cast<const float4*>(g)[q];
-        s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const float v = g[n4 * 4 + threadIdx.x]; s += v * v; }
-    s = block_sum256(s, red);
-    if (threadIdx.x == 0) atomicAdd(acc, s);
-}
-__global__ void clip_factor_kernel(const float* acc, float gscale, float max_norm, float* state) {
-    const float norm = sqrtf(acc[0]) * gscale;
-    state[5] = norm;
-    state[4] = max_norm > 0.f ? fminf(1.f, max_norm / (norm + 1e-6f)) : 1.f;
-}
-
-extern "C" int mh_grad_clip(const float* g, int64_t n, float grad_scale, float max_norm, float* scratch1, float* dev_state,
-                            mh_stream s) {
-    MH_REQUIRE(((uintptr_t)g & 15) == 0 && dev_state && scratch1, "mh_grad_clip: bad arguments");
-    if (hipMemsetAsync(scratch1, 0, sizeof(float), (hipStream_t)s) != hipSuccess) { mh_set_error("mh_grad_clip: memset failed"); return MH_EHIP; }
-    if (n > 0) hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)min((long)mh_cdiv(mh_cdiv(n, 4), 256), 2048L)), dim3(256), 0, (hipStream_t)s, g, (long)n, scratch1);
-    hipLaunchKernelGGL(clip_factor_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, (const float*)scratch1, grad_scale, max_norm, dev_state);
-    MH_LAUNCH_CHECK("mh_grad_clip");
-    return MH_OK;
-}
-
-static int adam_launch(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, float lr, float b1, float b2,
-                       float eps, float bc1, float bc2, float gscale, float* dev_state, int64_t clamp_index, float clamp_lo,
-                       float clamp_hi, int64_t* counter, int64_t counter_add, int tick, int64_t hole_lo, int64_t hole_hi, float* ema,
-                       const mh_ema_cfg* cfg, mh_stream s, const char* name) {
-    if (n == 0) return MH_OK;
-    MH_REQUIRE(((uintptr_t)p & 15) == 0 && ((uintptr_t)g & 15) == 0 && ((uintptr_t)m & 15) == 0 && ((uintptr_t)v & 15) == 0 &&
-                   ((uintptr_t)shadow & 7) == 0, "%s: buffers must be 16-byte aligned", name);
-    MH_REQUIRE(clamp_index < n, "%s: clamp_index %ld outside the %ld parameters", name, (long)clamp_index, (long)n);
-    MH_REQUIRE(hole_lo >= 0 && hole_lo <= hole_hi && hole_hi <= n && hole_lo % 4 == 0 && (hole_hi % 4 == 0 || hole_hi == hole_lo) &&
-                   (clamp_index < hole_lo || clamp_index >= hole_hi || hole_lo == hole_hi),
-               "%s: hole [%ld, %ld) must be quad-aligned, inside the %ld parameters and not hold the clamped one", name, (long)hole_lo, (long)hole_hi, (long)n);
-    if ((dev_state && tick) || counter)
-        hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, tick ? dev_state : nullptr, b1, b2, (long long*)counter, (long long)counter_add);
-    const long live = n - (hole_hi - hole_lo);
-    if (live == 0) return MH_OK;
-#define ADAM_LAUNCH_(KERN, ...) hipLaunchKernelGGL(KERN, dim3((unsigned)min((long)mh_cdiv(mh_cdiv(live, 4), 256), 8192L)), dim3(256), 0, (hipStream_t)s, p, g, m, v, (bf16_t*)shadow, (long)n, lr, b1, b2, eps, bc1, bc2, gscale, (const float*)dev_state, \
-                       clamp_index < 0 ? -1L : (long)clamp_index, clamp_lo, clamp_hi, (long)(hole_lo / 4), (long)(hole_hi / 4) __VA_ARGS__)
-    if (ema) ADAM_LAUNCH_(adam_ema_kernel, , ema, *cfg);
-    else if (tick == 2) ADAM_LAUNCH_(adam_range_kernel); else ADAM_LAUNCH_(adam_kernel);
-#undef ADAM_LAUNCH_
-    MH_LAUNCH_CHECK(name);
-    return MH_OK;
-}
-
-extern "C" int mh_adam(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, float lr, float b1, float b2,
-                       float eps, float bc1, float bc2, float gscale, float* dev_state, int64_t clamp_index, float clamp_lo,
-                       float clamp_hi, int64_t* counter, int64_t counter_add, int tick, int64_t hole_lo, int64_t hole_hi, mh_stream s) {
-    return adam_launch(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2, gscale, dev_state, clamp_index, clamp_lo, clamp_hi, counter,
-                       counter_add, tick, hole_lo, hole_hi, nullptr, nullptr, s, "mh_adam");
-}
-
-extern "C" int mh_adam_ema(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, float lr, float b1, float b2,
-                           float eps, float bc1, float bc2, float gscale, float* dev_state, int64_t clamp_index, float clamp_lo,
-                           float clamp_hi, int64_t* counter, int64_t counter_add, int tick, int64_t hole_lo, int64_t hole_hi, float* ema,
-                           const mh_ema_cfg* cfg, mh_stream s) {
-    MH_REQUIRE(ema && ((uintptr_t)ema & 15) == 0, "mh_adam_ema: the EMA buffer must be 16-byte aligned");
-    MH_REQUIRE(dev_state, "mh_adam_ema: the EMA decay follows the device step: dev_state is required");
-    MH_REQUIRE(cfg && cfg->warmup_gamma > 0.0, "mh_adam_ema: no settings, or warmup_gamma <= 0");
-    return adam_launch(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2, gscale, dev_state, clamp_index, clamp_lo, clamp_hi, counter,
-                       counter_add, tick, hole_lo, hole_hi, ema, cfg, s, "mh_adam_ema");
-}

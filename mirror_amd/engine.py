@@ -81,14 +81,14 @@ class TrainEngine:
         into whatever seed `Fn.manual_seed` last set, so that ranks never draw identical dropout masks.
         snapshot_grads: keep a copy of the (reduced) gradient arena of the last update in `self.grad_snap` (tests).
         model_ema: a mirror_amd.ema.ModelEmaV3 of `model` (train_mirror.py:787-799, :1283-1284).  Its arena takes the master arena's
-        layout and every update step lerps it inside the Adam launches (mh_adam_ema, decay from the device step t = the reference's
+        layout and every update step lerps it inside the optimizer launches (decay from the device step t = the reference's
         num_updates); parameters outside the arena (frozen ones) and f32 buffers follow in one mh_ema_update_many launch.  Its
         `update(model, step=num_updates)` is then a checked no-op.  Not under the fp8 policy.
         opt, weight_decay, momentum, filter_bias_and_bn: timm's optimizer_kwargs (create_optimizer_v2, train_mirror.py:742-746).
         opt: "adam" (torch.optim.Adam; L2 decay), "adamw", "sgd" / "nesterov" (torch.optim.SGD with Nesterov momentum, as timm maps
         both) or "momentum" (SGD without); lr / betas / eps are --lr / --opt-betas / --opt-eps.  With weight_decay > 0 and the filter
-        on, 1-D and `.bias` parameters do not decay (decay_groups).  "adam" with weight_decay 0 is the template's step (mh_adam);
-        everything else runs mh_optim_step over the same arenas (SGD allocates no second-moment arena, and no buffer at momentum 0)."""
+        on, 1-D and `.bias` parameters do not decay (decay_groups).  "adam" with weight_decay 0 is the template's step.  Every rule
+        runs mh_optim_step over the same arenas (SGD allocates no second-moment arena, and no buffer at momentum 0)."""
         if opt not in _OPTS:
             raise NotImplementedError(f"opt {opt!r}: only {', '.join(map(repr, _OPTS))} are implemented (timm's other optimizers are not)")
         self.opt = opt
@@ -98,7 +98,6 @@ class TrainEngine:
             raise ValueError(f"weight_decay {weight_decay} and momentum {momentum} must not be negative")
         if self._rule == "sgd" and self.nesterov and self.momentum <= 0.0:
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")        # torch.optim.SGD's own refusal
-        self._template_adam = self._rule == "adam" and not weight_decay          # the step as it always was: mh_adam / mh_adam_ema
         if precision not in POLICIES:
             raise ValueError(f"unknown precision {precision!r}")
         # timm's dispatch_clip_grad modes (train_mirror.py:1219-1229, --clip-mode): "norm" (the template's default: one fused
@@ -171,23 +170,22 @@ class TrainEngine:
         self._zero_pending = False
         self._t_stale = False
         self.sync_shadows()
-        self._opt_cfg = self._group_map = self._group_wd = None
-        if not self._template_adam:
-            from ._lib import OPT_ADAM, OPT_ADAMW, OPT_SGD, OptimCfg
-            rule = {"adam": OPT_ADAM, "adamw": OPT_ADAMW, "sgd": OPT_SGD}[self._rule]
-            self._opt_cfg = OptimCfg(rule, betas[0], betas[1], eps, self.momentum, int(self.nesterov))
-            if weight_decay:
-                # one byte per _ALIGN-element block of the arena names its decay group (a parameter's padding shares its last block
-                # and stays zero: p = g = m = 0 there); the kernel looks the group's weight decay up in a device table
-                groups = self._groups()
-                gmap = torch.zeros(total // _ALIGN, dtype=torch.uint8)
-                off = {id(p): o for p, o in zip(order, offs)}
-                for gi, (_, members) in enumerate(groups):
-                    for _, p in members:
-                        o = off[id(p)]
-                        gmap[o // _ALIGN:(o + p.numel() + _ALIGN - 1) // _ALIGN] = gi
-                self._group_map = gmap.to(self.device)
-                self._group_wd = torch.tensor([float(wd) for wd, _ in groups], dtype=f32).to(self.device)
+        from ._lib import OPT_ADAM, OPT_ADAMW, OPT_SGD, OptimCfg
+        rule = {"adam": OPT_ADAM, "adamw": OPT_ADAMW, "sgd": OPT_SGD}[self._rule]
+        self._opt_cfg = OptimCfg(rule, betas[0], betas[1], eps, self.momentum, int(self.nesterov))
+        self._group_map = self._group_wd = None          # no decay anywhere: no map, and the kernel looks nothing up
+        if weight_decay:
+            # one byte per _ALIGN-element block of the arena names its decay group (a parameter's padding shares its last block
+            # and stays zero: p = g = m = 0 there); the kernel looks the group's weight decay up in a device table
+            groups = self._groups()
+            gmap = torch.zeros(total // _ALIGN, dtype=torch.uint8)
+            off = {id(p): o for p, o in zip(order, offs)}
+            for gi, (_, members) in enumerate(groups):
+                for _, p in members:
+                    o = off[id(p)]
+                    gmap[o // _ALIGN:(o + p.numel() + _ALIGN - 1) // _ALIGN] = gi
+            self._group_map = gmap.to(self.device)
+            self._group_wd = torch.tensor([float(wd) for wd, _ in groups], dtype=f32).to(self.device)
         # gradient sink: Functions accumulate weight gradients straight into the arena (mirror_amd.functional._gbuf)
         self._slot_of = {p.data_ptr(): i for i, p in enumerate(order)}
         self._uses = [0] * len(order)        # sink writes per parameter per step, learnt during the first step
@@ -197,7 +195,7 @@ class TrainEngine:
         self._index_of = {id(p): i for i, p in enumerate(order)}
         self._proto = getattr(model, "prototypes", None)
         self._logit = getattr(model, "logit_scale", None)
-        # step state on the device {t, 1 - b1^t, 1 - b2^t, lr}: advanced by mh_adam itself, so nothing that changes from
+        # step state on the device {t, 1 - b1^t, 1 - b2^t, lr, clip, |g|}: advanced by the optimizer launch itself, so nothing that changes from
         # step to step is a launch argument and the whole step can be replayed as one HIP graph
         self._state = torch.tensor([0.0, 0.0, 0.0, float(lr), 1.0, 0.0], device=self.device, dtype=f32)
         # timm's --clip-grad (mode "norm") and --grad-accum-steps (train_mirror.py:1192-1230): both stay on the device
@@ -248,7 +246,7 @@ class TrainEngine:
         self.model_ema = ema
 
     def _ema_step(self) -> None:
-        """The EMA of everything mh_adam_ema did not cover (frozen parameters, f32 buffers, integer buffers), right behind it."""
+        """The EMA of everything the optimizer launches did not cover (frozen parameters, f32 buffers, integer buffers), right behind it."""
         ema = self.model_ema
         if self._ema_rows:
             K.ema_update_many(self._ema_arena, self._ema_table, self._ema_rows, dev_state=self._state, ema_cfg=self._ema_cfg)
@@ -549,7 +547,7 @@ class TrainEngine:
                     if early is not None:
                         # every gradient of rna_encoder.* was written on this stream (the branch's forward ran here, so did its backward
                         # nodes and the flush above): its share of the optimizer step runs now, beside the WSI encoder's backward,
-                        # instead of behind it — the step's tail keeps only the WSI / heads share of mh_adam's 28 B per parameter
+                        # instead of behind it — the step's tail keeps only the WSI / heads share of the update's 30 B per parameter
                         self._update(1.0, tick="early", rng=early)
         finally:
             Fn._wgrad_queue = None
@@ -610,11 +608,6 @@ class TrainEngine:
             return t if t is None or rng is None else t[lo:hi]
         if self.model_ema is not None:
             kw.update(ema=self._ema_arena[lo:hi], ema_cfg=self._ema_cfg)
-        if self._template_adam:
-            b1, b2 = self.betas
-            K.adam(cut(self.master), cut(self.grad), cut(self.m), cut(self.v), cut(self.shadow), self.lr, b1, b2, self.eps, 1.0, 1.0,
-                   grad_scale=gs, dev_state=self._state, tick=tick, **kw)
-            return
         gmap = self._group_map
         K.optim_step(cut(self.master), cut(self.grad), cut(self.m), cut(self.v), cut(self.shadow), self._opt_cfg, self._state,
                      grad_scale=gs, group_map=None if gmap is None else gmap[lo // _ALIGN:hi // _ALIGN], group_wd=self._group_wd,
@@ -676,15 +669,12 @@ class TrainEngine:
         return OrderedDict((k, float(vals[j]) / n) for j, k in enumerate(self.LOSS_NAMES))
 
     # ------------------------------------------------------------------ optimizer state (resume_checkpoint, train_mirror.py:772-780)
-    def _opt_order(self) -> List[Tuple[torch.nn.Parameter, int]]:
-        off = {id(p): o for p, o in zip(self.params, self.offsets)}
-        return [(p, off[id(p)]) for p in self.model.parameters() if id(p) in off]
-
     def _groups(self):
-        """decay_groups over the arena's parameters: the torch.optim param groups, in timm's order."""
+        """decay_groups over the arena's parameters: the torch.optim param groups, in timm's order.  Without decay the one group
+        carries the int 0, torch.optim's own default, whatever zero the engine was given."""
         off = {id(p) for p in self.params}
         return [(wd, [(n, p) for n, p in members if id(p) in off])
-                for wd, members in decay_groups(self.model, self.weight_decay, self.filter_bias_and_bn)]
+                for wd, members in decay_groups(self.model, self.weight_decay or 0, self.filter_bias_and_bn)]
 
     def state_dict(self) -> dict:
         """The state of the matching torch.optim optimizer built as timm builds it (what the reference checkpoints and
@@ -694,12 +684,8 @@ class TrainEngine:
         torch.optim.SGD.load_state_dict ignores."""
         t = float(self._state[0].item())
         off = {id(p): o for p, o in zip(self.params, self.offsets)}
-        if self._template_adam:
-            groups = [(0, [(None, p) for p, _ in self._opt_order()])]
-        else:
-            groups = self._groups()
         state, out_groups, i = {}, [], 0
-        for wd, members in groups:
+        for wd, members in self._groups():
             first = i
             for _, p in members:
                 o, n = off[id(p)], p.numel()
@@ -721,7 +707,7 @@ class TrainEngine:
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
-        groups = [(0, [(None, p) for p, _ in self._opt_order()])] if self._template_adam else self._groups()
+        groups = self._groups()
         order = [p for _, members in groups for _, p in members]
         off = {id(p): o for p, o in zip(self.params, self.offsets)}
         pg = sd.get("param_groups") or []

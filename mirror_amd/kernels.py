@@ -1780,17 +1780,42 @@ def clamp_(x: torch.Tensor, lo: float, hi: float) -> None:
 
 
 def grad_clip(g: torch.Tensor, grad_scale: float, max_norm: float, dev_state: torch.Tensor) -> None:
-    """Global-L2-norm clipping factor into dev_state[4] (and the norm into dev_state[5]); mh_adam applies it."""
+    """Global-L2-norm clipping factor into dev_state[4] (and the norm into dev_state[5]); the optimizer launch applies it."""
     _chk(g, dev_state)
     assert g.dtype == torch.float32 and g.is_contiguous() and dev_state.numel() == 6
     scratch = torch.empty(1, device=g.device, dtype=torch.float32)
     _lib.call("mh_grad_clip", _p(g), g.numel(), grad_scale, max_norm, _p(scratch), _p(dev_state), stream=_stream())
 
 
+def _step_args(name: str, p, need, shadow, dev_state, clamp, counter, counter_add, tick, hole, ema, ema_cfg):
+    """What adam() and optim_step() share.  Checks the arenas (`need`: p, g and the moments the rule reads), the shadow, the device
+    step state, the counter and the EMA, and returns the arguments that mh_adam and mh_optim_step have in common behind dev_state:
+    (clamp index, lo, hi, counter, counter_add, tick, hole_lo, hole_hi)."""
+    n = p.numel()
+    for t in need:
+        if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise MirrorHipError(f"{name}: p, g and the moments the rule reads are contiguous f32 tensors of one size")
+    if shadow is not None and (shadow.dtype != torch.bfloat16 or not shadow.is_contiguous() or shadow.numel() != n):
+        raise MirrorHipError(f"{name}: the shadow is a contiguous bf16 tensor of p's size")
+    if dev_state is not None and (dev_state.dtype != torch.float32 or dev_state.numel() != 6 or not dev_state.is_contiguous()):
+        raise MirrorHipError(f"{name}: dev_state is the f32[6] device step state")
+    if counter is not None and (counter.dtype != torch.int64 or counter.numel() != 1):
+        raise MirrorHipError(f"{name}: the counter is one int64")
+    ci, clo, chi = (-1, 0.0, 0.0) if clamp is None else (int(clamp[0]), float(clamp[1]), float(clamp[2]))
+    if ci >= n:
+        raise MirrorHipError(f"{name}: clamp index outside the arena")
+    if ema is not None and (ema.dtype != torch.float32 or not ema.is_contiguous() or ema.numel() != n or ema_cfg is None
+                            or dev_state is None):
+        raise MirrorHipError(f"{name}: the EMA buffer must be a contiguous f32 tensor of p's size, with ema_cfg and dev_state")
+    lo, hi = (0, 0) if hole is None else (int(hole[0]), int(hole[1]))
+    return ci, clo, chi, _p(counter), int(counter_add), 2 if tick == "early" else int(bool(tick)), lo, hi
+
+
 def adam(p, g, m, v, shadow, lr, b1, b2, eps, bc1, bc2, grad_scale=1.0, dev_state: Optional[torch.Tensor] = None,
          clamp: Optional[tuple] = None, counter: Optional[torch.Tensor] = None, counter_add: int = 0, tick: bool = True,
          hole: Optional[tuple] = None, ema: Optional[torch.Tensor] = None, ema_cfg=None) -> None:
-    """dev_state: optional f32[6] device tensor {t, 1-b1^t, 1-b2^t, lr, clip, |g|}; when given the step count / bias
+    """mh_adam: torch.optim.Adam without weight decay over flat f32 arenas (TrainEngine steps through optim_step).
+    dev_state: optional f32[6] device tensor {t, 1-b1^t, 1-b2^t, lr, clip, |g|}; when given the step count / bias
     corrections / lr live on the device (advanced by the launch itself), lr, bc1, bc2 are ignored and the gradient is
     also scaled by dev_state[4] (the factor grad_clip left there, else 1).  clamp = (index, lo, hi): that one parameter is clamped
     behind its update (master and shadow); counter (int64[1]) += counter_add in the same launches.  tick=False: dev_state is read,
@@ -1798,57 +1823,36 @@ def adam(p, g, m, v, shadow, lr, b1, b2, eps, bc1, bc2, grad_scale=1.0, dev_stat
     ema (f32, p's size) + ema_cfg (_lib.EmaCfg, needs dev_state): mh_adam_ema — every updated element's final value is also lerped
     into `ema` with timm's ModelEmaV3 decay of the device step, in the same pass."""
     _chk(p, g, m, v, shadow, dev_state, counter, ema)
-    assert counter is None or (counter.dtype == torch.int64 and counter.numel() == 1)
-    ci, clo, chi = (-1, 0.0, 0.0) if clamp is None else (int(clamp[0]), float(clamp[1]), float(clamp[2]))
-    if ci >= p.numel():
-        raise MirrorHipError("adam: clamp index outside the arena")
-    for t in (p, g, m, v):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel()
-    assert dev_state is None or (dev_state.dtype == torch.float32 and dev_state.numel() == 6 and dev_state.is_contiguous())
-    args = (_p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), lr, b1, b2, eps, bc1, bc2, grad_scale,
-            _p(dev_state), ci, clo, chi, _p(counter), int(counter_add), 2 if tick == "early" else int(bool(tick)),
-            *((0, 0) if hole is None else (int(hole[0]), int(hole[1]))))
+    tail = _step_args("adam", p, (p, g, m, v), shadow, dev_state, clamp, counter, counter_add, tick, hole, ema, ema_cfg)
+    args = (_p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), lr, b1, b2, eps, bc1, bc2, grad_scale, _p(dev_state), *tail)
     if ema is None:
         _lib.call("mh_adam", *args, stream=_stream())
-        return
-    if not (ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() == p.numel()) or ema_cfg is None or dev_state is None:
-        raise MirrorHipError("adam: the EMA buffer must be a contiguous f32 tensor of p's size, with ema_cfg and dev_state")
-    _lib.call("mh_adam_ema", *args, _p(ema), C.addressof(ema_cfg), stream=_stream())
+    else:
+        _lib.call("mh_adam_ema", *args, _p(ema), C.addressof(ema_cfg), stream=_stream())
 
 
 def optim_step(p, g, m, v, shadow, opt_cfg, dev_state: torch.Tensor, grad_scale=1.0, group_map: Optional[torch.Tensor] = None,
                group_wd: Optional[torch.Tensor] = None, clamp: Optional[tuple] = None, counter: Optional[torch.Tensor] = None,
                counter_add: int = 0, tick=True, hole: Optional[tuple] = None, ema: Optional[torch.Tensor] = None, ema_cfg=None) -> None:
     """mh_optim_step: torch.optim.Adam(weight_decay) / AdamW / SGD(momentum, nesterov) over flat f32 arenas, by opt_cfg
-    (_lib.OptimCfg).  m: exp_avg / momentum_buffer (None for SGD without momentum), v: exp_avg_sq (None for SGD).  group_map (uint8,
-    one entry per 8-element block of p) + group_wd (f32, one weight decay per group): per-parameter decay; None = no decay.
-    dev_state, clamp, counter, tick, hole, ema / ema_cfg: as in adam(); lr is dev_state[3]."""
+    (_lib.OptimCfg); TrainEngine's update.  m: exp_avg / momentum_buffer (None for SGD without momentum), v: exp_avg_sq (None for
+    SGD).  group_map (uint8, one entry per 8-element block of p) + group_wd (f32, one weight decay per group): per-parameter decay;
+    None = no decay.  dev_state (required here), clamp, counter, tick, hole, ema / ema_cfg: as in adam(); lr is dev_state[3]."""
     _chk(p, g, m, v, shadow, dev_state, counter, ema, group_map, group_wd)
-    assert counter is None or (counter.dtype == torch.int64 and counter.numel() == 1)
     n = p.numel()
-    ci, clo, chi = (-1, 0.0, 0.0) if clamp is None else (int(clamp[0]), float(clamp[1]), float(clamp[2]))
-    if ci >= n:
-        raise MirrorHipError("optim_step: clamp index outside the arena")
     sgd = opt_cfg.rule == _lib.OPT_SGD
     need = [p, g] + ([] if sgd and opt_cfg.momentum == 0.0 else [m]) + ([] if sgd else [v])
-    for t in need:
-        if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
-            raise MirrorHipError("optim_step: p, g and the moments the rule reads are contiguous f32 tensors of one size")
-    if shadow is not None and (shadow.dtype != torch.bfloat16 or not shadow.is_contiguous() or shadow.numel() != n):
-        raise MirrorHipError("optim_step: the shadow is a contiguous bf16 tensor of p's size")
-    if dev_state is None or dev_state.dtype != torch.float32 or dev_state.numel() != 6 or not dev_state.is_contiguous():
+    if dev_state is None:
         raise MirrorHipError("optim_step: dev_state is the f32[6] device step state")
+    tail = _step_args("optim_step", p, need, shadow, dev_state, clamp, counter, counter_add, tick, hole, ema, ema_cfg)
     ng = 0
     if group_map is not None:
         ng = 0 if group_wd is None else group_wd.numel()
         if (group_map.dtype != torch.uint8 or not group_map.is_contiguous() or group_map.numel() < (n + 7) // 8
                 or group_wd is None or group_wd.dtype != torch.float32 or not group_wd.is_contiguous() or not 1 <= ng <= 256):
             raise MirrorHipError("optim_step: group_map is uint8 with one entry per 8 elements, group_wd f32 with 1..256 decays")
-    if ema is not None and (ema.dtype != torch.float32 or not ema.is_contiguous() or ema.numel() != n or ema_cfg is None):
-        raise MirrorHipError("optim_step: the EMA buffer must be a contiguous f32 tensor of p's size, with ema_cfg")
     _lib.call("mh_optim_step", _p(p), _p(g), _p(m), _p(v), _p(shadow), n, C.addressof(opt_cfg), _p(group_map),
-              _p(group_wd) if group_map is not None else None, ng, grad_scale, _p(dev_state), ci, clo, chi, _p(counter),
-              int(counter_add), 2 if tick == "early" else int(bool(tick)), *((0, 0) if hole is None else (int(hole[0]), int(hole[1]))),
+              _p(group_wd) if group_map is not None else None, ng, grad_scale, _p(dev_state), *tail,
               _p(ema), None if ema is None else C.addressof(ema_cfg), stream=_stream())
 
 

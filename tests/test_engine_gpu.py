@@ -435,7 +435,7 @@ def test_d512_graph_replay_matches_eager_launch():
 
 def test_early_adam_for_the_rna_encoder_equals_the_single_launch(monkeypatch):
     """Round 5: the RNA encoder's parameters (one contiguous range of the arena) are updated on the RNA branch's stream as soon as that
-    stream has flushed its weight gradients, the rest behind the backward with tick=False and a hole (TrainEngine.step, mh_adam).  Same
+    stream has flushed its weight gradients, the rest behind the backward with tick=False and a hole (TrainEngine.step, mh_optim_step).  Same
     seeds, whole-step graph: losses, first / second moments and the parameter trajectory equal those of the one-launch step up to the
     gradients' own f32-atomics noise; the device step counter advances once per step; configurations that couple the ranges (global
     clipping norm, accumulation) keep the single launch."""
@@ -445,12 +445,12 @@ def test_early_adam_for_the_rna_encoder_equals_the_single_launch(monkeypatch):
     from mirror_amd.engine import TrainEngine
     from mirror_amd.losses import MIRRORLoss
     calls = []
-    real = K.adam
+    real = K.optim_step
 
     def counting(*a, **kw):
         calls.append((a[0].numel(), kw.get("tick", True), kw.get("hole")))
         return real(*a, **kw)
-    monkeypatch.setattr(K, "adam", counting)
+    monkeypatch.setattr(K, "optim_step", counting)
     runs = []
     for early in (True, False):
         monkeypatch.setattr(E, "_EARLY_ADAM", early)

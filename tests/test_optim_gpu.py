@@ -498,7 +498,8 @@ def test_default_engine_dict_is_unchanged_and_unknown_modes_are_refused():
     from mirror_amd.engine import TrainEngine
     from mirror_amd.losses import MIRRORLoss
     eng = TrainEngine(_make(), MIRRORLoss(), lr=1e-3, precision="fp32")
-    assert eng._template_adam and eng._opt_cfg is None and eng._group_map is None
+    from mirror_amd import _lib
+    assert eng._opt_cfg.rule == _lib.OPT_ADAM and eng._group_map is None and eng._group_wd is None
     sd = eng.state_dict()
     (g,) = sd["param_groups"]
     assert list(g) == ["lr", "betas", "eps", "weight_decay", "amsgrad", "params"]

@@ -8,7 +8,7 @@ from mirror_amd.engine import TrainEngine
 from mirror_amd.losses import MIRRORLoss
 from mirror_amd import kernels as K
 seen = collections.Counter()
-real_ln, real_mse, real_ma, real_dc, real_adam = K.layernorm_bwd, K.mse_masked_bwd, K.mask_apply_bwd, K.dropout_lite_colsum, K.adam
+real_ln, real_mse, real_ma, real_dc, real_opt = K.layernorm_bwd, K.mse_masked_bwd, K.mask_apply_bwd, K.dropout_lite_colsum, K.optim_step
 
 
 def ln(*a, **kw):
@@ -33,12 +33,12 @@ def dc(*a, **kw):
     return real_dc(*a, **kw)
 
 
-def adam(*a, **kw):
-    seen[f"adam tick={kw.get('tick', True)} hole={'yes' if kw.get('hole') else 'no'}"] += 1
-    return real_adam(*a, **kw)
+def opt(*a, **kw):
+    seen[f"optim_step tick={kw.get('tick', True)} hole={'yes' if kw.get('hole') else 'no'}"] += 1
+    return real_opt(*a, **kw)
 
 
-K.layernorm_bwd, K.mse_masked_bwd, K.mask_apply_bwd, K.dropout_lite_colsum, K.adam = ln, mse, ma, dc, adam
+K.layernorm_bwd, K.mse_masked_bwd, K.mask_apply_bwd, K.dropout_lite_colsum, K.optim_step = ln, mse, ma, dc, opt
 dev = torch.device("cuda", 0)
 torch.manual_seed(42)
 model = M.mirror(wsi_embed_dim=1024, rna_embed_dim=2048, embed_dim=512, wsi_num_tokens=4096, rna_encoder_depth=6, rna_mlp_ratio=4.0,
