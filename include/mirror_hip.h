@@ -747,6 +747,28 @@ int mh_optim_step(float* p, const float* g, float* m, float* v, void* shadow_bf1
                   int64_t clamp_index, float clamp_lo, float clamp_hi, int64_t* counter, int64_t counter_add, int tick,
                   int64_t hole_lo, int64_t hole_hi, float* ema, const mh_ema_cfg* ema_cfg, mh_stream s);
 
+/* mh_optim_step with one learning rate per parameter group (torch.optim's param_groups[i]["lr"], which lr schedulers write): the
+ * update of mirror_amd.optim.ArenaOptimizer.  group_map is required here; group_lr[n_groups] (device f32) stands beside group_wd, and
+ * group_lr[g] takes the place of dev_state[3] for the elements of group g.  The step size lr / (1 - b1^t) is formed per group by the
+ * same division as mh_optim_step's, so a table that holds one value everywhere gives mh_optim_step's bits with that value in
+ * dev_state[3].  Both tables live in device memory: a captured graph replays with whatever they hold at the replay.
+ * The group byte MH_OPT_SKIP_GROUP (255) marks blocks the launch leaves untouched — p, m, v, shadow and ema keep their bits: torch.optim's
+ * treatment of a parameter whose .grad is None.  It has no table entry, so n_groups <= 255 here.
+ * Every other argument keeps mh_optim_step's meaning.  Runs as `optim_groups_kernel<rule, EMA, momentum>`. */
+#define MH_OPT_SKIP_GROUP 255
+int mh_optim_groups(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, const mh_optim_cfg* opt,
+                    const uint8_t* group_map, const float* group_wd, const float* group_lr, int n_groups, float grad_scale,
+                    float* dev_state, int64_t clamp_index, float clamp_lo, float clamp_hi, int64_t* counter, int64_t counter_add,
+                    int tick, int64_t hole_lo, int64_t hole_hi, float* ema, const mh_ema_cfg* ema_cfg, mh_stream s);
+
+/* arena[off_i + j] = (float) src_i[j] for j < n_i, for the nrows rows {off_i, (int64) src_i, n_i, dtype_i} of the device table (int64
+ * [nrows, 4]; dtype_i = MH_F32 or MH_BF16, a bf16 source is widened; src_i aligned to its element size; the destination ranges must
+ * not overlap): the write-side twin of mh_ema_update_many, one launch for gradients that were left outside the gradient arena and for
+ * loading optimizer state.  One workgroup per row: split long tensors into rows of a few 10^4 elements (a multiple of 8).  16-byte
+ * accesses where source and destination reach a 16-byte boundary at the same element (a scalar head up to it, a scalar tail), scalar
+ * otherwise.  HBM-bound: 8 B per f32 element, 6 B per bf16 element.  Deterministic, graph capturable. */
+int mh_gather_many(float* arena, const int64_t* table, int nrows, mh_stream s);
+
 /* clip-grad "norm" mode (train_mirror.py:1206-1230): dev_state[5] = ||grad_scale * g||_2, dev_state[4] =
  * min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0); scratch1 = one device float. */
 int mh_grad_clip(const float* g, int64_t n, float grad_scale, float max_norm, float* scratch1, float* dev_state, mh_stream s);

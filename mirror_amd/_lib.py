@@ -72,6 +72,7 @@ class OptimCfg(C.Structure):
 
 
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
+OPT_SKIP_GROUP = 255        # MH_OPT_SKIP_GROUP: the group byte of blocks that mh_optim_groups leaves untouched
 
 
 class LossTermsDesc(C.Structure):
@@ -200,6 +201,8 @@ _SIGS = {
     "mh_adam_ema": [P, P, P, P, P, L, F, F, F, F, F, F, F, P, L, F, F, P, L, I, L, L, P, P],
     "mh_ema_update_many": [P, P, I, F, P, P],
     "mh_optim_step": [P, P, P, P, P, L, P, P, P, I, F, P, L, F, F, P, L, I, L, L, P, P],
+    "mh_optim_groups": [P, P, P, P, P, L, P, P, P, P, I, F, P, L, F, F, P, L, I, L, L, P, P],
+    "mh_gather_many": [P, P, I],
     "mh_grad_clip": [P, L, F, F, P, P],
     "mh_rna_block_fwd": [C.POINTER(RnaBlockDesc)],
     "mh_rna_block_bwd": [C.POINTER(RnaBlockDesc)],

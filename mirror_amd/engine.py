@@ -63,6 +63,85 @@ def decay_groups(model: torch.nn.Module, weight_decay: float, filter_bias_and_bn
     return [(0.0, no_decay), (weight_decay, decay)]
 
 
+def arena_state_dict(rule: str, t: float, groups, off: dict, m, v, skip=()) -> dict:
+    """The torch.optim-shaped state dict of an arena optimizer (TrainEngine, optim.ArenaOptimizer), on the CPU.  rule: "adam" /
+    "adamw" / "sgd"; t: the arena's step count; groups: [(the group's settings in torch's key order, without "params", [parameters]),
+    ...]; off: id(parameter) -> arena offset; m, v: the moment arenas (None where the rule has none).  State indices run through the
+    groups; parameters whose id is in `skip` (never updated) have no entry, as in torch.  SGD's dict carries t as the top-level "step"."""
+    state, out_groups, i = {}, [], 0
+    for settings, members in groups:
+        first = i
+        for p in members:
+            o, n = off[id(p)], p.numel()
+            if id(p) in skip:
+                pass
+            elif rule != "sgd":
+                state[i] = {"step": torch.tensor(t), "exp_avg": m[o:o + n].view(p.shape).cpu().clone(),
+                            "exp_avg_sq": v[o:o + n].view(p.shape).cpu().clone()}
+            elif m is not None and t > 0:          # torch creates the buffer at a parameter's first step
+                state[i] = {"momentum_buffer": m[o:o + n].view(p.shape).cpu().clone()}
+            i += 1
+        group = dict(settings)
+        group["params"] = list(range(first, i))
+        out_groups.append(group)
+    sd = {"state": state, "param_groups": out_groups}
+    if rule == "sgd":
+        sd["step"] = t
+    return sd
+
+
+def _fill_arena(arena: torch.Tensor, items) -> None:
+    """arena[o : o + n] = tensor for (o, tensor) in items: the tensors already on the device in one mh_gather_many launch, the
+    others (a checkpoint on the CPU, other dtypes) by copy_."""
+    there = [(o, x.detach()) for o, x in items if x.device == arena.device and x.dtype in (f32, bf16) and x.is_contiguous()]
+    if there:
+        K.gather_many(arena, K.gather_table(arena, there))
+    for o, x in items:
+        if not (x.device == arena.device and x.dtype in (f32, bf16) and x.is_contiguous()):
+            arena[o:o + x.numel()].copy_(x.reshape(-1))
+
+
+def arena_load_state(rule: str, who: str, sd: dict, members, off: dict, m, v, expect: Optional[int]) -> float:
+    """Check a torch.optim-shaped state dict against the arena optimizer `who` (its name, for the messages) of rule `rule` and copy
+    its moments into the arenas m, v.  members: [[parameters of group 0], ...]; expect: how many state entries a non-empty state
+    must have (None: any number; parameters without an entry keep their moments).  Returns the step count the dict holds."""
+    order = [p for group in members for p in group]
+    pg = sd.get("param_groups") or []
+    want = "momentum" if rule == "sgd" else "betas"
+    if pg and any(want not in g for g in pg):
+        raise ValueError(f"optimizer state of another rule: {who} loads param groups that hold "
+                         f"{want!r}, these hold {sorted(k for k in pg[0] if k != 'params')}")
+    if pg and [len(g["params"]) for g in pg] != [len(group) for group in members]:
+        raise ValueError(f"optimizer state has param groups of {[len(g['params']) for g in pg]} parameters, those of {who} "
+                         f"have {[len(group) for group in members]}")
+    if expect is not None and len(sd["state"]) not in (0, expect):
+        raise ValueError(f"optimizer state has {len(sd['state'])} entries, the model has {expect} parameters")
+    t = float(sd.get("step", 0.0)) if rule == "sgd" else 0.0
+    into_m, into_v = [], []
+    for i, p in enumerate(order):
+        st = sd["state"].get(i)
+        if st is None:
+            continue
+        def sized(x):
+            if x.numel() != p.numel():
+                raise ValueError(f"optimizer state entry {i} holds {tuple(x.shape)} for a parameter of shape {tuple(p.shape)}")
+            return off[id(p)], x
+        if rule == "sgd":
+            if m is not None:
+                into_m.append(sized(st["momentum_buffer"]))
+            continue
+        if "exp_avg" not in st:
+            raise ValueError(f"optimizer state of another rule: entry {i} holds {sorted(st)}, not Adam's exp_avg / exp_avg_sq")
+        into_m.append(sized(st["exp_avg"]))
+        into_v.append(sized(st["exp_avg_sq"]))
+        t = float(st["step"])
+    if into_m:
+        _fill_arena(m, into_m)
+    if into_v:
+        _fill_arena(v, into_v)
+    return t
+
+
 _EARLY_ADAM = True      # (test hook, round 5) the RNA encoder's share of the optimizer step on its branch's stream, beside the WSI backward
 
 
@@ -676,65 +755,27 @@ class TrainEngine:
         return [(wd, [(n, p) for n, p in members if id(p) in off])
                 for wd, members in decay_groups(self.model, self.weight_decay or 0, self.filter_bias_and_bn)]
 
+    def _group_settings(self, wd) -> dict:
+        if self._rule != "sgd":
+            return {"lr": float(self.lr), "betas": tuple(self.betas), "eps": self.eps, "weight_decay": wd, "amsgrad": False}
+        return {"lr": float(self.lr), "momentum": self.momentum, "dampening": 0, "weight_decay": wd, "nesterov": self.nesterov}
+
     def state_dict(self) -> dict:
         """The state of the matching torch.optim optimizer built as timm builds it (what the reference checkpoints and
         `resume_checkpoint` reloads), on the CPU: param groups in decay_groups order, state indices running through them.
         Adam / AdamW: {step, exp_avg, exp_avg_sq} per parameter; SGD: {momentum_buffer}, no state without momentum.  SGD keeps no
         step: the engine's (the EMA decay and fp8 delayed scaling read it) travels as the extra top-level entry "step", which
         torch.optim.SGD.load_state_dict ignores."""
-        t = float(self._state[0].item())
         off = {id(p): o for p, o in zip(self.params, self.offsets)}
-        state, out_groups, i = {}, [], 0
-        for wd, members in self._groups():
-            first = i
-            for _, p in members:
-                o, n = off[id(p)], p.numel()
-                if self._rule != "sgd":
-                    state[i] = {"step": torch.tensor(t), "exp_avg": self.m[o:o + n].view(p.shape).cpu().clone(),
-                                "exp_avg_sq": self.v[o:o + n].view(p.shape).cpu().clone()}
-                elif self.m is not None and t > 0:          # torch creates the buffer at a parameter's first step
-                    state[i] = {"momentum_buffer": self.m[o:o + n].view(p.shape).cpu().clone()}
-                i += 1
-            if self._rule != "sgd":
-                group = {"lr": float(self.lr), "betas": tuple(self.betas), "eps": self.eps, "weight_decay": wd, "amsgrad": False}
-            else:
-                group = {"lr": float(self.lr), "momentum": self.momentum, "dampening": 0, "weight_decay": wd, "nesterov": self.nesterov}
-            group["params"] = list(range(first, i))
-            out_groups.append(group)
-        sd = {"state": state, "param_groups": out_groups}
-        if self._rule == "sgd":
-            sd["step"] = t
-        return sd
+        groups = [(self._group_settings(wd), [p for _, p in members]) for wd, members in self._groups()]
+        return arena_state_dict(self._rule, float(self._state[0].item()), groups, off, self.m, self.v)
 
     def load_state_dict(self, sd: dict) -> None:
-        groups = self._groups()
-        order = [p for _, members in groups for _, p in members]
         off = {id(p): o for p, o in zip(self.params, self.offsets)}
+        members = [[p for _, p in m] for _, m in self._groups()]
         pg = sd.get("param_groups") or []
-        want = "momentum" if self._rule == "sgd" else "betas"
-        if pg and any(want not in g for g in pg):
-            raise ValueError(f"optimizer state of another rule: TrainEngine(opt={self.opt!r}) loads param groups that hold "
-                             f"{want!r}, these hold {sorted(k for k in pg[0] if k != 'params')}")
-        if pg and [len(g["params"]) for g in pg] != [len(members) for _, members in groups]:
-            raise ValueError(f"optimizer state has param groups of {[len(g['params']) for g in pg]} parameters, this engine's "
-                             f"(opt={self.opt!r}, weight_decay={self.weight_decay}) have {[len(m) for _, m in groups]}")
-        if len(sd["state"]) not in (0, len(order)):
-            raise ValueError(f"optimizer state has {len(sd['state'])} entries, the model has {len(order)} parameters")
-        t = float(sd.get("step", 0.0)) if self._rule == "sgd" else 0.0
-        for i, p in enumerate(order):
-            st = sd["state"].get(i)
-            if st is None:
-                continue
-            o, n = off[id(p)], p.numel()
-            if self._rule == "sgd":
-                if self.m is not None:
-                    self.m[o:o + n].copy_(st["momentum_buffer"].reshape(-1))
-                continue
-            if "exp_avg" not in st:
-                raise ValueError(f"optimizer state of another rule: entry {i} holds {sorted(st)}, not Adam's exp_avg / exp_avg_sq")
-            self.m[o:o + n].copy_(st["exp_avg"].reshape(-1))
-            self.v[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
-            t = float(st["step"])
+        t = arena_load_state(self._rule, f"TrainEngine(opt={self.opt!r}, weight_decay={self.weight_decay})", sd, members, off,
+                             self.m, self.v, expect=sum(len(m) for m in members))
         if pg:
             self.lr = float(pg[0].get("lr", self.lr))
         b1, b2 = self.betas

@@ -1856,6 +1856,59 @@ def optim_step(p, g, m, v, shadow, opt_cfg, dev_state: torch.Tensor, grad_scale=
               _p(ema), None if ema is None else C.addressof(ema_cfg), stream=_stream())
 
 
+def optim_groups(p, g, m, v, shadow, opt_cfg, dev_state: torch.Tensor, group_map: torch.Tensor, group_wd: torch.Tensor,
+                 group_lr: torch.Tensor, grad_scale=1.0, clamp: Optional[tuple] = None, counter: Optional[torch.Tensor] = None,
+                 counter_add: int = 0, tick=True, hole: Optional[tuple] = None, ema: Optional[torch.Tensor] = None, ema_cfg=None) -> None:
+    """mh_optim_groups: optim_step with one learning rate per group — group_lr (f32, one per group, beside group_wd) replaces
+    dev_state[3] for the elements of each group — and with the group byte _lib.OPT_SKIP_GROUP for blocks that are left untouched
+    (torch.optim's parameter without a gradient).  group_map, group_wd and group_lr are required, at most 255 groups; both tables are
+    read from the device at run time, so a captured launch replays with what they hold then."""
+    _chk(p, g, m, v, shadow, dev_state, counter, ema, group_map, group_wd, group_lr)
+    n = p.numel()
+    sgd = opt_cfg.rule == _lib.OPT_SGD
+    need = [p, g] + ([] if sgd and opt_cfg.momentum == 0.0 else [m]) + ([] if sgd else [v])
+    if dev_state is None:
+        raise MirrorHipError("optim_groups: dev_state is the f32[6] device step state")
+    tail = _step_args("optim_groups", p, need, shadow, dev_state, clamp, counter, counter_add, tick, hole, ema, ema_cfg)
+    ng = 0 if group_wd is None else group_wd.numel()
+    if (group_map is None or group_map.dtype != torch.uint8 or not group_map.is_contiguous() or group_map.numel() < (n + 7) // 8
+            or not 1 <= ng <= _lib.OPT_SKIP_GROUP or group_lr is None
+            or any(t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != ng for t in (group_wd, group_lr))):
+        raise MirrorHipError("optim_groups: group_map is uint8 with one entry per 8 elements, group_wd and group_lr f32 with the "
+                             "same 1..255 entries")
+    _lib.call("mh_optim_groups", _p(p), _p(g), _p(m), _p(v), _p(shadow), n, C.addressof(opt_cfg), _p(group_map), _p(group_wd),
+              _p(group_lr), ng, grad_scale, _p(dev_state), *tail, _p(ema), None if ema is None else C.addressof(ema_cfg),
+              stream=_stream())
+
+
+GATHER_ROW = 1 << 15        # elements per mh_gather_many row: one workgroup copies a row, long tensors are split (a multiple of 8)
+
+
+def gather_table(arena: torch.Tensor, items) -> torch.Tensor:
+    """The device table of gather_many for `items` = [(arena offset, source tensor), ...]: rows {offset, address, n, dtype} of at
+    most GATHER_ROW elements.  Sources are contiguous f32 or bf16 tensors on the arena's device; every range is checked against the
+    arena here, on the host (the caller keeps the ranges disjoint and the sources alive until the launch has run)."""
+    rows = []
+    for off, t in items:
+        _chk(t)
+        if t.device != arena.device or not t.is_contiguous() or off < 0 or off + t.numel() > arena.numel():
+            raise MirrorHipError(f"gather_table: a contiguous source on the arena's device inside its {arena.numel()} elements, got "
+                                 f"{tuple(t.shape)} at {off}")
+        code, size, ptr = dt(t), t.element_size(), t.data_ptr()
+        for s in range(0, t.numel(), GATHER_ROW):
+            rows += [off + s, ptr + size * s, min(GATHER_ROW, t.numel() - s), code]
+    return torch.tensor(rows, dtype=torch.int64).view(-1, 4).to(arena.device)
+
+
+def gather_many(arena: torch.Tensor, table: torch.Tensor) -> None:
+    """arena[o_i : o_i + n_i] = src_i (f32, or bf16 widened) for the rows of `table` (gather_table), in one launch."""
+    _chk(arena, table)
+    if not (arena.dtype == torch.float32 and arena.is_contiguous() and table.dtype == torch.int64 and table.is_contiguous()
+            and table.dim() == 2 and table.shape[1] == 4 and table.device == arena.device):
+        raise MirrorHipError("gather_many: f32 contiguous arena, int64 [nrows, 4] table on its device")
+    _lib.call("mh_gather_many", _p(arena), _p(table), int(table.shape[0]), stream=_stream())
+
+
 def ema_update_many(ema: torch.Tensor, table: torch.Tensor, nseg: int, weight: float = 1.0, dev_state: Optional[torch.Tensor] = None,
                     ema_cfg=None) -> None:
     """ema[o_i : o_i + n_i] = lerp(ema[o_i : o_i + n_i], src_i, w) for the rows {o_i, src_i address, n_i} of `table` (int64 [nseg, 3]
