@@ -1482,11 +1482,11 @@ class GeluFn(Function):
 
 gelu = GeluFn.apply
 
-_dropout_state = {"seed": 0x5EED, "offset": 0, "base": None}
+_dropout_state = {"seed": 0x5EED, "offset": 0, "base": None, "noise": 0}
 
 
 def manual_seed(seed: int) -> None:
-    _dropout_state["seed"], _dropout_state["offset"] = int(seed) & ((1 << 63) - 1), 0
+    _dropout_state["seed"], _dropout_state["offset"], _dropout_state["noise"] = int(seed) & ((1 << 63) - 1), 0, 0
     if _dropout_state["base"] is not None:
         _dropout_state["base"].zero_()
 
@@ -1499,19 +1499,24 @@ def dropout_step_begin(device) -> None:
     _dropout_state["offset"] = 0
 
 
+def _step_used() -> int:
+    """What a step consumed of the streams, as a whole number of lite blocks (8 elements): the next step's first lite site must not
+    share the last block of this one (the kernels mask the base with ~7)."""
+    used, _dropout_state["offset"] = (_dropout_state["offset"] + 7) // 8 * 8, 0
+    return used
+
+
 def dropout_step_end() -> None:
     """Advance the device base by what this step consumed (a device-side add: captured with the step)."""
-    base = _dropout_state["base"]
-    if base is not None and _dropout_state["offset"]:
-        base.add_(_dropout_state["offset"])
-    _dropout_state["offset"] = 0
+    base, used = _dropout_state["base"], _step_used()
+    if base is not None and used:
+        base.add_(used)
 
 
 def dropout_step_take():
     """dropout_step_end for a caller that advances the device base inside a launch of its own (mh_adam's `counter`): returns
     (base tensor or None, offsets this step consumed) and resets the host offset."""
-    base, used = _dropout_state["base"], _dropout_state["offset"]
-    _dropout_state["offset"] = 0
+    base, used = _dropout_state["base"], _step_used()
     return (base, used) if (base is not None and used) else (None, 0)
 
 
@@ -1525,19 +1530,31 @@ _NOISE_OFFSET = 1 << 44      # the noise draws' own range of the Philox counter 
 def noise_draws(B: int, N: int, D: int, L: int, device):
     """(rand [B, N], rand [B, D], randn [B, L], randn [B, L]) — the step's four draws (models/mirror.py:630, :516, :832-833) as ONE launch on
     the dropout stream's generator (mh_noise_draws; seed and per-step device base of manual_seed / dropout_step_begin): under a captured
-    step torch's generator costs four launches plus two state fills in front of every replay.  The draws live at a FIXED offset of their
-    own and take nothing from the running dropout offset — the RNA branch's HIP-graph replay has its dropout offsets baked in from 0
-    (graphed.py) and the draws are issued in front of it; what makes them differ from step to step is the device base, so the caller
-    advances the running offset by noise_draws_advance() at the END of its forward (a step without a single dropout site would otherwise
-    repeat its masks)."""
+    step torch's generator costs four launches plus two state fills in front of every replay.  The draws live in a range of their own,
+    at _NOISE_OFFSET + the running host offset (+ the device base), and take nothing from the running dropout offset while the forward
+    runs — the RNA branch's HIP-graph replay has its dropout offsets baked in from 0 (graphed.py) and the draws are issued in front of
+    it.  Inside an engine step the host offset is 0 here (a constant a captured step can bake in) and the device base moves the range;
+    on a bare forward nothing advances a base and the running host offset does.  Either way the caller ends its forward with
+    noise_draws_advance(), which leaves the running offset at or behind the end of the range drawn here: the ranges of consecutive
+    forwards are disjoint, with or without a dropout site in between."""
     n0, n1 = (B * N + 3) // 4 * 4, (B * D + 3) // 4 * 4
-    buf = K.noise_draws(n0 + n1, 2 * B * L, _dropout_state["seed"], _NOISE_OFFSET, _dropout_state["base"], device)
+    start = (_dropout_state["offset"] + 3) // 4 * 4
+    offset = _NOISE_OFFSET + start
+    _dropout_state["noise"] = start + n0 + n1 + 2 * B * L       # where this forward's noise range ends, as a running offset
+    if _dropout_tap is not None:
+        _dropout_tap.append(((n0 + n1, 2 * B * L), None, int(_dropout_state["seed"]), offset, False))
+    buf = K.noise_draws(n0 + n1, 2 * B * L, _dropout_state["seed"], offset, _dropout_state["base"], device)
     e = n0 + n1
     return (buf[:B * N].view(B, N), buf[n0:n0 + B * D].view(B, D), buf[e:e + B * L].view(B, L), buf[e + B * L:e + 2 * B * L].view(B, L))
 
 
 def noise_draws_advance() -> None:
-    _dropout_state["offset"] = (_dropout_state["offset"] + 7) // 8 * 8 + 8
+    """End of a forward that called noise_draws: the running offset moves to the block behind the forward's last lite block, and at
+    least to the end of the noise range drawn (rounded up to 8) — over the forward it has then moved by no less than the number of
+    noise elements, so that the next forward's noise range, and through the step's consumption the next step's device base, lies
+    behind this one's.  A forward whose dropout sites consumed more than it drew noise ends where it always did."""
+    end, _dropout_state["noise"] = _dropout_state["noise"], 0
+    _dropout_state["offset"] = max((_dropout_state["offset"] + 7) // 8 * 8 + 8, (end + 7) // 8 * 8)
 
 
 def _lite_offset() -> int:
@@ -1547,7 +1564,8 @@ def _lite_offset() -> int:
 
 # Test hook (train-mode parity): while this is a list, every dropout site of a forward pass appends
 # (shape, p, seed, host offset, lite) in launch order; dropout_tap_masks() then regenerates the multipliers the kernels applied
-# (0 or 1 / (1 - p)) so that an oracle run can be handed the very masks of a train-mode step.
+# (0 or 1 / (1 - p)) so that an oracle run can be handed the very masks of a train-mode step.  The noise launch of a forward
+# (noise_draws) is recorded as ((n_uniform, n_normal), None, seed, effective host offset, False): p is None.
 _dropout_tap: Optional[list] = None
 
 
@@ -1557,10 +1575,13 @@ def _tap(shape, p, seed, offset, lite) -> None:
 
 
 def dropout_tap_masks(records, device, base: Optional[torch.Tensor] = None):
-    """The multiplier tensors (f32, 0 or 1 / (1 - p)) of the recorded dropout sites, regenerated by the dropout kernels
-    themselves from (seed, offset [+ the device base the step ran under])."""
+    """The multiplier tensors (f32, 0 or 1 / (1 - p)) of the recorded dropout sites (for a noise record: the noise buffer), regenerated
+    by the kernels themselves from (seed, offset [+ the device base the step ran under])."""
     out = []
     for shape, p, seed, offset, lite in records:
+        if p is None:       # the noise launch: the buffer itself
+            out.append(K.noise_draws(shape[0], shape[1], seed, offset, base, device))
+            continue
         ones = torch.ones(shape, device=device, dtype=f32)
         out.append(K.dropout_lite(ones, p, seed, offset, base) if lite else K.dropout(ones, p, seed, offset, dev_base=base))
     return out

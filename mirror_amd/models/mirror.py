@@ -641,7 +641,9 @@ class MIRROR(nn.Module):
             t.record_stream(main)       # allocated in a helper stream's pool, consumed on the main stream
         rna_retention_target = rna_emb
         if own_draws:
-            Fn.noise_draws_advance()      # the next step's draws must differ even if this one had no dropout site (Fn.noise_draws)
+            # the next forward's draws — bare, or the next engine step's through the device base — lie behind this one's: the running
+            # offset moves past the noise elements drawn, whether or not a dropout site ran in between (Fn.noise_draws)
+            Fn.noise_draws_advance()
         return (wsi_alignment_emb, wsi_retention_emb, wsi_retention_target, wsi_mask, wsi_score, wsi_mu, wsi_logstd,
                 rna_alignment_emb, rna_retention_emb, rna_retention_target, rna_mask, rna_score, rna_mu, rna_logstd,
                 logit_scale)
