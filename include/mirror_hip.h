@@ -426,6 +426,20 @@ int mh_nys_attn1_bwd(const void* qkv, const void* lm, const void* w2, const void
 int mh_nys_attn3_bwd(const void* qkv, const void* lm, const float* av, const void* dav, const float* lse3, float* delta3,
                      void* dqkv, float* dlm, const float* mrow, const float* mlm, int B, int h, int n_p, int m, int dh,
                      float scale, int64_t lm_ld, mh_stream s);
+/* One row of the Nystrom attention matrix: row[b, h, :] = (attn1 @ pinv(attn2) @ attn3)[cls_row, :], f32 [B, h, n_p] — what [3P]
+ * NystromAttention.forward(..., return_attn=True) returns, for the one query position whose map is drawn (TransMIL's CLS token);
+ * the n_p x n_p matrix is never formed:  p1 = softmax_j(scale q[cls_row] . k_l[j]),  u = p1 Z,
+ * row[n] = sum_j u[j] exp(scale q_l[j] . k[n] - lse3[j]).
+ *   qkv [B,n_p,3D] and lm [B,m,2D] (row stride lm_ld as above) of element type dt (MH_BF16 or MH_F32), D = h dh;
+ *   z = pinv(attn2) per (b, h): z_colmajor = 1: bf16, column-major (mh_pinv_chain_fwd's zfT); 0: f32, row-major [B,h,m,m];
+ *   lse3 [B,h,m] f32 = row logsumexp of scale q_l k^T (mh_nys_attn3_fwd's), or NULL: the kernel takes it in a first pass over k;
+ *   mrow / mlm as for mh_nys_attn*: an invalid landmark has p1 = 0 and a uniform attn3 row (the package's fully masked row), a valid
+ *   landmark's row is zero on invalid keys, and row[n] of an invalid key n is written as exactly 0.
+ * Supported: (dh, m) = (64, 256) and (96, 384), n_p a multiple of m, 0 <= cls_row < n_p; anything else returns MH_EINVAL.
+ * Every row[b, h, n] has one writer (no atomics).  Entries may be slightly negative and rows need not sum to 1 (z is a pseudo-inverse). */
+int mh_nys_cls_attn(const void* qkv, const void* lm, const void* z, const float* lse3, float* row, const float* mrow, const float* mlm,
+                    int B, int h, int n_p, int m, int dh, int cls_row, float scale, int64_t lm_ld, int z_colmajor, int dt,
+                    mh_stream s);
 /* out[r, 0:cols] = bf16(a[r] + b[r]) (f32 [rows, cols], b may be NULL) at row stride out_ld, out[r, cols:cols + zero_cols] = 0: the
  * landmark gradient (q_l | k_l halves from the attention kernels + sim2's products) written as rows [dq_l | dk_l | 0] of to_qkv's
  * output gradient, where its data / weight gradient products pick it up together with the sequence rows. */

@@ -145,6 +145,7 @@ _SIGS = {
     "mh_nys_attn3_fwd": [P, P, P, P, P, L, P, P, I, I, I, I, I, F, L, P, P],
     "mh_nys_attn1_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, L],
     "mh_nys_attn3_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, L],
+    "mh_nys_cls_attn": [P, P, P, P, P, P, P, I, I, I, I, I, I, F, L, I, I],
     "mh_seq_finish": [P, P, I, I, I, I, I],
     "mh_seq_finish_bwd": [P, P, I, I, I, I, I],
     "mh_ppeg_merge": [P, P, P, P, P, P, P, P, I],

@@ -830,11 +830,12 @@ class NystromLink(_Link):
     v_cols: to_qkv's pending v-column launch (linear(defer_from=) / NormQkvLmFn), run by NystromCoreFn.forward under the pinv chain;
     core: NystromCoreFn took the link (its backward runs when its output needs a gradient); wgrad: to_out's weight-gradient launch
     (ToOutDropAddFn.backward), run by NystromCoreFn.backward beside the chain; lm_merge: (de, the landmark rows' merge into de) for
-    NormQkvLmFn.backward."""
-    __slots__ = ("v_cols", "core", "wgrad", "lm_merge")
+    NormQkvLmFn.backward; capture: None, or a dict that NystromCoreFn.forward fills with the operands of its core (qkv, lm, z, z_colmajor,
+    lse3, kmask, heads, scale) for the attention map (K.nys_cls_attn) — inference only, see TransLayer.forward(capture=)."""
+    __slots__ = ("v_cols", "core", "wgrad", "lm_merge", "capture")
 
     def __init__(self):
-        self.v_cols = self.wgrad = self.lm_merge = None
+        self.v_cols = self.wgrad = self.lm_merge = self.capture = None
         self.core = False
 
     def run(self, name: str) -> None:
@@ -2074,6 +2075,11 @@ class NystromCoreFn(Function):
             K.gemm(a1, w2, out=_heads(out, 0, 1, h), mma=mma)
             K.resconv(qkv[..., 2 * D:], res_w.detach().contiguous(), out, h, transpose=False, accumulate=True)
         stats = (lse1, lse3) if fused else (a1, a3)
+        if link is not None and link.capture is not None:
+            # the operands of one row of attn1 @ pinv @ attn3 (K.nys_cls_attn): the pseudo-inverse as the chain left it (column-major
+            # bf16) or as f32 row-major; lse3 only on the fused path (the kernel takes it itself otherwise).  No launch unless asked.
+            link.capture.update(qkv=qkv, lm=lm, z=zfT if chain else (zf if zf.dtype == f32 else K.cast(zf, f32)), z_colmajor=bool(chain),
+                                lse3=lse3 if fused else None, kmask=kmask, heads=h, scale=scale)
         ctx.has_o1 = o1 is not None
         ctx.save_for_backward(qkv, res_w, lm, stats[0], a2, stats[1], av, w2, st, zfT if chain else zf,
                               *([o1] if o1 is not None else []), *[t for it in saved for t in it])

@@ -1167,6 +1167,49 @@ def nys_attn3_fwd(qkv, lm, heads: int, scale: float, kmask=None, rc=None):
     return av, lse3
 
 
+NYS_CLS_GEOMETRIES = ((64, 256), (96, 384))      # (dh, m) pairs csrc/nystrom_cls.hip is built for
+
+
+def nys_cls_attn(qkv, lm, z, heads: int, scale: float, cls_row: int, lse3=None, mrow=None, mlm=None, z_colmajor: bool = False):
+    """row [B, h, n_p] f32 = (attn1 @ pinv(attn2) @ attn3)[cls_row, :] of [3P] NystromAttention (its return_attn=True), without
+    the n_p x n_p matrix (csrc/nystrom_cls.hip).  qkv [B, n_p, 3D] and lm [B, m, 2D] bf16 or f32 (same dtype; lm may be rows of a
+    wider buffer, see _lm_ld); z [B, h, m, m] = pinv(attn2): f32 row-major, or with z_colmajor the pinv chain's bf16 zfT;
+    lse3 [B, h, m] f32 from nys_attn3_fwd, or None (the kernel takes it in a pass of its own); mrow [B, n_p] / mlm [B, m]: the
+    key-padding plan (both or neither).  Entries of an invalid key are exactly 0."""
+    if qkv.dim() != 3 or lm.dim() != 3 or qkv.shape[2] % (3 * heads) or qkv.dtype != lm.dtype:
+        raise MirrorHipError(f"nys_cls_attn: qkv [B, n_p, 3D] and lm [B, m, 2D] of one dtype, D a multiple of heads={heads}; got "
+                             f"{tuple(qkv.shape)} {qkv.dtype}, {tuple(lm.shape)} {lm.dtype}")
+    B, n_p, D3 = qkv.shape
+    D, m = D3 // 3, lm.shape[1]
+    dh = D // heads
+    if (dh, m) not in NYS_CLS_GEOMETRIES:
+        raise MirrorHipError(f"nys_cls_attn: built for (dh, m) in {NYS_CLS_GEOMETRIES}, got ({dh}, {m})")
+    if tuple(lm.shape) != (B, m, 2 * D) or n_p < m or n_p % m:
+        raise MirrorHipError(f"nys_cls_attn: lm must be [{B}, m, {2 * D}] and n_p={n_p} a multiple of m={m}; lm is {tuple(lm.shape)}")
+    if not 0 <= int(cls_row) < n_p:
+        raise MirrorHipError(f"nys_cls_attn: cls_row={cls_row} outside [0, {n_p})")
+    if (mrow is None) != (mlm is None):
+        raise MirrorHipError("nys_cls_attn: mrow and mlm go together (both or neither)")
+    _contig(qkv, "nys_cls_attn: qkv")
+    if not lm.is_contiguous() and _lm_ld(lm) == 0:
+        raise MirrorHipError(f"nys_cls_attn: lm rows must be unit-stride and evenly spaced, got strides {lm.stride()}")
+    zdt = torch.bfloat16 if z_colmajor else torch.float32
+    if tuple(z.shape) != (B, heads, m, m) or z.dtype != zdt or not z.is_contiguous():
+        raise MirrorHipError(f"nys_cls_attn: z must be contiguous {zdt} [{B}, {heads}, {m}, {m}] (z_colmajor={z_colmajor}), got "
+                             f"{z.dtype} {tuple(z.shape)} contiguous={z.is_contiguous()}")
+    if lse3 is not None and not (tuple(lse3.shape) == (B, heads, m) and lse3.dtype == torch.float32 and lse3.is_contiguous()):
+        raise MirrorHipError(f"nys_cls_attn: lse3 must be contiguous f32 [{B}, {heads}, {m}]")
+    if mrow is not None and not (tuple(mrow.shape) == (B, n_p) and tuple(mlm.shape) == (B, m) and mrow.dtype == mlm.dtype == torch.float32
+                                 and mrow.is_contiguous() and mlm.is_contiguous()):
+        raise MirrorHipError(f"nys_cls_attn: mrow / mlm must be contiguous f32 [{B}, {n_p}] / [{B}, {m}]")
+    _chk(qkv, lm, z, lse3, mrow, mlm)        # (behind the argument checks: those read no data and give their message on any device)
+    row = torch.empty((B, heads, n_p), device=qkv.device, dtype=torch.float32)
+    _nys_launch("nys_cls_kernel", (1 if lse3 is not None else 2) * 2.0 * n_p * m * dh * B * heads,
+                lambda: _lib.call("mh_nys_cls_attn", _p(qkv), _p(lm), _p(z), _p(lse3), _p(row), _p(mrow), _p(mlm), B, heads, n_p, m, dh,
+                                  int(cls_row), float(scale), _lm_ld(lm), int(z_colmajor), dt(qkv), stream=_stream()))
+    return row
+
+
 def nys_attn1_bwd(qkv, lm, w2, dout, lse1, o1, delta1, dqkv, dw2, dlm, heads: int, scale: float, kmask=None) -> None:
     """attn1's backward (mh_nys_attn1_bwd), ONE kernel that walks the rows once (5 products per tile): ADDS into dw2 and into the k_l half
     of dlm (both f32, zeroed by the caller), WRITES delta1 [B, h, n_p] from the forward's saved rows o1 and the q block of dqkv."""

@@ -184,16 +184,24 @@ class TransLayer(nn.Module):
         self.attn = NystromAttention(dim=dim, dim_head=dim // 8, heads=8, num_landmarks=dim // 2,
                                      pinv_iterations=6, residual=True, dropout=0.1)
 
-    def forward(self, x, prec: Precision, mask=None):
+    def forward(self, x, prec: Precision, mask=None, capture: Optional[list] = None):
         """mask: optional [B, n] bool key-padding mask (True = real token) or an Fn.KeyMask, the `mask` argument of [3P]
         NystromAttention.forward that the reference never passes (models/mirror.py:312); BASELINE config 4 uses it for
-        variable-length slides.  It is front-padded with False like the sequence."""
+        variable-length slides.  It is front-padded with False like the sequence.
+        capture: a list that receives one dict with the operands of this layer's attention core (qkv, lm, z, z_colmajor, lse3, kmask,
+        heads, scale, and pad / n of the front-padded sequence) — what K.nys_cls_attn turns into a row of [3P] `return_attn=True`.
+        Inference only (eval mode, no grad); with capture=None the forward launches exactly what it always did."""
         a = self.attn
+        if capture is not None and (self.training or torch.is_grad_enabled()):
+            raise RuntimeError("TransLayer.forward(capture=): attention maps are read in eval mode under torch.no_grad()")
         n, m = x.shape[1], a.num_landmarks
         pad = (m - n % m) % m
         l = math.ceil(n / m)  # noqa: E741
         lm = kmask = mrow = None
         link, res = Fn.NystromLink(), Fn.ResidualLink()     # hand-overs between this layer's nodes; x feeds exactly self.norm and the add
+        if capture is not None:
+            link.capture = {"pad": pad, "n": n}
+            capture.append(link.capture)
         if mask is not None:
             km = mask if isinstance(mask, Fn.KeyMask) else Fn.KeyMask(mask.to(x.device))
             if tuple(km.shape) != tuple(x.shape[:2]):
@@ -254,9 +262,10 @@ class FeatureTransMIL(nn.Module):
         self.norm = nn.LayerNorm(embed_dim)
         self.precision: Optional[str] = None
 
-    def _encode(self, h, keep_rows: Optional[int], mask: Optional[torch.Tensor] = None):
+    def _encode(self, h, keep_rows: Optional[int], mask: Optional[torch.Tensor] = None, capture: Optional[list] = None):
         """mask: optional [B, N] bool, True = real patch (BASELINE config 4; the reference has no such argument).  The
-        sequence [cls, x_0..x_{N-1}, x_0..x_{add-1}] carries [True, mask, mask[:, :add]]."""
+        sequence [cls, x_0..x_{N-1}, x_0..x_{add-1}] carries [True, mask, mask[:, :add]].
+        capture: see TransLayer.forward (one dict per layer, layer1 first)."""
         prec = resolve_precision(self.precision)
         if not h.is_cuda:
             raise MirrorHipError("mirror_amd models run on MI355X only (no CPU fallback): move the inputs to the GPU")
@@ -267,9 +276,9 @@ class FeatureTransMIL(nn.Module):
         smask = None
         if mask is not None:
             smask = Fn.KeyMask(mask.to(h.device, torch.bool), lead=1, wrap=add)
-        seq = self.layer1(seq, prec, smask)
+        seq = self.layer1(seq, prec, smask, capture)
         seq = self.pos_layer(seq, side, side)
-        seq = self.layer2(seq, prec, smask)
+        seq = self.layer2(seq, prec, smask, capture)
         rows = seq.shape[1] - add if keep_rows is None else keep_rows
         # the pre-training encoder output also feeds the retention decoder's bf16 projection: the norm writes that copy itself
         return Fn.layer_norm(seq, self.norm.weight, self.norm.bias, self.norm.eps, rows=rows, out_dtype=f32,
@@ -277,6 +286,33 @@ class FeatureTransMIL(nn.Module):
 
     def forward(self, h):
         return self._encode(h, keep_rows=1)[:, 0]
+
+    def forward_with_attention(self, h, mask: Optional[torch.Tensor] = None):
+        """(emb, attn): emb is forward(h) bit for bit; attn [B, 2, heads, N] f32 is the CLS row of [3P] NystromAttention's
+        `attn1 @ pinv(attn2) @ attn3` (its return_attn=True) in layer1 and layer2, restricted to the N patches of h in h's order —
+        the slide attention map (see mirror_amd.explain.slide_attention).  The layers see [front pad | cls | x_0..x_{N-1} |
+        x_0..x_{add-1}]: the weight on a wrapped-around duplicate is ADDED to the patch it duplicates, the weight on the pad
+        positions and on CLS itself is dropped.  So a row does not sum to 1, and because pinv(attn2) is an iterated pseudo-inverse
+        entries may be slightly negative, exactly as in the package's `attn`.  mask: optional [B, N] bool (True = real patch);
+        masked patches get exactly 0.  Eval mode and torch.no_grad() only: no gradient flows through the map."""
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("forward_with_attention: call it in eval mode under torch.no_grad() (the map is an inference output)")
+        ops: list = []
+        emb = self._encode(h, keep_rows=1, mask=mask, capture=ops)[:, 0]
+        n_tok = h.shape[1]
+        maps = []
+        for o in ops:
+            km = o["kmask"]
+            row = Fn.K.nys_cls_attn(o["qkv"], o["lm"], o["z"], o["heads"], o["scale"], o["pad"], lse3=o["lse3"],
+                                    mrow=None if km is None else km[0], mlm=None if km is None else km[1],
+                                    z_colmajor=o["z_colmajor"])                     # [B, heads, n_p], cls at index pad
+            first = o["pad"] + 1
+            m = row[:, :, first:first + n_tok].clone()
+            add = o["n"] - 1 - n_tok
+            if add:
+                m[:, :, :add] += row[:, :, first + n_tok:first + n_tok + add]
+            maps.append(m)
+        return emb, torch.stack(maps, dim=1)
 
 
 # ===========================================
@@ -686,13 +722,26 @@ class MIRRORClassifier(nn.Module):
     def forward(self, wsi_emb: torch.Tensor, rna_emb: Optional[torch.Tensor] = None) -> torch.Tensor:
         prec = resolve_precision(self.precision)
         self.wsi_encoder.precision = self.rna_encoder.precision = self.precision
-        w = self.wsi_encoder(wsi_emb)                                     # [B, D] f32
+        return self._head(self.wsi_encoder(wsi_emb), rna_emb, prec)       # w: [B, D] f32
+
+    def _head(self, w: torch.Tensor, rna_emb: Optional[torch.Tensor], prec: Precision) -> torch.Tensor:
+        """RNA branch, fusion and the linear head behind the WSI embedding w (shared by forward and forward_with_attention)."""
         if rna_emb is None:
             fused = w
         else:
             r = self.rna_encoder(rna_emb)
             fused = Fn.add(w, r, f32) if self.fusion == "add" else torch.cat((w, r), dim=1)
         return Fn.linear(fused.contiguous(), self.head.weight, self.head.bias, prec=prec, out_dtype=f32)
+
+    def forward_with_attention(self, wsi_emb: torch.Tensor, rna_emb: Optional[torch.Tensor] = None):
+        """(logits, attn): logits are forward(...) bit for bit, attn [B, 2, heads, N] is the WSI encoder's slide attention map
+        (FeatureTransMIL.forward_with_attention has the contract).  Eval mode and torch.no_grad() only."""
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("forward_with_attention: call it in eval mode under torch.no_grad() (the map is an inference output)")
+        prec = resolve_precision(self.precision)
+        self.wsi_encoder.precision = self.rna_encoder.precision = self.precision
+        w, attn = self.wsi_encoder.forward_with_attention(wsi_emb)
+        return self._head(w, rna_emb, prec), attn
 
 
 def mirror_classifier(**kwargs) -> MIRRORClassifier:
