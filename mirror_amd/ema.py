@@ -9,9 +9,9 @@
 The EMA weights live in one flat, 16-B-aligned f32 arena; the parameters of `.module` are views of it.  Two update paths:
   * standalone (`update(model, step)`, e.g. downstream fine-tuning under a plain torch.optim optimizer): ONE mh_ema_update_many
     launch over a table of (EMA offset, source address, n) rows;
-  * attached to a TrainEngine (`TrainEngine(..., model_ema=ema)`): the arena takes the master arena's layout and mh_adam_ema lerps
-    every updated parameter inside the Adam pass (+8 B per parameter, no launch of its own, decay from the device step: the update
-    is part of the captured whole-step graph).  `update(model, step=num_updates)` is then a checked no-op.
+  * attached to a TrainEngine (`TrainEngine(..., model_ema=ema)`): the arena takes the master arena's layout and mh_optim_step lerps
+    every updated parameter inside the optimizer pass (+8 B per parameter, no launch of its own, decay from the device step: the
+    update is part of the captured whole-step graph).  `update(model, step=num_updates)` is then a checked no-op.
 
 A kernel write does not bump torch's version counter: the bf16 weight copies of `.module` (bf16 policies) are rebuilt by a forward
 pre-hook whenever the arena was updated or written through torch since the last forward — one refresh per validation, not per step.
@@ -28,9 +28,9 @@ from torch import nn
 from . import functional as Fn
 from . import kernels as K
 from ._lib import EmaCfg, MirrorHipError
+from .arena import ALIGN, lay_out
 
 f32, bf16 = torch.float32, torch.bfloat16
-_ALIGN = 8          # elements (32 B): the engine's parameter alignment; keeps the bf16 copies 16-B aligned for the transposes
 _ROW = 16384        # elements per mh_ema_update_many row (a multiple of 4: the rows of one tensor keep its 16-B alignment)
 
 
@@ -39,10 +39,6 @@ def _unwrap(model: nn.Module) -> nn.Module:
     while isinstance(model, (DistributedDataParallel, DataParallel)):
         model = model.module
     return model
-
-
-def _pad(n: int) -> int:
-    return (n + _ALIGN - 1) // _ALIGN * _ALIGN
 
 
 def _rows(off: int, t: torch.Tensor) -> List[int]:
@@ -95,12 +91,10 @@ class ModelEmaV3(nn.Module):
             if v.is_floating_point() and v.dtype != f32:
                 raise NotImplementedError(f"ModelEmaV3: {k} is {v.dtype}; the EMA kernels take f32 state only")
         # one flat arena: every f32 state_dict entry (parameters and floating buffers), state_dict order, 8-element aligned
-        lay, total = [], 0
-        for k, v in src.items():
-            if v.is_floating_point():
-                lay.append((k, total))
-                total += _pad(v.numel())
-        self.arena = torch.zeros(max(total, _ALIGN), device=self.device, dtype=f32)
+        keys = [k for k, v in src.items() if v.is_floating_point()]
+        offs, total = lay_out([src[k].numel() for k in keys])
+        lay = list(zip(keys, offs))
+        self.arena = torch.zeros(max(total, ALIGN), device=self.device, dtype=f32)
         off = dict(lay)
         # .module: the model's structure with its tensors replaced WITHOUT copying the storages they view (a parameter of an
         # engine-managed model is a view of the whole master arena, its .grad one of the grad arena) nor the captured graphs and
@@ -133,7 +127,7 @@ class ModelEmaV3(nn.Module):
         self.module.eval()
         self._names = list(self.module.state_dict(keep_vars=True).keys())
         self._param_names = pnames
-        self._lay = [(k, o) for k, o in lay]
+        self._lay = lay
         self._engine = None
         self._table_key = self._table = None
         self._nrows = 0
@@ -203,25 +197,20 @@ class ModelEmaV3(nn.Module):
         self._touch()
 
     # ------------------------------------------------------------------ TrainEngine attachment
-    def _attach(self, engine) -> Tuple[torch.Tensor, Optional[torch.Tensor], int]:
-        """Re-lay the arena out like engine.master (same offsets; parameters outside it, and f32 buffers, behind it) and return
-        (arena, table of the entries behind the master range or None, its row count).  Called once, by TrainEngine."""
+    def _attach(self, pa, model: nn.Module, engine) -> Tuple[torch.Tensor, Optional[torch.Tensor], int]:
+        """Re-lay the arena out like the master of `pa`, the ParamArena of `model` (same offsets; parameters outside it, and f32 buffers,
+        behind it) and return (arena, table of the entries behind the master range or None, its row count).  Called once, by `engine`."""
         if self._engine is not None:
             raise ValueError("this ModelEmaV3 is already attached to a TrainEngine")
-        model = engine.model
         src = dict(model.state_dict(keep_vars=True))
         if list(src.keys()) != self._names:
             raise ValueError("ModelEmaV3 attached to an engine whose model has other state entries than the EMA's")
         name_of = {id(v): k for k, v in src.items()}
-        off = {name_of[id(p)]: o for p, o in zip(engine.params, engine.offsets)}
-        total = engine.numel
-        tail = []
-        for k, _ in self._lay:
-            if k not in off:
-                off[k] = total
-                tail.append(k)
-                total += _pad(src[k].numel())
-        arena = torch.zeros(max(total, _ALIGN), device=engine.device, dtype=f32)
+        off = {name_of[id(p)]: o for p, o in zip(pa.params, pa.offsets)}
+        tail = [k for k, _ in self._lay if k not in off]
+        offs, total = lay_out([pa.numel] + [src[k].numel() for k in tail])      # (pa.numel is a multiple of ALIGN)
+        off.update(zip(tail, offs[1:]))
+        arena = torch.zeros(max(total, ALIGN), device=pa.device, dtype=f32)
         ema_sd = self.module.state_dict(keep_vars=True)
         with torch.no_grad():
             for k, _ in self._lay:
@@ -238,13 +227,13 @@ class ModelEmaV3(nn.Module):
             if self.exclude_buffers and k not in self._param_names:
                 cp.append((ema_sd[k], s))
                 continue
-            if not s.is_contiguous() or s.device != engine.device:
-                raise MirrorHipError(f"ModelEmaV3: {k} must be a contiguous f32 tensor on {engine.device}")
+            if not s.is_contiguous() or s.device != pa.device:
+                raise MirrorHipError(f"ModelEmaV3: {k} must be a contiguous f32 tensor on {pa.device}")
             rows += _rows(off[k], s)
         self._engine_copies = cp + [(ema_sd[k], src[k].detach()) for k in self._names if not ema_sd[k].is_floating_point()]
         self._engine = engine
         self._touch()
-        table = torch.tensor(rows, dtype=torch.int64).to(engine.device) if rows else None
+        table = torch.tensor(rows, dtype=torch.int64).to(pa.device) if rows else None
         return arena, table, len(rows) // 3
 
     def _cfg(self) -> EmaCfg:

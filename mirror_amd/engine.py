@@ -1,11 +1,11 @@
 """Training step engine for the MIRROR hot path: the per-step semantics of `train_one_epoch`
 (train_mirror.py:1126-1284) on MI355X, one process per GPU.
 
-  * flat arenas: f32 master params, f32 grads, Adam m/v and a bf16 shadow live in five contiguous HBM
-    buffers; module parameters are views into them.  Adam (+ the bf16 shadow refresh) is ONE kernel over
-    the arena, zero-grad is one memset, and gradient all-reduce works on arena slices (no flatten copies).
+  * flat arenas (arena.ParamArena): f32 master params, f32 grads, the moments and a bf16 shadow live in five contiguous HBM
+    buffers; module parameters are views into them.  The update (+ the bf16 shadow refresh) is ONE kernel over
+    the arena (mh_optim_step), zero-grad is one memset, and gradient all-reduce works on arena slices (no flatten copies).
   * data parallel = DDP semantics (gradient AVG across ranks, train_mirror.py:811-813): arena buckets are
-    all-reduced (SUM; the 1/world factor is folded into the Adam kernel) over RCCL on a side HIP stream as soon as autograd has finished the parameters they hold,
+    all-reduced (SUM; the 1/world factor is folded into the optimizer kernel) over RCCL on a side HIP stream as soon as autograd has finished the parameters they hold,
     overlapping the WSI backward; the arena is laid out in reverse registration order so buckets complete
     roughly front to back.
   * step glue kept from the reference: prototype rows L2-normalised before every batch (:1133-1136),
@@ -23,13 +23,13 @@ import torch.distributed as dist
 
 from . import functional as Fn
 from . import kernels as K
+from .arena import ALIGN, ParamArena, check_opt, decay_groups, group_settings, rule_cfg  # noqa: F401  (decay_groups: imported from here too)
 from .functional import POLICIES
 
 f32, bf16 = torch.float32, torch.bfloat16
-_ALIGN = 8  # elements: keeps every parameter 32-B aligned in f32 and 16-B aligned in the bf16 shadow
 
 
-def plan_buckets(sizes: Sequence[int], cap_elems: int, align: int = _ALIGN):
+def plan_buckets(sizes: Sequence[int], cap_elems: int, align: int = ALIGN):
     """Cut the arena (parameters laid out back to back, each padded to `align` elements) into all-reduce
     buckets of at least `cap_elems` elements (the last one takes the remainder).
     Returns ([[start, end, n_params], ...], owner) with owner[i] = bucket index of parameter i."""
@@ -44,102 +44,6 @@ def plan_buckets(sizes: Sequence[int], cap_elems: int, align: int = _ALIGN):
             buckets.append([start, off, count])
             start, count = off, 0
     return buckets, owner
-
-
-# timm's --opt values that create_optimizer_v2 maps to the three rules of mh_optim_step: name -> (rule, nesterov)
-_OPTS = {"adam": ("adam", False), "adamw": ("adamw", False), "sgd": ("sgd", True), "nesterov": ("sgd", True), "momentum": ("sgd", False)}
-
-
-def decay_groups(model: torch.nn.Module, weight_decay: float, filter_bias_and_bn: bool = True):
-    """The parameter groups timm's create_optimizer_v2 hands to torch.optim (train_mirror.py:742-746), as [(weight_decay, [(name,
-    parameter), ...]), ...] over the trainable parameters in model.parameters() order.  With weight_decay > 0 and the filter on:
-    param_groups_weight_decay's [no_decay, decay], no_decay = `p.ndim <= 1 or name.endswith(".bias")` at weight_decay 0 (neither
-    model defines no_weight_decay()); otherwise one group that carries weight_decay."""
-    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
-    if not (weight_decay and filter_bias_and_bn):
-        return [(weight_decay, named)]
-    no_decay = [(n, p) for n, p in named if p.ndim <= 1 or n.endswith(".bias")]
-    decay = [(n, p) for n, p in named if not (p.ndim <= 1 or n.endswith(".bias"))]
-    return [(0.0, no_decay), (weight_decay, decay)]
-
-
-def arena_state_dict(rule: str, t: float, groups, off: dict, m, v, skip=()) -> dict:
-    """The torch.optim-shaped state dict of an arena optimizer (TrainEngine, optim.ArenaOptimizer), on the CPU.  rule: "adam" /
-    "adamw" / "sgd"; t: the arena's step count; groups: [(the group's settings in torch's key order, without "params", [parameters]),
-    ...]; off: id(parameter) -> arena offset; m, v: the moment arenas (None where the rule has none).  State indices run through the
-    groups; parameters whose id is in `skip` (never updated) have no entry, as in torch.  SGD's dict carries t as the top-level "step"."""
-    state, out_groups, i = {}, [], 0
-    for settings, members in groups:
-        first = i
-        for p in members:
-            o, n = off[id(p)], p.numel()
-            if id(p) in skip:
-                pass
-            elif rule != "sgd":
-                state[i] = {"step": torch.tensor(t), "exp_avg": m[o:o + n].view(p.shape).cpu().clone(),
-                            "exp_avg_sq": v[o:o + n].view(p.shape).cpu().clone()}
-            elif m is not None and t > 0:          # torch creates the buffer at a parameter's first step
-                state[i] = {"momentum_buffer": m[o:o + n].view(p.shape).cpu().clone()}
-            i += 1
-        group = dict(settings)
-        group["params"] = list(range(first, i))
-        out_groups.append(group)
-    sd = {"state": state, "param_groups": out_groups}
-    if rule == "sgd":
-        sd["step"] = t
-    return sd
-
-
-def _fill_arena(arena: torch.Tensor, items) -> None:
-    """arena[o : o + n] = tensor for (o, tensor) in items: the tensors already on the device in one mh_gather_many launch, the
-    others (a checkpoint on the CPU, other dtypes) by copy_."""
-    there = [(o, x.detach()) for o, x in items if x.device == arena.device and x.dtype in (f32, bf16) and x.is_contiguous()]
-    if there:
-        K.gather_many(arena, K.gather_table(arena, there))
-    for o, x in items:
-        if not (x.device == arena.device and x.dtype in (f32, bf16) and x.is_contiguous()):
-            arena[o:o + x.numel()].copy_(x.reshape(-1))
-
-
-def arena_load_state(rule: str, who: str, sd: dict, members, off: dict, m, v, expect: Optional[int]) -> float:
-    """Check a torch.optim-shaped state dict against the arena optimizer `who` (its name, for the messages) of rule `rule` and copy
-    its moments into the arenas m, v.  members: [[parameters of group 0], ...]; expect: how many state entries a non-empty state
-    must have (None: any number; parameters without an entry keep their moments).  Returns the step count the dict holds."""
-    order = [p for group in members for p in group]
-    pg = sd.get("param_groups") or []
-    want = "momentum" if rule == "sgd" else "betas"
-    if pg and any(want not in g for g in pg):
-        raise ValueError(f"optimizer state of another rule: {who} loads param groups that hold "
-                         f"{want!r}, these hold {sorted(k for k in pg[0] if k != 'params')}")
-    if pg and [len(g["params"]) for g in pg] != [len(group) for group in members]:
-        raise ValueError(f"optimizer state has param groups of {[len(g['params']) for g in pg]} parameters, those of {who} "
-                         f"have {[len(group) for group in members]}")
-    if expect is not None and len(sd["state"]) not in (0, expect):
-        raise ValueError(f"optimizer state has {len(sd['state'])} entries, the model has {expect} parameters")
-    t = float(sd.get("step", 0.0)) if rule == "sgd" else 0.0
-    into_m, into_v = [], []
-    for i, p in enumerate(order):
-        st = sd["state"].get(i)
-        if st is None:
-            continue
-        def sized(x):
-            if x.numel() != p.numel():
-                raise ValueError(f"optimizer state entry {i} holds {tuple(x.shape)} for a parameter of shape {tuple(p.shape)}")
-            return off[id(p)], x
-        if rule == "sgd":
-            if m is not None:
-                into_m.append(sized(st["momentum_buffer"]))
-            continue
-        if "exp_avg" not in st:
-            raise ValueError(f"optimizer state of another rule: entry {i} holds {sorted(st)}, not Adam's exp_avg / exp_avg_sq")
-        into_m.append(sized(st["exp_avg"]))
-        into_v.append(sized(st["exp_avg_sq"]))
-        t = float(st["step"])
-    if into_m:
-        _fill_arena(m, into_m)
-    if into_v:
-        _fill_arena(v, into_v)
-    return t
 
 
 _EARLY_ADAM = True      # (test hook, round 5) the RNA encoder's share of the optimizer step on its branch's stream, beside the WSI backward
@@ -168,15 +72,11 @@ class TrainEngine:
         both) or "momentum" (SGD without); lr / betas / eps are --lr / --opt-betas / --opt-eps.  With weight_decay > 0 and the filter
         on, 1-D and `.bias` parameters do not decay (decay_groups).  "adam" with weight_decay 0 is the template's step.  Every rule
         runs mh_optim_step over the same arenas (SGD allocates no second-moment arena, and no buffer at momentum 0)."""
-        if opt not in _OPTS:
-            raise NotImplementedError(f"opt {opt!r}: only {', '.join(map(repr, _OPTS))} are implemented (timm's other optimizers are not)")
         self.opt = opt
-        self._rule, self.nesterov = _OPTS[opt]
         self.weight_decay, self.momentum, self.filter_bias_and_bn = weight_decay, float(momentum), bool(filter_bias_and_bn)
         if weight_decay < 0.0 or momentum < 0.0:
             raise ValueError(f"weight_decay {weight_decay} and momentum {momentum} must not be negative")
-        if self._rule == "sgd" and self.nesterov and self.momentum <= 0.0:
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")        # torch.optim.SGD's own refusal
+        self._rule, self.nesterov = check_opt(opt, self.momentum)
         if precision not in POLICIES:
             raise ValueError(f"unknown precision {precision!r}")
         # timm's dispatch_clip_grad modes (train_mirror.py:1219-1229, --clip-mode): "norm" (the template's default: one fused
@@ -217,53 +117,30 @@ class TrainEngine:
             raise Fn.K.MirrorHipError("TrainEngine needs the model on an MI355X device (model.to('cuda') first)")
         self.device = params[0].device
         # arena order: reverse registration order ~ the order in which autograd finishes gradients
-        order = list(reversed(params))
-        offs, total = [], 0
-        for p in order:
-            offs.append(total)
-            total += (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
-        self.numel = total
-        self.master = torch.zeros(total, device=self.device, dtype=f32)
-        self.grad = torch.zeros(total, device=self.device, dtype=f32)
-        # exp_avg / momentum_buffer and exp_avg_sq: SGD has no second moment, and no buffer at all without momentum
-        self.m = torch.zeros(total, device=self.device, dtype=f32) if self._rule != "sgd" or self.momentum > 0.0 else None
-        self.v = torch.zeros(total, device=self.device, dtype=f32) if self._rule != "sgd" else None
-        # bf16 copies of the master arena, and W^T of the 2-D weights (skinny data-gradient kernels stream them like forward weights)
-        bf = self._bf = Fn.ArenaShadows(self.master, zip(order, offs)) if POLICIES[precision].act == bf16 else None
-        self.shadow, self.shadow_t, self._t_params = (bf.flat, bf.flat_t, bf.t_params) if bf is not None else (None, None, [])
-        self.params, self.offsets = order, offs
+        pa = self.arena = ParamArena(list(reversed(params)), self._rule, self.momentum > 0.0, precision, lr)
+        # plain attributes, bound once: step() and _update() read them per launch
+        self.params, self.offsets, self.numel = pa.params, pa.offsets, pa.numel
+        order = pa.params
+        self.master, self.grad, self.m, self.v, self._state = pa.master, pa.grad, pa.m, pa.v, pa.state
+        self._bf, self.shadow, self.shadow_t, self._t_params = pa.bf, pa.shadow, pa.shadow_t, pa.t_params
+        for p, view in zip(order, pa.grad_views):
+            p.grad = view
         # the RNA encoder's parameters (80 % of the arena at c2) are one contiguous range: their gradients are complete when the RNA
         # branch's stream has flushed its deferred weight gradients, ~2 ms before the WSI encoder's last one (see _EARLY_ADAM)
         self._early_range = None
         pname = {id(p): n for n, p in model.named_parameters()}
         idx = [i for i, p in enumerate(order) if pname.get(id(p), "").startswith("rna_encoder.")]
         if idx and idx == list(range(idx[0], idx[-1] + 1)):
-            last = idx[-1]
-            self._early_range = (offs[idx[0]], offs[last] + (order[last].numel() + _ALIGN - 1) // _ALIGN * _ALIGN)
-        with torch.no_grad():
-            for p, o in zip(order, offs):
-                n = p.numel()
-                self.master[o:o + n].copy_(p.detach().reshape(-1))
-                p.data = self.master[o:o + n].view(p.shape)
-                p.grad = self.grad[o:o + n].view(p.shape)
-        self._zero_pending = False
-        self._t_stale = False
+            self._early_range = pa.range_of(idx[0], idx[-1])
+        self._zero_pending = self._t_stale = False
         self.sync_shadows()
-        from ._lib import OPT_ADAM, OPT_ADAMW, OPT_SGD, OptimCfg
-        rule = {"adam": OPT_ADAM, "adamw": OPT_ADAMW, "sgd": OPT_SGD}[self._rule]
-        self._opt_cfg = OptimCfg(rule, betas[0], betas[1], eps, self.momentum, int(self.nesterov))
+        self._opt_cfg = rule_cfg(self._rule, betas, eps, self.momentum, self.nesterov)
         self._group_map = self._group_wd = None          # no decay anywhere: no map, and the kernel looks nothing up
         if weight_decay:
-            # one byte per _ALIGN-element block of the arena names its decay group (a parameter's padding shares its last block
-            # and stays zero: p = g = m = 0 there); the kernel looks the group's weight decay up in a device table
+            # one byte per block names its decay group (ParamArena.group_bytes); the kernel looks its weight decay up in a device table
             groups = self._groups()
-            gmap = torch.zeros(total // _ALIGN, dtype=torch.uint8)
-            off = {id(p): o for p, o in zip(order, offs)}
-            for gi, (_, members) in enumerate(groups):
-                for _, p in members:
-                    o = off[id(p)]
-                    gmap[o // _ALIGN:(o + p.numel() + _ALIGN - 1) // _ALIGN] = gi
-            self._group_map = gmap.to(self.device)
+            group_of = {id(p): gi for gi, (_, members) in enumerate(groups) for _, p in members}
+            self._group_map = pa.group_bytes([group_of[id(p)] for p in order]).to(self.device)
             self._group_wd = torch.tensor([float(wd) for wd, _ in groups], dtype=f32).to(self.device)
         # gradient sink: Functions accumulate weight gradients straight into the arena (mirror_amd.functional._gbuf)
         self._slot_of = {p.data_ptr(): i for i, p in enumerate(order)}
@@ -274,9 +151,6 @@ class TrainEngine:
         self._index_of = {id(p): i for i, p in enumerate(order)}
         self._proto = getattr(model, "prototypes", None)
         self._logit = getattr(model, "logit_scale", None)
-        # step state on the device {t, 1 - b1^t, 1 - b2^t, lr, clip, |g|}: advanced by the optimizer launch itself, so nothing that changes from
-        # step to step is a launch argument and the whole step can be replayed as one HIP graph
-        self._state = torch.tensor([0.0, 0.0, 0.0, float(lr), 1.0, 0.0], device=self.device, dtype=f32)
         # timm's --clip-grad (mode "norm") and --grad-accum-steps (train_mirror.py:1192-1230): both stay on the device
         self.clip_grad = clip_grad
         self.accum_steps = max(1, int(accum_steps))
@@ -316,7 +190,7 @@ class TrainEngine:
         from .ema import _unwrap
         if _unwrap(self.model) is not self.model:
             raise ValueError("TrainEngine drives the bare model: pass it, not a DDP wrapper")
-        self._ema_arena, self._ema_table, self._ema_rows = ema._attach(self)
+        self._ema_arena, self._ema_table, self._ema_rows = ema._attach(self.arena, self.model, self)
         self._ema_cfg = ema._cfg()
         if self.world > 1:
             # rank-identical, as the master is: rank 0's EMA (a fresh EMA is rank 0's model, which is what the master broadcast above held)
@@ -336,11 +210,8 @@ class TrainEngine:
     # ------------------------------------------------------------------ shadows
     def sync_shadows(self) -> None:
         """(Re)publish the bf16 copies after the master arena was written by anything but step()."""
-        if self.shadow is None:
-            return
-        self._bf.refresh()
         self._t_stale = False
-        self._bf.publish(owner=self)
+        self.arena.sync_shadows(owner=self)
 
     def refresh_transposes_now(self) -> None:
         """The transposed copies trail an update until the next step starts (see _step_body); anything that differentiates
@@ -440,13 +311,16 @@ class TrainEngine:
         b = self._bucket_of[id(p)]
         self._pending[b] -= 1
         if self._pending[b] == 0:
-            s, e, _ = self.buckets[b]
-            # a bucket mixes parameters whose gradient kernels were queued on different streams (main, RNA side stream):
-            # the reduction has to wait for all of them, not only for the stream of the parameter that completed it
-            self.comm_stream.wait_stream(torch.cuda.current_stream())
-            Fn.join_side_streams(self.device, self.comm_stream)
-            with torch.cuda.stream(self.comm_stream):
-                self._works.append(self._reduce_slice(s, e))
+            self._start_reduce(b)
+
+    def _start_reduce(self, b: int) -> None:
+        s, e, _ = self.buckets[b]
+        # a bucket mixes parameters whose gradient kernels were queued on different streams (main, RNA side stream):
+        # the reduction has to wait for all of them, not only for the stream of the parameter that completed it
+        self.comm_stream.wait_stream(torch.cuda.current_stream())
+        Fn.join_side_streams(self.device, self.comm_stream)
+        with torch.cuda.stream(self.comm_stream):
+            self._works.append(self._reduce_slice(s, e))
 
     def _reduce_slice(self, s: int, e: int):
         """SUM all-reduce of arena slice [s, e) (called on the communication stream); returns the work handle."""
@@ -459,14 +333,9 @@ class TrainEngine:
     def _finish_reduce(self) -> None:
         if self.world == 1:
             return
-        if any(c != 0 for c in self._pending):  # a parameter got no gradient this step: reduce what is left
-            for b, c in enumerate(self._pending):
-                if c != 0:
-                    s, e, _ = self.buckets[b]
-                    self.comm_stream.wait_stream(torch.cuda.current_stream())
-                    Fn.join_side_streams(self.device, self.comm_stream)
-                    with torch.cuda.stream(self.comm_stream):
-                        self._works.append(self._reduce_slice(s, e))
+        for b, c in enumerate(self._pending):
+            if c != 0:          # a parameter got no gradient this step: reduce what is left
+                self._start_reduce(b)
         for w in self._works:
             w.wait()
         if self._widen:            # bf16 wire format: widen the summed buckets back into the f32 arena (on the comm stream, in order)
@@ -689,7 +558,7 @@ class TrainEngine:
             kw.update(ema=self._ema_arena[lo:hi], ema_cfg=self._ema_cfg)
         gmap = self._group_map
         K.optim_step(cut(self.master), cut(self.grad), cut(self.m), cut(self.v), cut(self.shadow), self._opt_cfg, self._state,
-                     grad_scale=gs, group_map=None if gmap is None else gmap[lo // _ALIGN:hi // _ALIGN], group_wd=self._group_wd,
+                     grad_scale=gs, group_map=None if gmap is None else gmap[lo // ALIGN:hi // ALIGN], group_wd=self._group_wd,
                      tick=tick, **kw)
 
     @staticmethod
@@ -751,35 +620,25 @@ class TrainEngine:
     def _groups(self):
         """decay_groups over the arena's parameters: the torch.optim param groups, in timm's order.  Without decay the one group
         carries the int 0, torch.optim's own default, whatever zero the engine was given."""
-        off = {id(p) for p in self.params}
-        return [(wd, [(n, p) for n, p in members if id(p) in off])
+        return [(wd, [(n, p) for n, p in members if id(p) in self.arena.off_of])
                 for wd, members in decay_groups(self.model, self.weight_decay or 0, self.filter_bias_and_bn)]
-
-    def _group_settings(self, wd) -> dict:
-        if self._rule != "sgd":
-            return {"lr": float(self.lr), "betas": tuple(self.betas), "eps": self.eps, "weight_decay": wd, "amsgrad": False}
-        return {"lr": float(self.lr), "momentum": self.momentum, "dampening": 0, "weight_decay": wd, "nesterov": self.nesterov}
 
     def state_dict(self) -> dict:
         """The state of the matching torch.optim optimizer built as timm builds it (what the reference checkpoints and
-        `resume_checkpoint` reloads), on the CPU: param groups in decay_groups order, state indices running through them.
-        Adam / AdamW: {step, exp_avg, exp_avg_sq} per parameter; SGD: {momentum_buffer}, no state without momentum.  SGD keeps no
-        step: the engine's (the EMA decay and fp8 delayed scaling read it) travels as the extra top-level entry "step", which
-        torch.optim.SGD.load_state_dict ignores."""
-        off = {id(p): o for p, o in zip(self.params, self.offsets)}
-        groups = [(self._group_settings(wd), [p for _, p in members]) for wd, members in self._groups()]
-        return arena_state_dict(self._rule, float(self._state[0].item()), groups, off, self.m, self.v)
+        `resume_checkpoint` reloads): ParamArena.state_dict over the param groups in decay_groups order.  SGD's extra "step" is the
+        engine's, which the EMA decay and fp8 delayed scaling read."""
+        groups = [(group_settings(self._rule, float(self.lr), self.betas, self.eps, wd, self.momentum, self.nesterov), [p for _, p in members])
+                  for wd, members in self._groups()]
+        return self.arena.state_dict(groups, float(self._state[0].item()))
 
     def load_state_dict(self, sd: dict) -> None:
-        off = {id(p): o for p, o in zip(self.params, self.offsets)}
         members = [[p for _, p in m] for _, m in self._groups()]
         pg = sd.get("param_groups") or []
-        t = arena_load_state(self._rule, f"TrainEngine(opt={self.opt!r}, weight_decay={self.weight_decay})", sd, members, off,
-                             self.m, self.v, expect=sum(len(m) for m in members))
+        t = self.arena.load_state(f"TrainEngine(opt={self.opt!r}, weight_decay={self.weight_decay})", sd, members,
+                                  expect=sum(len(m) for m in members))
         if pg:
             self.lr = float(pg[0].get("lr", self.lr))
-        b1, b2 = self.betas
-        self._state[:4].copy_(torch.tensor([t, 1.0 - b1 ** t, 1.0 - b2 ** t, float(self.lr)]))
+        self.arena.set_step(t, *self.betas, self.lr, keep_clip=True)
         self._state_lr = float(self.lr)
         self.step_count = int(t)
         self._graph, self._graph_warm = None, 0          # a captured step is still valid, but re-capture keeps this simple

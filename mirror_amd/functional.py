@@ -89,7 +89,7 @@ def shadow_t(w: torch.Tensor, prec: Precision) -> torch.Tensor:
         if owner is not None and getattr(owner, "_t_stale", False):
             owner.refresh_transposes_now()      # a backward pass outside TrainEngine.step(): its transposes trail the update
         return rec.kept_t
-    # An optimizer that rewrites the master through raw kernels (TrainEngine: mh_adam) does not bump the version counter:
+    # An optimizer that rewrites the master through raw kernels (TrainEngine: mh_optim_step) does not bump the version counter:
     # for a weight whose bf16 shadow it keeps but whose transpose it does not (a dimension that is not a multiple of 32),
     # a cached W^T would be the first step's for ever — transpose the live shadow on every call instead (small weights).
     if rec.kept is not None and rec.kept_at == at:
@@ -109,7 +109,7 @@ def register_shadow_t(w: torch.Tensor, t: Optional[torch.Tensor], owner=None) ->
 
 
 def register_shadow(w: torch.Tensor, s: Optional[torch.Tensor]) -> None:
-    """An optimizer that maintains the bf16 copy itself (mh_adam writes master + shadow in one pass) publishes it
+    """An optimizer that maintains the bf16 copy itself (mh_optim_step writes master + shadow in one pass) publishes it
     here; whoever rewrites the master outside that optimizer must refresh the shadow (TrainEngine.sync_shadows).
     `w` must be the long-lived parameter object: the copy is served to lookups through that object, while it stays on the block it
     had here."""
@@ -1515,7 +1515,7 @@ def dropout_step_end() -> None:
 
 
 def dropout_step_take():
-    """dropout_step_end for a caller that advances the device base inside a launch of its own (mh_adam's `counter`): returns
+    """dropout_step_end for a caller that advances the device base inside a launch of its own (mh_optim_step's `counter`): returns
     (base tensor or None, offsets this step consumed) and resets the host offset."""
     base, used = _dropout_state["base"], _step_used()
     return (base, used) if (base is not None and used) else (None, 0)

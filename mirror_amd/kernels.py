@@ -1874,6 +1874,24 @@ def adam(p, g, m, v, shadow, lr, b1, b2, eps, bc1, bc2, grad_scale=1.0, dev_stat
         _lib.call("mh_adam_ema", *args, _p(ema), C.addressof(ema_cfg), stream=_stream())
 
 
+def _optim_args(name: str, p, g, m, v, shadow, opt_cfg, dev_state, group_map, tables, most: int, what: str, optional: bool, **kw):
+    """What optim_step() and optim_groups() share in front of the launch: the moments the rule reads, the required dev_state, _step_args
+    (kw) and the group map with its tables (`tables`: f32 of one size, 1..`most` entries; `what` ends the refusal; optional: there may
+    be no map, and then no groups).  Returns (number of groups, what _step_args returns)."""
+    sgd = opt_cfg.rule == _lib.OPT_SGD
+    need = [p, g] + ([] if sgd and opt_cfg.momentum == 0.0 else [m]) + ([] if sgd else [v])
+    if dev_state is None:
+        raise MirrorHipError(f"{name}: dev_state is the f32[6] device step state")
+    tail = _step_args(name, p, need, shadow, dev_state, **kw)
+    if group_map is None and optional:
+        return 0, tail
+    ng = 0 if tables[0] is None else tables[0].numel()
+    if (group_map is None or group_map.dtype != torch.uint8 or not group_map.is_contiguous() or group_map.numel() < (p.numel() + 7) // 8 or not 1 <= ng <= most
+            or any(t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != ng for t in tables)):
+        raise MirrorHipError(f"{name}: group_map is uint8 with one entry per 8 elements, {what}")
+    return ng, tail
+
+
 def optim_step(p, g, m, v, shadow, opt_cfg, dev_state: torch.Tensor, grad_scale=1.0, group_map: Optional[torch.Tensor] = None,
                group_wd: Optional[torch.Tensor] = None, clamp: Optional[tuple] = None, counter: Optional[torch.Tensor] = None,
                counter_add: int = 0, tick=True, hole: Optional[tuple] = None, ema: Optional[torch.Tensor] = None, ema_cfg=None) -> None:
@@ -1882,19 +1900,9 @@ def optim_step(p, g, m, v, shadow, opt_cfg, dev_state: torch.Tensor, grad_scale=
     SGD).  group_map (uint8, one entry per 8-element block of p) + group_wd (f32, one weight decay per group): per-parameter decay;
     None = no decay.  dev_state (required here), clamp, counter, tick, hole, ema / ema_cfg: as in adam(); lr is dev_state[3]."""
     _chk(p, g, m, v, shadow, dev_state, counter, ema, group_map, group_wd)
-    n = p.numel()
-    sgd = opt_cfg.rule == _lib.OPT_SGD
-    need = [p, g] + ([] if sgd and opt_cfg.momentum == 0.0 else [m]) + ([] if sgd else [v])
-    if dev_state is None:
-        raise MirrorHipError("optim_step: dev_state is the f32[6] device step state")
-    tail = _step_args("optim_step", p, need, shadow, dev_state, clamp, counter, counter_add, tick, hole, ema, ema_cfg)
-    ng = 0
-    if group_map is not None:
-        ng = 0 if group_wd is None else group_wd.numel()
-        if (group_map.dtype != torch.uint8 or not group_map.is_contiguous() or group_map.numel() < (n + 7) // 8
-                or group_wd is None or group_wd.dtype != torch.float32 or not group_wd.is_contiguous() or not 1 <= ng <= 256):
-            raise MirrorHipError("optim_step: group_map is uint8 with one entry per 8 elements, group_wd f32 with 1..256 decays")
-    _lib.call("mh_optim_step", _p(p), _p(g), _p(m), _p(v), _p(shadow), n, C.addressof(opt_cfg), _p(group_map),
+    ng, tail = _optim_args("optim_step", p, g, m, v, shadow, opt_cfg, dev_state, group_map, (group_wd,), 256, "group_wd f32 with 1..256 decays", True,
+                           clamp=clamp, counter=counter, counter_add=counter_add, tick=tick, hole=hole, ema=ema, ema_cfg=ema_cfg)
+    _lib.call("mh_optim_step", _p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), C.addressof(opt_cfg), _p(group_map),
               _p(group_wd) if group_map is not None else None, ng, grad_scale, _p(dev_state), *tail,
               _p(ema), None if ema is None else C.addressof(ema_cfg), stream=_stream())
 
@@ -1907,19 +1915,10 @@ def optim_groups(p, g, m, v, shadow, opt_cfg, dev_state: torch.Tensor, group_map
     (torch.optim's parameter without a gradient).  group_map, group_wd and group_lr are required, at most 255 groups; both tables are
     read from the device at run time, so a captured launch replays with what they hold then."""
     _chk(p, g, m, v, shadow, dev_state, counter, ema, group_map, group_wd, group_lr)
-    n = p.numel()
-    sgd = opt_cfg.rule == _lib.OPT_SGD
-    need = [p, g] + ([] if sgd and opt_cfg.momentum == 0.0 else [m]) + ([] if sgd else [v])
-    if dev_state is None:
-        raise MirrorHipError("optim_groups: dev_state is the f32[6] device step state")
-    tail = _step_args("optim_groups", p, need, shadow, dev_state, clamp, counter, counter_add, tick, hole, ema, ema_cfg)
-    ng = 0 if group_wd is None else group_wd.numel()
-    if (group_map is None or group_map.dtype != torch.uint8 or not group_map.is_contiguous() or group_map.numel() < (n + 7) // 8
-            or not 1 <= ng <= _lib.OPT_SKIP_GROUP or group_lr is None
-            or any(t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != ng for t in (group_wd, group_lr))):
-        raise MirrorHipError("optim_groups: group_map is uint8 with one entry per 8 elements, group_wd and group_lr f32 with the "
-                             "same 1..255 entries")
-    _lib.call("mh_optim_groups", _p(p), _p(g), _p(m), _p(v), _p(shadow), n, C.addressof(opt_cfg), _p(group_map), _p(group_wd),
+    ng, tail = _optim_args("optim_groups", p, g, m, v, shadow, opt_cfg, dev_state, group_map, (group_wd, group_lr), _lib.OPT_SKIP_GROUP,
+                           "group_wd and group_lr f32 with the same 1..255 entries", False,
+                           clamp=clamp, counter=counter, counter_add=counter_add, tick=tick, hole=hole, ema=ema, ema_cfg=ema_cfg)
+    _lib.call("mh_optim_groups", _p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), C.addressof(opt_cfg), _p(group_map), _p(group_wd),
               _p(group_lr), ng, grad_scale, _p(dev_state), *tail, _p(ema), None if ema is None else C.addressof(ema_cfg),
               stream=_stream())
 

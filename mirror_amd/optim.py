@@ -13,16 +13,12 @@ from typing import List, Optional
 
 import torch
 
-from . import functional as Fn
 from . import kernels as K
-from ._lib import OPT_ADAM, OPT_ADAMW, OPT_SGD, OPT_SKIP_GROUP, MirrorHipError, OptimCfg
-from .engine import _ALIGN, _OPTS, arena_load_state, arena_state_dict, decay_groups
+from ._lib import OPT_SKIP_GROUP, MirrorHipError
+from .arena import ParamArena, check_opt, decay_groups, group_settings, rule_cfg
 from .functional import POLICIES
 
 f32, bf16 = torch.float32, torch.bfloat16
-
-_ADAM_KEYS = ("lr", "betas", "eps", "weight_decay", "amsgrad")
-_SGD_KEYS = ("lr", "momentum", "dampening", "weight_decay", "nesterov")
 
 
 class ArenaOptimizer(torch.optim.Optimizer):
@@ -57,19 +53,14 @@ class ArenaOptimizer(torch.optim.Optimizer):
 
     def __init__(self, params, opt: str = "adam", lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, momentum: float = 0.9,
                  weight_decay: float = 0.0, precision: str = "bf16"):
-        if opt not in _OPTS:
-            raise NotImplementedError(f"opt {opt!r}: only {', '.join(map(repr, _OPTS))} are implemented (timm's other optimizers are not)")
+        self._rule, nesterov = check_opt(opt)
         if precision not in POLICIES:
             raise ValueError(f"unknown precision {precision!r}")
         self.opt = opt
-        self._rule, nesterov = _OPTS[opt]
         if lr < 0.0 or weight_decay < 0.0 or momentum < 0.0 or eps < 0.0:
             raise ValueError(f"lr {lr}, weight_decay {weight_decay}, momentum {momentum} and eps {eps} must not be negative")
-        if self._rule == "sgd":
-            defaults = dict(lr=lr, momentum=float(momentum), dampening=0, weight_decay=weight_decay, nesterov=nesterov)
-        else:
-            defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False)
-        self._keys = _SGD_KEYS if self._rule == "sgd" else _ADAM_KEYS
+        defaults = group_settings(self._rule, lr, betas, eps, weight_decay, float(momentum), nesterov)
+        self._keys = tuple(defaults)          # torch's keys for the rule
         self._laid_out = False
         super().__init__(params, defaults)
         self._cfg_key = None
@@ -81,44 +72,20 @@ class ArenaOptimizer(torch.optim.Optimizer):
                                      f"{tuple(p.shape)} {p.dtype} on {p.device}, requires_grad={p.requires_grad}: there is no CPU path")
         if len(self.param_groups) > OPT_SKIP_GROUP:
             raise NotImplementedError(f"{len(self.param_groups)} parameter groups: the group byte holds {OPT_SKIP_GROUP}")
-        self.device = order[0].device
-        offs, total = [], 0
-        for p in order:
-            offs.append(total)
-            total += (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
-        self.numel = total
-        self.params, self.offsets = order, offs
-        self.master = torch.zeros(total, device=self.device, dtype=f32)
-        self.grad = torch.zeros(total, device=self.device, dtype=f32)
-        mom = self._rule != "sgd" or defaults["momentum"] > 0.0
-        self.m = torch.zeros(total, device=self.device, dtype=f32) if mom else None
-        self.v = torch.zeros(total, device=self.device, dtype=f32) if self._rule != "sgd" else None
-        self._bf = Fn.ArenaShadows(self.master, zip(order, offs)) if POLICIES[precision].act == bf16 else None
-        self.shadow = None if self._bf is None else self._bf.flat
-        self._gviews: List[torch.Tensor] = []
-        with torch.no_grad():
-            for p, o in zip(order, offs):
-                n = p.numel()
-                self.master[o:o + n].copy_(p.detach().reshape(-1))
-                p.data = self.master[o:o + n].view(p.shape)
-                self._gviews.append(self.grad[o:o + n].view(p.shape))
-                p.grad = self._gviews[-1]
+        pa = self.arena = ParamArena(order, self._rule, float(momentum) > 0.0, precision, lr)
+        self.params, self.offsets, self.numel, self.device = pa.params, pa.offsets, pa.numel, pa.device
+        self.master, self.grad, self.m, self.v, self._state = pa.master, pa.grad, pa.m, pa.v, pa.state
+        self._bf, self.shadow, self._gviews = pa.bf, pa.shadow, pa.grad_views
+        for p, view in zip(order, self._gviews):
+            p.grad = view
         self.sync_shadows()
-        # one byte per _ALIGN-element block of the arena names its parameter group (a parameter's padding shares its last block and
-        # stays zero); OPT_SKIP_GROUP once a parameter is known to have no gradient.  The tables [weight decay; lr] live in one fixed
-        # device buffer: the kernel looks both up per block, so a captured launch follows the schedulers
-        self._gmap_host = torch.zeros(total // _ALIGN, dtype=torch.uint8)
-        self._group_of = []
-        for gi, g in enumerate(self.param_groups):
-            self._group_of += [gi] * len(g["params"])
-        for p, o, gi in zip(order, offs, self._group_of):
-            self._gmap_host[o // _ALIGN:(o + p.numel() + _ALIGN - 1) // _ALIGN] = gi
+        # one byte per block names its parameter group (ParamArena.group_bytes); OPT_SKIP_GROUP once a parameter is known to have no gradient.
+        # The tables [weight decay; lr] live in one fixed device buffer (state[3] is not read): a captured launch follows the schedulers
+        self._gmap_host = pa.group_bytes([gi for gi, g in enumerate(self.param_groups) for _ in g["params"]])
         self._gmap = self._gmap_host.to(self.device)
         self._tab = torch.zeros(2, len(self.param_groups), device=self.device, dtype=f32)
         self._tab_host = None                 # what the device tables hold (None: nothing yet)
         self._has: Optional[List[bool]] = None      # per parameter: has a gradient (fixed by the first step)
-        # step state on the device {t, 1 - b1^t, 1 - b2^t, lr (unused: the table has it), clip, |g|}, advanced by the launch itself
-        self._state = torch.tensor([0.0, 0.0, 0.0, float(lr), 1.0, 0.0], device=self.device, dtype=f32)
         self._clipped = False
         self._laid_out = True
 
@@ -141,16 +108,15 @@ class ArenaOptimizer(torch.optim.Optimizer):
             mu, nesterov, damp = key
             if damp != 0:
                 raise NotImplementedError("SGD dampening is not built (timm passes 0)")
-            if nesterov and mu <= 0.0:
-                raise ValueError("Nesterov momentum requires a momentum and zero dampening")        # torch.optim.SGD's own refusal
+            check_opt(self.opt, mu, nesterov)
             if self._cfg_key is not None and (mu > 0.0) != (self.m is not None):
                 raise NotImplementedError("momentum cannot change between zero and non-zero: the buffer arena is laid out at construction")
-            cfg = OptimCfg(OPT_SGD, 0.0, 0.0, 0.0, float(mu), int(bool(nesterov)))
+            cfg = rule_cfg("sgd", (0.0, 0.0), 0.0, mu, nesterov)
         else:
             (b1, b2), eps, amsgrad = key
             if amsgrad:
                 raise NotImplementedError("amsgrad is not built")
-            cfg = OptimCfg(OPT_ADAM if self._rule == "adam" else OPT_ADAMW, float(b1), float(b2), float(eps), 0.0, 0)
+            cfg = rule_cfg(self._rule, (b1, b2), eps, 0.0, False)
         if self._cfg_key is not None and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("betas / eps / momentum changed: they are launch arguments, capture step() again")
         self._opt_cfg, self._cfg_key = cfg, key
@@ -192,9 +158,10 @@ class ArenaOptimizer(torch.optim.Optimizer):
             if not all(has):
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("run one eager step() before capturing: the first step fixes which parameters have gradients")
-                for p, o, h in zip(self.params, self.offsets, has):
+                for p, h in zip(self.params, has):
                     if not h:
-                        self._gmap_host[o // _ALIGN:(o + p.numel() + _ALIGN - 1) // _ALIGN] = OPT_SKIP_GROUP
+                        first, end = self.arena.span(p)
+                        self._gmap_host[first:end] = OPT_SKIP_GROUP
                 self._gmap.copy_(self._gmap_host)
             self._has = has
         if items:
@@ -251,26 +218,19 @@ class ArenaOptimizer(torch.optim.Optimizer):
 
     def sync_shadows(self) -> None:
         """(Re)publish the bf16 copies after the master arena was written by anything but step()."""
-        if self._bf is not None:
-            self._bf.refresh()
-            self._bf.publish()
+        self.arena.sync_shadows()
 
     # ------------------------------------------------------------------ state (torch.optim's shape and entry order)
-    def _skipped(self):
-        return () if self._has is None else {id(p) for p, h in zip(self.params, self._has) if not h}
-
     def state_dict(self) -> dict:
-        """torch.optim's dict for the same groups, on the CPU: Adam / AdamW {step, exp_avg, exp_avg_sq} per parameter, SGD
-        {momentum_buffer}; a skipped parameter has no entry.  SGD keeps no step in torch: the arena's travels as the extra top-level
-        "step", which torch.optim.SGD.load_state_dict ignores.  Group entries beyond torch's keys for the rule (a scheduler's
-        "initial_lr") follow them."""
-        off = {id(p): o for p, o in zip(self.params, self.offsets)}
+        """torch.optim's dict for the same groups (ParamArena.state_dict); a skipped parameter has no entry.  Group entries beyond
+        torch's keys for the rule (a scheduler's "initial_lr") follow them."""
         groups = []
         for g in self.param_groups:
             settings = {k: g[k] for k in self._keys}
             settings.update({k: v for k, v in g.items() if k not in self._keys and k != "params"})
             groups.append((settings, g["params"]))
-        return arena_state_dict(self._rule, float(self._state[0].item()), groups, off, self.m, self.v, skip=self._skipped())
+        skip = () if self._has is None else {id(p) for p, h in zip(self.params, self._has) if not h}
+        return self.arena.state_dict(groups, float(self._state[0].item()), skip=skip)
 
     def load_state_dict(self, state_dict: dict) -> None:
         """Load this optimizer's dict, or torch.optim.Adam / AdamW / SGD's over the same groups (tensors on the device arrive in one
@@ -282,23 +242,21 @@ class ArenaOptimizer(torch.optim.Optimizer):
         pg = sd.get("param_groups") or []
         if any(g.get("amsgrad") or g.get("maximize") for g in pg):
             raise NotImplementedError("amsgrad and maximize are not built")
-        off = {id(p): o for p, o in zip(self.params, self.offsets)}
         expect = None if self._has is None else sum(self._has)
-        t = arena_load_state(self._rule, f"ArenaOptimizer(opt={self.opt!r})", sd, [g["params"] for g in self.param_groups], off,
-                             self.m, self.v, expect=expect)
+        t = self.arena.load_state(f"ArenaOptimizer(opt={self.opt!r})", sd, [g["params"] for g in self.param_groups], expect)
         if self._rule == "sgd" and sd["state"] and t == 0.0:
             t = 1.0                       # torch.optim.SGD's dict has no step; buffers mean that at least one was taken
         for g, new in zip(self.param_groups, pg):
             g.update({k: v for k, v in new.items() if k in self._keys or k == "initial_lr"})
         self._settings()
         b1, b2 = (self._opt_cfg.beta1, self._opt_cfg.beta2) if self._rule != "sgd" else (0.0, 0.0)
-        self._state.copy_(torch.tensor([t, 1.0 - b1 ** t, 1.0 - b2 ** t, float(self.param_groups[0]["lr"]), 1.0, 0.0]))
+        self.arena.set_step(t, b1, b2, self.param_groups[0]["lr"])
         self._clipped = False
         self.sync_shadows()
 
 
 def param_groups_of(model: torch.nn.Module, weight_decay: float = 0.0, filter_bias_and_bn: bool = True) -> List[dict]:
-    """timm's parameter groups (engine.decay_groups) in torch's form, over the parameters that require gradients."""
+    """timm's parameter groups (arena.decay_groups) in torch's form, over the parameters that require gradients."""
     return [{"params": [p for _, p in members], "weight_decay": wd}
             for wd, members in decay_groups(model, weight_decay, filter_bias_and_bn)]
 

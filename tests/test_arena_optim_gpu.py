@@ -516,3 +516,89 @@ def test_bf16_policy_step_writes_the_copies_the_forward_reads():
     wsi, rna = _batch(90)
     with torch.no_grad():
         assert torch.equal(model(wsi, rna), fresh(wsi, rna))
+
+
+# ====================================================================== 5. ParamArena under the optimizer
+PA_SHAPES = [(1,), (7,), (9,), (32, 64), (33, 5)]          # offsets 0, 8, 16, 32, 2080; 2248 elements, 18 of them padding (7 + 1 + 7 + 0 + 3)
+
+
+def _pa_params(seed=12):
+    gen = torch.Generator().manual_seed(seed)
+    return [torch.nn.Parameter(torch.randn(*s, generator=gen).cuda()) for s in PA_SHAPES]
+
+
+def _padding(offsets, params, total):
+    pad = torch.ones(total, dtype=torch.bool)
+    for p, o in zip(params, offsets):
+        pad[o:o + p.numel()] = False
+    return pad.cuda()
+
+
+def test_param_arena_aliases_parameters_and_publishes_its_copies():
+    from mirror_amd import functional as Fn
+    from mirror_amd.arena import ParamArena
+    params = _pa_params()
+    before = [p.detach().clone() for p in params]
+    pa = ParamArena(params, "adamw", True, "bf16", 1e-3)
+    assert pa.offsets == [0, 8, 16, 32, 2080] and pa.numel == 2248
+    for p, o, view, was in zip(params, pa.offsets, pa.grad_views, before):
+        assert p.data_ptr() == pa.master.data_ptr() + 4 * o and view.data_ptr() == pa.grad.data_ptr() + 4 * o
+        assert view.shape == p.shape and torch.equal(p.detach(), was)
+        assert torch.equal(pa.master[o:o + p.numel()], was.reshape(-1))
+    pad = _padding(pa.offsets, params, pa.numel)
+    assert int(pad.sum()) == 18 and not bool(pa.master[pad].any())
+    assert [(id(p), o) for p, o in pa.t_params] == [(id(params[3]), 32)]
+    assert pa.shadow.numel() == pa.shadow_t.numel() == pa.numel
+    pa.sync_shadows()
+    for p, o in zip(params, pa.offsets):
+        s = Fn.shadow(p, Fn.BF16)
+        assert s.data_ptr() == pa.shadow.data_ptr() + 2 * o and s.shape == p.shape
+        assert torch.equal(_bits(s), _bits(p.detach().bfloat16()))
+    wt = Fn.shadow_t(params[3], Fn.BF16)
+    assert wt.data_ptr() == pa.shadow_t.data_ptr() + 2 * 32 and torch.equal(_bits(wt), _bits(params[3].detach().bfloat16().t().contiguous()))
+
+
+def _pa_optimizer(lr=1e-2):
+    from mirror_amd.optim import ArenaOptimizer
+    ps = _pa_params()
+    groups = [{"params": [ps[0], ps[1], ps[2]], "weight_decay": 0.0}, {"params": [ps[3], ps[4]], "weight_decay": 0.1}]
+    return ArenaOptimizer(groups, opt="adamw", lr=lr, precision="bf16")
+
+
+def _pa_step(opts, k):
+    g = torch.randn(opts[0].numel, generator=torch.Generator().manual_seed(100 + k)).cuda()
+    for o in opts:
+        o.zero_grad()
+        for view, off in zip(o._gviews, o.offsets):
+            view.copy_(g[off:off + view.numel()].view(view.shape))
+        o.step()
+
+
+def test_three_adamw_steps_leave_the_padding_bit_zero():
+    opt = _pa_optimizer()
+    start = opt.master.clone()
+    for k in range(3):
+        _pa_step([opt], k)
+    pad = _padding(opt.offsets, opt.params, opt.numel)
+    assert float(opt._state[0]) == 3.0 and not torch.equal(opt.master, start)
+    for name in ("master", "m", "v", "shadow"):
+        t = getattr(opt, name)[pad]
+        assert t.numel() == 18 and bool((_bits(t).view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32) == 0).all()), name
+
+
+def test_state_dict_round_trip_continues_bit_for_bit():
+    a, b = _pa_optimizer(), _pa_optimizer(lr=0.5)
+    for k in range(2):
+        _pa_step([a], k)
+    b.load_state_dict(a.state_dict())
+    b.master.copy_(a.master)            # the optimizer's dict holds the moments and settings; the parameters travel with the model
+    b.sync_shadows()
+    # the reloaded bias corrections are the host's float64 powers rounded once, the original's the tick kernel's float32 powf: they may
+    # differ in the last bits, and nothing reads them — the next launch's tick forms both from t before the update does
+    assert b.param_groups[0]["lr"] == 1e-2 and float(b._state[0]) == float(a._state[0]) == 2.0
+    for k in (2,):
+        _pa_step([a, b], k)
+    assert float(a._state[0]) == 3.0
+    for name in ("master", "m", "v"):
+        assert torch.equal(getattr(a, name), getattr(b, name)), name
+    assert torch.equal(a._state[:3], b._state[:3])
