@@ -600,6 +600,45 @@ int mh_mse_masked_bwd(const void* pred, const void* tgt, const float* mask, cons
  * elements; src is the bank of all slides' patch features back to back ([src_rows, F]); row holds GLOBAL row indices
  * (slide offset + sampled index; clamped to the bank). */
 int mh_gather_rows(const void* src, const int64_t* row, void* out, int64_t R, int64_t F, int64_t src_rows, int dt, mh_stream s);
+/* Data feed draws (csrc/datafeed.hip): the token draw `np.random.choice(n_i, N, replace=n_i < N)` of dataset_pretrain.py:157-161,
+ * dataset_subtyping.py:187-200 and dataset_survival.py:293-314 for a whole batch, and the slide-id draw of utils/loader.py:15-26
+ * (`WeightedRandomSampler(weights, len(weights))`), one launch each, no host round trip, capturable in a graph.
+ *
+ * The stream: Philox4x32-10 under key = (lo32(seed), hi32(seed)) like mh_dropout / mh_noise_draws, whose counters have c2 = c3 = 0;
+ * a draw sets bit 31 of c3 and so never shares a block with them under the same seed:
+ *     counter = (lo32(blk), kind, lo32(draw), 0x80000000 | hi32(draw))     kind = 0 for token draws, 1 for slide-id draws; draw < 2^63
+ * Element e of a draw is word e & 3 of block blk = e >> 2.
+ *
+ * mh_sample_rows: rows [B, N] int64.  Batch slot b holds slide sl = slot_slide[b] of n = length[sl] rows that begin at bank row
+ * start[sl], and uses draw = offset + *dev_base + b (*dev_base counts as 0 when the pointer is NULL; it is device memory, so a captured
+ * graph that bumps it draws fresh rows at every replay, and two slots that hold the same slide get different rows).  The result
+ * depends on (seed, draw, n, N) only.  With w_e = element e of the draw:
+ *   n <  N (with replacement):     rows[b, i] = start[sl] + ((w_i * n) >> 32); the multiply-shift favours some rows by at most
+ *                                  n / 2^32 (relative), against a uniform draw.
+ *   n >= N (without replacement):  row j of the slide gets the 64-bit key K_j = (w_j << 32) | j; rows[b, :] = start[sl] + the N
+ *                                  indices j with the smallest keys, in ascending key order — a uniformly random ORDERED subset, what
+ *                                  np.random.choice(n, N, replace=False) returns.  Equal 32-bit words are ordered by index: a relative
+ *                                  bias of order 2^-32.
+ * All four tables are device memory.  A slot whose slide id lies outside [0, S) gets -1 in every row (mh_gather_rows clamps to the
+ * bank); a slot whose slide has length <= 0 or >= 2^31 gets start[sl] in every row: the lengths live on the device, so the launch
+ * cannot refuse them without a read-back (DeviceSlideBank refuses such slides when it is built).  MH_EINVAL for N > 8192, N < 0, B < 0
+ * or offset + B >= 2^63.
+ * The kernel: one workgroup per slot sorts keys in LDS (at most 16384).  It keeps the keys whose word lies below a threshold chosen
+ * for an expected N + slack * sqrt(N) candidates, compacts them into LDS and sorts those; a slide whose n keys all fit a sort of that
+ * size (the next power of two, at least 128) skips the threshold and sorts them all.  When fewer than N or more than 16384 keys pass,
+ * the threshold moves and the pass repeats — any threshold that lets between N and 16384 keys through gives the same rows bit for
+ * bit, so `slack` (>= 0; 8: a retry about once in 1e15 slots, 0: about every other slot, 1e3 on a slide above 16384 rows: always too
+ * many at first) changes the time, never the result. */
+int mh_sample_rows(const int64_t* slot_slide, const int64_t* length, const int64_t* start, int64_t* rows, int B, int N, int64_t S,
+                   uint64_t seed, uint64_t offset, const uint64_t* dev_base, float slack, mh_stream s);
+/* out [count] int64 = slide ids drawn with replacement from the distribution whose cumulative sums are cdf [S] (f64, device,
+ * non-decreasing, cdf[S - 1] = 1), on the stream above with kind = 1 and draw = offset + *dev_base.  Output i uses elements 2 i and 2 i + 1:
+ *     u = (((w_{2i} >> 5) << 26) | (w_{2i+1} >> 6)) * 2^-53        (53 random bits, u in [0, 1), exact in f64)
+ *     out[i] = min(#{k : cdf[k] <= u}, S - 1)                      (a binary search, no other arithmetic)
+ * An entry of weight 0 (cdf[k] == cdf[k - 1], or cdf[0] == 0) is never drawn.  By distribution this is torch's
+ * WeightedRandomSampler(weights, count, replacement=True); the values differ, as under any change of generator.  count <= 2^32. */
+int mh_sample_weighted(const double* cdf, int64_t S, int64_t* out, int64_t count, uint64_t seed, uint64_t offset,
+                       const uint64_t* dev_base, mh_stream s);
 /* Gradient of the WSI encoder output E [B, T, D] (f32), which three consumers read (models/mirror.py:684, :690, :700, :833):
  *   dE[b, t] = gfull[b, t] + alpha * x[b, t - 1] (t >= 1) + (t == 0 ? c[b] : 0)
  * gfull f32 [B, T, D], x [B, T-1, D] in dt_x, c f32 [B, D]; each may be NULL (taken as zero). */

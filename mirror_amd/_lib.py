@@ -183,6 +183,8 @@ _SIGS = {
     "mh_mse_masked_bwd": [P, P, P, P, P, F, P, P, L, I, L, L, I, I, I, P, I],
     "mh_fanout_bwd": [P, P, F, P, P, I, I, I, I],
     "mh_gather_rows": [P, P, P, L, L, L, I],
+    "mh_sample_rows": [P, P, P, P, I, I, L, U64, U64, P, F],
+    "mh_sample_weighted": [P, L, P, L, U64, U64, P],
     "mh_quant_fp8": [P, L, P, P, P, I],
     "mh_quant_fp8_delayed": [P, L, P, P, P, P, F, I],
     "mh_gemm_fp8": [P, L, L, P, L, P, L, L, I, P, P, P, I, I, I, I, I],

@@ -7,11 +7,18 @@ The reference loads one slide's patch features [n_i, F] per item, draws `num_wsi
 bf16), the index draw runs on the device (a random permutation prefix when the slide is long enough, i.i.d. uniform
 draws — i.e. sampling WITH replacement — when it is short: the two branches of :157) and the gather is one HIP kernel
 launch per batch (mh_gather_rows, HBM bound: N * F * 2 bytes per sample).
+
+`DeviceSlideBank.sample` / `batch_sampled` / `epoch` are the same feed on the library's own Philox stream: the index draw of a whole batch
+is ONE launch (mh_sample_rows) that reads the slide ids and lengths on the device, so it can be captured in a graph and restated from
+(seed, draw id) on the host.  With a `targets` table the bank also serves the downstream datasets (dataset_subtyping.py:187-200: label;
+dataset_survival.py:293-314: disc_label, event_time, censorship), and `ClassBalancedSampler` is `utils/loader.py:15-26`
+(train_survival.py:948-949 --weighted-sampler) on the same stream.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence
+from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import kernels as K
@@ -33,9 +40,12 @@ class DeviceSlideBank:
     dataset would collate: (wsi [B, N, F], rna [B, G] float32)."""
 
     def __init__(self, slides: Sequence[torch.Tensor], rna: torch.Tensor, num_wsi_feature_tokens: int, device="cuda",
-                 dtype: Optional[torch.dtype] = None):
+                 dtype: Optional[torch.dtype] = None, targets: Optional[Dict[str, torch.Tensor]] = None):
         if len(slides) == 0 or len(slides) != rna.shape[0]:
             raise ValueError("need one RNA row per slide")
+        for name, t in (targets or {}).items():
+            if t.dim() < 1 or t.shape[0] != len(slides):
+                raise ValueError(f"target table {name!r} needs one row per slide")
         Fd = slides[0].shape[1]
         for sl in slides:
             if sl.dim() != 2 or sl.shape[1] != Fd or sl.shape[0] == 0:
@@ -50,6 +60,12 @@ class DeviceSlideBank:
         self.bank = torch.cat([sl.to(dtype) for sl in slides], dim=0).to(dev).contiguous()
         self.rna = rna.to(dev, torch.float32).contiguous()
         self.device = dev
+        if int(self.lengths.max()) >= 1 << 31:
+            raise MirrorHipError("DeviceSlideBank: a slide of 2^31 rows or more is beyond the device draw's 31-bit row index")
+        # the tables mh_sample_rows reads, and the per-slide targets of the downstream datasets (label / disc_label, event_time, censorship)
+        self.lengths_dev = self.lengths.to(dev)
+        self.offsets_dev = self.offsets.to(dev)
+        self.targets = {name: t.to(dev).contiguous() for name, t in (targets or {}).items()}
 
     def __len__(self) -> int:
         return int(self.lengths.numel())
@@ -67,6 +83,93 @@ class DeviceSlideBank:
         wsi = K.gather_rows(self.bank, rows)
         idx = torch.as_tensor(list(ids), device=self.device, dtype=torch.int64)
         return wsi, K.gather_rows(self.rna, idx)
+
+    def _ids(self, ids) -> torch.Tensor:
+        if isinstance(ids, torch.Tensor):
+            if not ids.is_cuda:
+                raise MirrorHipError("DeviceSlideBank: slide ids are a sequence of ints or a device int64 tensor (no CPU path)")
+            if ids.dtype != torch.int64 or ids.dim() != 1:
+                raise MirrorHipError(f"DeviceSlideBank: device slide ids must be 1-d int64, got {tuple(ids.shape)} {ids.dtype}")
+            return ids.contiguous()
+        return torch.as_tensor([int(i) for i in ids], device=self.device, dtype=torch.int64)
+
+    def sample(self, ids, *, seed: int, offset: int = 0, dev_base: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[B, N] global row indices for the slides `ids` in ONE launch (mh_sample_rows): slot b uses draw id offset + *dev_base + b
+        under `seed`.  With a device tensor for `ids` nothing touches the host, and the call can be captured in a graph (after one call
+        outside a capture: the first launch of a process opts the kernel in to its 128 KiB of LDS)."""
+        return K.sample_rows(self._ids(ids), self.lengths_dev, self.offsets_dev, self.num_tokens, seed, offset, dev_base)
+
+    def batch_sampled(self, ids, *, seed: int, offset: int = 0, dev_base: Optional[torch.Tensor] = None):
+        """(wsi [B, N, F], rna [B, G]) — and, for a bank with targets, a dict of the target rows of `ids` — on the device draw."""
+        idx = self._ids(ids)
+        rows = K.sample_rows(idx, self.lengths_dev, self.offsets_dev, self.num_tokens, seed, offset, dev_base)
+        wsi, rna = K.gather_rows(self.bank, rows), K.gather_rows(self.rna, idx)
+        if not self.targets:
+            return wsi, rna
+        return wsi, rna, {name: t.index_select(0, idx) for name, t in self.targets.items()}
+
+    def epoch(self, batch_size: int, *, epoch: int, seed: int, sampler: Optional["ClassBalancedSampler"] = None, shuffle: bool = True,
+              drop_last: bool = False, start_batch: int = 0) -> Iterator:
+        """`batch_sampled` results over one epoch of slide ids.  The ids are the sampler's single draw of len(bank) ids (draw id `epoch`
+        under the sampler's seed), or a host permutation seeded by seed + epoch (`shuffle`), or range(len(bank)); the batch whose first
+        slot is k draws its tokens with draw ids (epoch << 32) + k + b under `seed`.  Everything follows from (seed, epoch, batch
+        index): `start_batch` resumes an interrupted epoch with the batches it would have seen."""
+        if sampler is not None:
+            ids = sampler.draw(len(self), offset=int(epoch))
+        else:
+            ids = torch.as_tensor(epoch_ids(len(self), epoch=epoch, seed=seed, shuffle=shuffle), device=self.device, dtype=torch.int64)
+        for first, count, offset in epoch_plan(len(self), batch_size, epoch=epoch, drop_last=drop_last)[int(start_batch):]:
+            yield self.batch_sampled(ids[first:first + count], seed=seed, offset=offset)
+
+
+def epoch_ids(n: int, *, epoch: int, seed: int, shuffle: bool = True) -> List[int]:
+    """The slide ids of one epoch without a sampler: torch.randperm(n) under seed + epoch, or 0 .. n - 1."""
+    if not shuffle:
+        return list(range(n))
+    return torch.randperm(n, generator=torch.Generator().manual_seed(int(seed) + int(epoch))).tolist()
+
+
+def epoch_plan(n: int, batch_size: int, *, epoch: int, drop_last: bool = False) -> List[Tuple[int, int, int]]:
+    """(first slot, slots, token draw offset) of every batch of an epoch of n ids: offset = (epoch << 32) + first slot."""
+    if batch_size <= 0 or not 0 <= int(epoch) < 1 << 30 or n >= 1 << 32:
+        raise ValueError("epoch_plan: batch_size >= 1, 0 <= epoch < 2^30, fewer than 2^32 ids")
+    plan = []
+    for first in range(0, n, batch_size):
+        count = min(batch_size, n - first)
+        if count == batch_size or not drop_last:
+            plan.append((first, count, (int(epoch) << 32) + first))
+    return plan
+
+
+def balanced_weights(labels) -> np.ndarray:
+    """`make_weights_for_balanced_classes` of utils/loader.py:16-23: len / count[label] per sample, f64."""
+    labels = np.asarray(torch.as_tensor(labels).cpu().numpy(), dtype=np.int64).reshape(-1)
+    if labels.size == 0 or labels.min() < 0:
+        raise ValueError("balanced_weights: need at least one label, none negative")
+    counts = np.bincount(labels)
+    return float(labels.size) / counts[labels].astype(np.float64)
+
+
+class ClassBalancedSampler:
+    """`class_balanced_sampler(dataset)` of utils/loader.py:15-26 — WeightedRandomSampler(len / count[label], len(dataset)), with
+    replacement — as one launch on the library's stream (mh_sample_weighted).  The cdf (cumsum / sum, f64) is built once on the host;
+    `draw(count, offset)` returns `count` device ids for draw id offset + *dev_base under `seed`.  torch's sampler draws other values
+    from the same distribution."""
+
+    def __init__(self, labels, *, device, seed: int):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise MirrorHipError("ClassBalancedSampler draws on an MI355X device (no CPU path); use utils/loader.py on the host")
+        self.weights = balanced_weights(labels)
+        csum = np.cumsum(self.weights)
+        self.cdf = torch.from_numpy(csum / csum[-1]).to(dev)
+        self.device, self.seed = dev, int(seed)
+
+    def __len__(self) -> int:
+        return int(self.weights.size)
+
+    def draw(self, count: int, offset: int = 0, dev_base: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return K.sample_weighted(self.cdf, count, self.seed, offset, dev_base)
 
 
 class HostFeeder:

@@ -1315,6 +1315,54 @@ def gather_rows(src: torch.Tensor, rows: torch.Tensor, out: Optional[torch.Tenso
     return out
 
 
+def _i64_table(t: torch.Tensor, name: str) -> torch.Tensor:
+    if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
+        raise MirrorHipError(f"{name} must be a contiguous 1-d int64 tensor, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def _draw_base(dev_base: Optional[torch.Tensor], name: str) -> None:
+    if dev_base is not None and (dev_base.dtype not in (torch.int64, torch.uint64) or dev_base.numel() < 1):
+        raise MirrorHipError(f"{name}: dev_base is one 64-bit counter in device memory")
+
+
+def sample_rows(slot_slide: torch.Tensor, lengths: torch.Tensor, starts: torch.Tensor, N: int, seed: int, offset: int,
+                dev_base: Optional[torch.Tensor] = None, slack: float = 8.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 [B, N] bank rows: slot b draws N rows of slide slot_slide[b] (lengths / starts: the [S] tables of the bank) with draw id
+    offset + *dev_base + b under `seed` (mh_sample_rows: without replacement when the slide has >= N rows, with replacement below).
+    `slack` moves the kernel's candidate threshold, never the result."""
+    _chk(slot_slide, lengths, starts, dev_base, out)
+    _i64_table(slot_slide, "sample_rows: slot_slide"), _i64_table(lengths, "sample_rows: lengths"), _i64_table(starts, "sample_rows: starts")
+    _draw_base(dev_base, "sample_rows")
+    if lengths.numel() != starts.numel():
+        raise MirrorHipError("sample_rows: one length and one start per slide")
+    B, N = slot_slide.numel(), int(N)
+    if out is None:
+        out = torch.empty((B, max(N, 0)), device=slot_slide.device, dtype=torch.int64)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (B, N) or not out.is_contiguous():
+        raise MirrorHipError(f"sample_rows: out must be a contiguous int64 [{B}, {N}] tensor")
+    _lib.call("mh_sample_rows", _p(slot_slide), _p(lengths), _p(starts), _p(out), B, N, lengths.numel(), int(seed) & (2 ** 64 - 1), int(offset),
+              _p(dev_base), float(slack), stream=_stream())
+    return out
+
+
+def sample_weighted(cdf: torch.Tensor, count: int, seed: int, offset: int, dev_base: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 [count] ids drawn with replacement from the distribution with cumulative sums cdf [S] (f64), draw id offset + *dev_base
+    under `seed` (mh_sample_weighted)."""
+    _chk(cdf, dev_base, out)
+    if cdf.dtype != torch.float64 or cdf.dim() != 1 or cdf.numel() == 0 or not cdf.is_contiguous():
+        raise MirrorHipError(f"sample_weighted: cdf must be a non-empty contiguous 1-d float64 tensor, got {tuple(cdf.shape)} {cdf.dtype}")
+    _draw_base(dev_base, "sample_weighted")
+    count = int(count)
+    if out is None:
+        out = torch.empty((max(count, 0),), device=cdf.device, dtype=torch.int64)
+    elif out.dtype != torch.int64 or out.numel() != count or not out.is_contiguous():
+        raise MirrorHipError(f"sample_weighted: out must be a contiguous int64 tensor of {count} elements")
+    _lib.call("mh_sample_weighted", _p(cdf), cdf.numel(), _p(out), count, int(seed) & (2 ** 64 - 1), int(offset), _p(dev_base), stream=_stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- masking
 def rank_mask(noise: torch.Tensor, len_keep: int) -> torch.Tensor:
     _chk(noise)
