@@ -165,7 +165,6 @@ _SIGS = {
     "mh_relu_bwd": [P, P, P, L, I, L, L, L, I, I, I],
     "mh_dropout": [P, P, L, F, U64, U64, P, I, I],
     "mh_noise_draws": [P, L, L, U64, U64, P],
-    "mh_gemm_w4": [P, P, P, P, I, I, I, L, L, L],
     "mh_dropout_add": [P, P, P, L, F, U64, U64, P, I],
     "mh_dropout_lite": [P, P, P, L, F, U64, U64, P, I, I],
     "mh_timestamp": [P],
@@ -225,7 +224,7 @@ _SIGS = {
     "mh_infonce_rows_bwd": [P, L, P, P, P, I, F, F, I, I, P, P],
     "mh_infonce_fold": [P, P, P, P, I, P, P, I, I],
 }
-EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "mh_gemm_select_pp", "mh_gemm_variant_name", "mh_device_ok", "mh_nys_attn3_ws_floats", "mh_rna_block_workspace_bytes",
+EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "mh_gemm_variant_name", "mh_device_ok", "mh_nys_attn3_ws_floats", "mh_rna_block_workspace_bytes",
                                  "mh_gemm_workspace_bytes", "mh_layernorm_bwd_workspace_bytes", "mh_nys_attn3_workspace_bytes",
                                  "mh_pinv_chain_workspace_bytes", "mh_resconv_bwd_workspace_bytes", "mh_mask_apply_bwd_dbias_ok"])
 
@@ -234,7 +233,7 @@ _lib = None
 # The ABI generation this binding was written against (mh_version() of csrc/errors.cpp).  _SIGS above restates the argument lists of
 # include/mirror_hip.h by hand: a library built from another generation would be called with shifted arguments (a stream where a
 # counter belongs) and corrupt device memory silently, so load() refuses anything but this exact number.
-ABI_VERSION = 121
+ABI_VERSION = 122
 
 
 class MirrorHipError(RuntimeError):
@@ -263,8 +262,6 @@ def load() -> C.CDLL:
     lib.mh_exp_build.restype = C.c_int
     lib.mh_gemm_variant_name.restype = C.c_char_p
     lib.mh_gemm_variant_name.argtypes = []
-    lib.mh_gemm_select_pp.restype = C.c_int
-    lib.mh_gemm_select_pp.argtypes = [C.c_int]
     lib.mh_device_ok.restype = C.c_int
     lib.mh_nys_attn3_ws_floats.restype = C.c_int64
     lib.mh_nys_attn3_ws_floats.argtypes = [C.c_int, C.c_int, C.c_int]

@@ -1,17 +1,21 @@
-// Large-tile variant of the bf16 MFMA GEMM: 256 x 256 x 64 block tile, 512 threads = 8 waves (2 x 4), wave tile
-// 128 x 64 (4 x 2 MFMA blocks, 128 accumulator registers), two waves per SIMD.
+// Large-tile MFMA GEMM: 256 x 256 x 64 block tile, 512 threads = 8 waves (2 x 4), wave tile 128 x 64 (128 accumulator registers),
+// two waves per SIMD.
 //
 // Why: the projection / weight-gradient GEMMs of the step are long and thin (M = 69632, K = 512..1536).  With 128 x 128
 // tiles every MFMA flop pulls (BM + BN) / (BM BN) = 1/64 byte through L2 -> LDS, i.e. ~39 TB/s at the 2.5 PFLOP/s
-// peak — more than the fabric delivers; 256 x 256 tiles halve that, and halve the LDS fragment reads per MFMA as well
-// (6 fragment reads feed 8 MFMAs instead of 4 feeding 4).  Same staging scheme as gemm_kernel (global -> registers
-// one K-tile ahead -> double-buffered LDS, ds_read_b64_tr_b16 for K-strided operands), 144 KiB of LDS.
-// Used by gemm_launch_bf16 when N is a multiple of 256, K of 64, M a multiple of 256 (or ragged with K-contiguous A rows:
-// loads clamp to the last row, stores are guarded) and the operands are 16-byte aligned.
+// peak — more than the fabric delivers; 256 x 256 tiles halve that, and halve the LDS fragment reads per MFMA as well.
+//
+// Three main loops over that tile, one per kind of launch:
+//   gemm_pq_kernel   bf16 operands, direct-to-LDS staging, PERSISTENT (one workgroup per CU walks the units): the default.
+//   gemm_pp_kernel   the same staging, one workgroup per tile: launches with GemmArgs.shared_chip set (another stream's kernel
+//                    shares the chip), and the epilogue cases gemm_pq_kernel has no variant for (pq_variant() < 0: f32 atomics, ...).
+//   gemm_big_kernel  e4m3 operands (gemm_try_big_fp8) only: global -> registers one K-tile ahead -> double-buffered LDS, the staging
+//                    scheme of gemm_kernel, with the 32 x 32 x 64 f8f6f4 MFMA.
+// bf16 launches come from gemm_launch_bf16 (gemm_try_big_bf16: N a multiple of 256, K of 64, M a multiple of 256 or ragged with
+// K-contiguous A rows — loads clamp to the last row, stores are guarded — 16-byte aligned operands, at least 128 workgroups), from the
+// fused-epilogue launches (gemm_big_epi) and from the row-window launches (gemm_big_window).  Split-K reductions into one f32 C go
+// through bf16 partial tiles and fold_partials_kernel when the caller gave a workspace, through f32 atomics otherwise.
 #include "gemm_kernel.h"
-#ifndef GEMM_EXP
-#define GEMM_EXP 0
-#endif
 
 // the tail mh_gemm offers to the next fold launch (gemm_kernel.h: GemmTail); host-side state of the calling thread's launch sequence
 static thread_local GemmTail g_tail = {nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0.f};
@@ -227,7 +231,6 @@ __device__ __forceinline__ void epilogue_big_t(const GemmArgs& g, bf16_t* C, f32
                 o[w] = pack_bf2(a0, a1);
             }
         }
-        if (GEMM_EXP == 5) { if (o[0] == 0x12345678u) *reinterpret_cast<u32x4*>(dst) = o; continue; }
         __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(dst));      // pq_store_note
         if constexpr (EPI == MH_EPI_SQERR) {
             // masked squared error against the f32 target rows (losses/mirror_loss.py:98-103) on the bf16-rounded prediction
@@ -264,9 +267,10 @@ __device__ __forceinline__ void epilogue_big_t(const GemmArgs& g, bf16_t* C, f32
     }
 }
 
-// FP8 instance (BASELINE config 5): the operands are e4m3 bytes with K contiguous, described to the staging code as bf16 rows
-// of half the length (same 128-byte K-tile rows, same LDS image); a lane then owns 32 consecutive bytes of a 64-byte k-step
-// and the product is v_mfma_scale_f32_32x32x64_f8f6f4 (unit scales) — 16 instead of 32 MFMAs per K-tile at twice the K each.
+// gemm_big_kernel: the fp8 product (BASELINE config 5), register-staged.  The operands are e4m3 bytes with K contiguous, described
+// to the staging code as bf16 rows of half the length (128-byte K-tile rows); a lane then owns 32 consecutive bytes of a 64-byte
+// k-step and the product is v_mfma_scale_f32_32x32x64_f8f6f4 (unit scales): 16 MFMAs per K-tile.  One K-slice, no partial tiles,
+// no fused epilogue, no accumulate (gemm_try_big_fp8 refuses those); the batch is a batch of row windows (sA1 / sC1).
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4f __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ i32x8 f8_pair(bf16x8 lo, bf16x8 hi) {
@@ -274,54 +278,32 @@ __device__ __forceinline__ i32x8 f8_pair(bf16x8 lo, bf16x8 hi) {
     return i32x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 }
 
-// A tile load for the fused-epilogue instances: K-contiguous A whose M rows are row windows of larger batches (GemmArgs.a_rpb /
-// a_skip: `to_out(out)[:, -n:]`, `retention_head(x)[:, 1:]`): a 256-row tile crosses at most one batch boundary (a_rpb >= 256),
-// at local row `bnd`; rows past M re-read row M - 1 (their results are never stored).
-template <int NCH>
-__device__ __forceinline__ void load_a_window(u32x4 (&regs)[NCH], const bf16_t* __restrict__ base, long ld, int tile0, int dim, int k0,
-                                              int tid, int adj0, int bnd, int skip) {
-#pragma unroll
-    for (int i = 0; i < NCH; i++) {
-        const int cid = tid + i * NTB;
-        const int rl = min(tile0 + (cid >> 3), dim - 1) - tile0, c = cid & 7;
-        const int row = tile0 + rl + adj0 + (rl >= bnd ? skip : 0);
-        regs[i] = *reinterpret_cast<const u32x4*>(base + (long)row * ld + k0 + c * 8);
-    }
-}
-
-template <typename TC, bool AKC, bool BKC, bool FP8 = false, bool PART = false, int EPI = 0>
+template <typename TC>
 __global__ __launch_bounds__(NTB) void gemm_big_kernel(GemmArgs g) {
-    static_assert(!FP8 || (AKC && BKC), "fp8 operands are K-contiguous");
-    static_assert(EPI == 0 || (AKC && !FP8 && !PART), "fused epilogues: K-contiguous A, plain bf16 operands, no split-K");
-    using GA = TileGeom<1, AKC, BIG>;
-    using GB = TileGeom<1, BKC, BIG>;
+    using G = TileGeom<1, true, BIG>;
     constexpr int BK = 64;
-    constexpr int STAGE = GA::BYTES + GB::BYTES;
+    constexpr int STAGE = 2 * G::BYTES;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
     static_assert((BIG / 2) * (BIG + 4) * 4 <= 2 * STAGE, "epilogue half tile must fit the staging LDS");
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3;
-    // XCD-aware order over the WHOLE grid (tiles x K-slices x batches), not just over the tiles of one slice: workgroups are dealt
-    // round-robin over the 8 XCDs (private L2s), so linear id L runs on XCD L % 8; unit u = (L % 8) * (total / 8) + L / 8 gives
-    // each XCD a contiguous range of units, and unit -> (batch, K-slice, tile) with the tile fastest puts all M x N tiles of one
-    // K-slice on ONE XCD at about the same time: a weight-gradient slice's A and B panels are fetched from HBM once per XCD
-    // instead of once per tile (513 -> 260 MB per launch on the step's nine weight gradients).
-    const int tiles = gridDim.x, nwg = tiles * gridDim.y * gridDim.z;
-    const int lin = blockIdx.x + tiles * (blockIdx.y + gridDim.y * blockIdx.z);
+    // XCD-aware order over the WHOLE grid (tiles x K-slices x batches; this kernel has one K-slice), not just over the tiles of one
+    // slice: workgroups are dealt round-robin over the 8 XCDs (private L2s), so linear id L runs on XCD L % 8; unit u = (L % 8) *
+    // (total / 8) + L / 8 gives each XCD a contiguous range of units, and unit -> (batch, K-slice, tile) with the tile fastest puts all
+    // M x N tiles of one K-slice on ONE XCD at about the same time: a weight-gradient slice's A and B panels are fetched from HBM once
+    // per XCD instead of once per tile (513 -> 260 MB per launch on the step's nine weight gradients).
+    const int tiles = gridDim.x, nwg = tiles * gridDim.z;
+    const int lin = blockIdx.x + tiles * blockIdx.z;
     const int xcd = lin & 7, q8 = nwg >> 3, r8 = nwg & 7;
     const int unit = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (lin >> 3);
-    const int wgid = unit % tiles, slice = unit / tiles;
+    const int wgid = unit % tiles, z = unit / tiles;
     const int tile_m = wgid / g.tiles_n, tile_n = wgid % g.tiles_n;
-    const int z = slice / (int)gridDim.y;
     const int b1 = z / g.batch2, b2 = z % g.batch2;
     const bf16_t* A = reinterpret_cast<const bf16_t*>(g.A) + b1 * g.sA1 + b2 * g.sA2;
     const bf16_t* B = reinterpret_cast<const bf16_t*>(g.B) + b1 * g.sB1 + b2 * g.sB2;
     TC* C = reinterpret_cast<TC*>(g.C) + b1 * g.sC1 + b2 * g.sC2;
-    const int split = slice % (int)gridDim.y;
-    const int kbeg = split * g.k_per_split;
-    const int kend = min(g.K, kbeg + g.k_per_split);
-    const int nt = (kend - kbeg) / BK;
+    const int nt = g.K / BK;
 
     f32x16 acc[BWM][BWN];
 #pragma unroll
@@ -331,144 +313,62 @@ __global__ __launch_bounds__(NTB) void gemm_big_kernel(GemmArgs g) {
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
 
-    using SA = Stager<1, bf16_t, AKC, BIG, true, NTB>;
-    using SB = Stager<1, bf16_t, BKC, BIG, true, NTB>;
-    u32x4 ra[SA::NCH], rb[SB::NCH];
+    using S = Stager<1, bf16_t, true, BIG, true, NTB>;
+    u32x4 ra[S::NCH], rb[S::NCH];
     // One register set, written to LDS right AFTER the barrier that frees the other stage and re-issued at once: the
     // ds_write pass (~80 B/clk per CU, ~800 cycles per K-tile) then drains under the MFMAs of the current tile instead
-    // of sitting between the last MFMA and the barrier (8192^3: 732 -> 1094 TFLOP/s).
-    int adj0 = 0, bnd = 1 << 30;
-    if constexpr (AKC) {
-        if (g.a_rpb > 0) {
-            const int b0 = min((tile_m * BIG) / g.a_rpb, g.w_last);
-            adj0 = b0 * g.a_skip;
-            bnd = b0 < g.w_last ? (b0 + 1) * g.a_rpb - tile_m * BIG : (1 << 30);
-        }
-    }
-#define LOAD_A_(K0_)                                                                                         \
-    do {                                                                                                     \
-        if constexpr (EPI != 0) load_a_window<SA::NCH>(ra, A, g.lda, tile_m * BIG, g.M, K0_, tid, adj0, bnd, g.a_skip); \
-        else SA::load(ra, A, g.lda, tile_m * BIG, g.M, K0_, kend, true, tid);                                \
-    } while (0)
+    // of sitting between the last MFMA and the barrier.
     if (nt > 0) {
-        LOAD_A_(kbeg);
-        SB::load(rb, B, g.ldb, tile_n * BIG, g.N, kbeg, kend, true, tid);
-        SA::store(ra, smem, tid);
-        SB::store(rb, smem + GA::BYTES, tid);
+        S::load(ra, A, g.lda, tile_m * BIG, g.M, 0, g.K, true, tid);
+        S::load(rb, B, g.ldb, tile_n * BIG, g.N, 0, g.K, true, tid);
+        S::store(ra, smem, tid);
+        S::store(rb, smem + G::BYTES, tid);
         if (nt > 1) {
-            LOAD_A_(kbeg + BK);
-            SB::load(rb, B, g.ldb, tile_n * BIG, g.N, kbeg + BK, kend, true, tid);
+            S::load(ra, A, g.lda, tile_m * BIG, g.M, BK, g.K, true, tid);
+            S::load(rb, B, g.ldb, tile_n * BIG, g.N, BK, g.K, true, tid);
         }
     }
     __syncthreads();
     for (int t = 0; t < nt; t++) {
         const int cur = t & 1;
-#ifndef GEMM_EXP
-#define GEMM_EXP 0
-#endif
         if (t + 1 < nt) {
-            if (GEMM_EXP != 1 && GEMM_EXP != 3) {     // timing experiments (tools/exp/gemm_exp.cpp): 1 = no loads / stores, 3 = no LDS stores
-                SA::store(ra, smem + (cur ^ 1) * STAGE, tid);
-                SB::store(rb, smem + (cur ^ 1) * STAGE + GA::BYTES, tid);
-            }
-            if (t + 2 < nt && GEMM_EXP != 1) {
-                const int k0 = GEMM_EXP == 2 ? kbeg : kbeg + (t + 2) * BK;    // 2 = always the same K-tile (cache resident)
-                LOAD_A_(k0);
-                SB::load(rb, B, g.ldb, tile_n * BIG, g.N, k0, kend, true, tid);
+            S::store(ra, smem + (cur ^ 1) * STAGE, tid);
+            S::store(rb, smem + (cur ^ 1) * STAGE + G::BYTES, tid);
+            if (t + 2 < nt) {
+                S::load(ra, A, g.lda, tile_m * BIG, g.M, (t + 2) * BK, g.K, true, tid);
+                S::load(rb, B, g.ldb, tile_n * BIG, g.N, (t + 2) * BK, g.K, true, tid);
             }
         }
         const char* at = smem + cur * STAGE;
-        const char* bt = at + GA::BYTES;
-        if constexpr (FP8) {
+        const char* bt = at + G::BYTES;
 #pragma unroll
-            for (int s8 = 0; s8 < 2; s8++) {      // two 64-byte k-steps per 128-byte tile row; lane half hl owns bytes [32 hl, 32 hl + 32)
-                const int ks = 32 * s8 + 8 * (lane >> 5);      // in 2-byte units; frag_bf16 adds another 8 (lane >> 5)
-                i32x8 af[BWM], bfr[BWN];
+        for (int s8 = 0; s8 < 2; s8++) {      // two 64-byte k-steps per 128-byte tile row; lane half hl owns bytes [32 hl, 32 hl + 32)
+            const int ks = 32 * s8 + 8 * (lane >> 5);      // in 2-byte units; frag_bf16 adds another 8 (lane >> 5)
+            i32x8 af[BWM], bfr[BWN];
 #pragma unroll
-                for (int i = 0; i < BWM; i++)
-                    af[i] = f8_pair(frag_bf16<true, BIG>(at, wm * BWM * 32 + i * 32, ks, lane), frag_bf16<true, BIG>(at, wm * BWM * 32 + i * 32, ks + 8, lane));
+            for (int i = 0; i < BWM; i++)
+                af[i] = f8_pair(frag_bf16<true, BIG>(at, wm * BWM * 32 + i * 32, ks, lane), frag_bf16<true, BIG>(at, wm * BWM * 32 + i * 32, ks + 8, lane));
 #pragma unroll
-                for (int j = 0; j < BWN; j++)
-                    bfr[j] = f8_pair(frag_bf16<true, BIG>(bt, wn * BWN * 32 + j * 32, ks, lane), frag_bf16<true, BIG>(bt, wn * BWN * 32 + j * 32, ks + 8, lane));
-#pragma unroll
-                for (int i = 0; i < BWM; i++)
-#pragma unroll
-                    for (int j = 0; j < BWN; j++) {
-                        if constexpr (sizeof(TC) == 2) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bfr[j], af[i], acc[i][j], 0, 0, 0, 127, 0, 127);   // C^T
-                        else acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af[i], bfr[j], acc[i][j], 0, 0, 0, 127, 0, 127);
-                    }
-            }
-        } else {
-#pragma unroll
-        for (int ks = 0; ks < BK; ks += 16) {
-            bf16x8 af[BWM], bfr[BWN];
-#pragma unroll
-            for (int i = 0; i < BWM; i++) af[i] = frag_bf16<AKC, BIG>(at, wm * BWM * 32 + i * 32, ks, lane);
-#pragma unroll
-            for (int j = 0; j < BWN; j++) bfr[j] = frag_bf16<BKC, BIG>(bt, wn * BWN * 32 + j * 32, ks, lane);
+            for (int j = 0; j < BWN; j++)
+                bfr[j] = f8_pair(frag_bf16<true, BIG>(bt, wn * BWN * 32 + j * 32, ks, lane), frag_bf16<true, BIG>(bt, wn * BWN * 32 + j * 32, ks + 8, lane));
 #pragma unroll
             for (int i = 0; i < BWM; i++)
 #pragma unroll
                 for (int j = 0; j < BWN; j++) {
-                    if constexpr (sizeof(TC) == 2) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);   // C^T
-                    else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+                    if constexpr (sizeof(TC) == 2) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bfr[j], af[i], acc[i][j], 0, 0, 0, 127, 0, 127);   // C^T
+                    else acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af[i], bfr[j], acc[i][j], 0, 0, 0, 127, 0, 127);
                 }
-        }
         }
         __syncthreads();
     }
-#undef LOAD_A_
-    if constexpr (EPI != 0) {
-        if constexpr (sizeof(TC) == 2) epilogue_big_t<0, EPI>(g, C, acc, smem, tile_m * BIG, tile_n * BIG, wm, wn, lane, tid, true, g.alpha);
-        else epilogue_big<TC, 0, EPI>(g, C, acc, smem, tile_m * BIG, tile_n * BIG, wm, wn, lane, tid, true, g.ldc, g.alpha);
-        return;
-    }
-    if constexpr (FP8) {      // per-tensor dequantisation factors live on the device: fold them into alpha
-        const float a8 = g.alpha * g.scale_a[0] * g.scale_b[0];
-        if constexpr (sizeof(TC) == 2) epilogue_big_t<0>(g, C, acc, smem, tile_m * BIG, tile_n * BIG, wm, wn, lane, tid, true, a8);
-        else epilogue_big<TC, 0>(g, C, acc, smem, tile_m * BIG, tile_n * BIG, wm, wn, lane, tid, true, g.ldc, a8);
-        return;
-    }
-    if (GEMM_EXP == 4) {
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < BWM; i++)
-#pragma unroll
-            for (int j = 0; j < BWN; j++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) ss += acc[i][j][r];
-        if (ss == 123.456f) C[0] = (TC)0;
-        return;
-    }
-    const bool lead = (split == 0);
-    if constexpr (sizeof(TC) == 2) {      // bf16 C is never an atomic target (mh_gemm requires f32 for split-K)
-        if (g.accumulate) epilogue_big_t<1>(g, C, acc, smem, tile_m * BIG, tile_n * BIG, wm, wn, lane, tid, lead, g.alpha);
-        else epilogue_big_t<0>(g, C, acc, smem, tile_m * BIG, tile_n * BIG, wm, wn, lane, tid, lead, g.alpha);
-        return;
-    }
-    if constexpr (PART) {
-        // partial tile -> workspace [part][M][N] with plain 16-byte stores (part = z * splits + split); 16.7 M same-matrix
-        // f32 atomics of a 64-way split cost more than the whole K loop, a fold pass over the partials does not.  (Its own
-        // instance: with three epilogues inlined into one kernel the compiler spilled in the f32 instances.)
-        if constexpr (sizeof(TC) == 4) {      // partial tiles are stored as bf16 (see fold_partials_kernel)
-            bf16_t* P = reinterpret_cast<bf16_t*>(g.ws) + ((long)z * gridDim.y + split) * (long)g.M * g.N;
-            epilogue_big<bf16_t, 0>(g, P, acc, smem, tile_m * BIG, tile_n * BIG, wm, wn, lane, tid, false, (long)g.N, g.alpha);
-        }
-        return;
-    }
-    if (g.atomic) {
-        if constexpr (sizeof(TC) == 4)
-            epilogue_atomic_big(g, C, acc, tile_m * BIG + wm * BWM * 32, tile_n * BIG + wn * BWN * 32, lane);
-    } else if (g.accumulate) {
-        epilogue_big<TC, 1>(g, C, acc, smem, tile_m * BIG, tile_n * BIG, wm, wn, lane, tid, lead, g.ldc, g.alpha);
-    } else {
-        epilogue_big<TC, 0>(g, C, acc, smem, tile_m * BIG, tile_n * BIG, wm, wn, lane, tid, lead, g.ldc, g.alpha);
-    }
+    const float a8 = g.alpha * g.scale_a[0] * g.scale_b[0];      // per-tensor dequantisation factors live on the device: fold them into alpha
+    if constexpr (sizeof(TC) == 2) epilogue_big_t<0>(g, C, acc, smem, tile_m * BIG, tile_n * BIG, wm, wn, lane, tid, true, a8);
+    else epilogue_big<TC, 0>(g, C, acc, smem, tile_m * BIG, tile_n * BIG, wm, wn, lane, tid, true, g.ldc, a8);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// gemm_pp_kernel: the same 256 x 256 x 64 tile and wave grid, a different main loop (cdna_hip_programming.md §5: direct-to-LDS
-// staging, counted waits, raw barriers, the two wave rows in ping-pong).
+// gemm_pp_kernel: bf16 operands, one workgroup per tile (when it runs: see the head of this file).  Main loop after
+// cdna_hip_programming.md §5: direct-to-LDS staging, counted waits, raw barriers, the two wave rows in ping-pong.
 //   * staging: global_load_lds_dwordx4 (1 KiB per wave instruction, no staging registers, no ds_write pass).  The LDS images are
 //     lane-linear, the bank swizzle sits in the per-lane SOURCE address and in the fragment reads (rule 21):
 //       K-contiguous operand: [256 rows][128 B], 16-byte chunk c of row r stored at chunk c ^ ((r >> 1) & 7)  -> ds_read_b128 conflict free
@@ -478,7 +378,8 @@ __global__ __launch_bounds__(NTB) void gemm_big_kernel(GemmArgs g) {
 //   * a k-step = LOAD segment (6 fragment reads, the stage requests) | barrier | COMPUTE segment (8 MFMAs) | barrier; waves 4-7 run
 //     one barrier behind waves 0-3, so on every SIMD one wave computes while its partner loads (the matrix pipe is never left idle
 //     by the fragment reads, and the two groups' LDS bursts do not collide).
-// Epilogues, XCD order, split-K partials and the fused epilogues are gemm_big_kernel's.
+// Its epilogues are epilogue_big / epilogue_big_t / epilogue_atomic_big above (shared with gemm_big_kernel), with the fused epilogues
+// (EPI) and the split-K partial tiles (PART) as template cases; its unit order over the XCDs is the one gemm_big_kernel describes.
 constexpr int PP_OP = BIG * 64 * 2;          // bytes of one operand tile image
 constexpr int PP_STAGE = 2 * PP_OP;
 constexpr int PP_LDS = 136 * 1024;           // 2 stages (128 KiB); the epilogue images (133120 B + reduction scratch) reuse them
@@ -1336,120 +1237,6 @@ static void launch_fold(const float* ws_, int parts, long mn, float* C, long ldc
 #undef FOLD_
 }
 
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// gemm_w4_kernel (round 5 experiment, verdict item 4 "GEMM structure"): the same 256 x 256 x 64 tile on FOUR waves, one per SIMD, each
-// owning a 128 x 128 part (8 x 8 blocks of 16 x 16: 256 accumulator registers).  Per k-half a wave reads 16 fragments for 64 MFMAs (the
-// 8-wave kernels: 12 for 32): a K-tile is 32 ds_read_b128 and then 128 MFMAs back to back on AGPR accumulators, one barrier per K-tile.
-// K-contiguous A and B, bf16 C, alpha = 1, optional bias; whole tiles only; one workgroup per tile, two stages.
-// MEASURED (profiles/r05_l_gemm_four_wave_experiment.txt): bit-equal to mh_gemm, 0.78-0.81 x the persistent 8-wave kernel's rate (633-801
-// vs 780-1031 TF/s on the step's forward shapes).  What it lacks is everything around the K loop that the persistent kernel has (the
-// pipeline across tiles, stores draining under the next tile's loop) plus a prefetch deeper than one K-tile — its K-tile lasts half
-// as long, so one tile ahead no longer covers the L2 latency (without steady-state requests it runs at 786 TF/s at K = 512) — and the
-// fragment reads interleaved with the MFMAs: the first form, with the next k-half's reads in front of the current MFMAs, made the
-// compiler wait for lgkmcnt(0) anyway and shuffle 900 v_accvgpr copies through the loop (549-672 TF/s).  Not on the product path.
-constexpr int W4_NT = 256, W4_QM = 8, W4_QN = 8;
-constexpr int W4_STAGE = 4 * P2_SUB;                       // A_k0 | A_k1 | B_k0 | B_k1
-constexpr int W4_CPITCH = 128 + 8;                         // bf16 elements per staged C row of a wave's 128 x 128 part
-constexpr int W4_LDS = 4 * 128 * W4_CPITCH * 2;            // 139264 B: the C staging (4 waves) is larger than the two stages (131072)
-__global__ __launch_bounds__(W4_NT) void gemm_w4_kernel(GemmArgs g) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    // XCD-aware tile order: workgroups of one launch run on XCD blockIdx.x % 8; consecutive tiles of an XCD share their A rows
-    const int tiles = g.tiles_m * g.tiles_n;
-    const int q8 = tiles >> 3, r8 = tiles & 7, xcd = blockIdx.x & 7;
-    const int unit = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-    const int tile_m = unit / g.tiles_n, tile_n = unit % g.tiles_n;
-    const bf16_t* A = reinterpret_cast<const bf16_t*>(g.A);
-    const bf16_t* B = reinterpret_cast<const bf16_t*>(g.B);
-    // each wave requests the pieces the 8-wave layout gives waves w and w + 4
-    P2Stage<true> sa0, sa1, sb0, sb1;
-    sa0.init(A, g.lda, tile_m * BIG, g.M, 0, wave, lane, 0, 1 << 30, 0);
-    sa1.init(A, g.lda, tile_m * BIG, g.M, 0, wave + 4, lane, 0, 1 << 30, 0);
-    sb0.init(B, g.ldb, tile_n * BIG, g.N, 0, wave, lane, 0, 1 << 30, 0);
-    sb1.init(B, g.ldb, tile_n * BIG, g.N, 0, wave + 4, lane, 0, 1 << 30, 0);
-    auto request = [&](char* st, int t) {
-#pragma unroll
-        for (int kh = 0; kh < 2; kh++) {
-            sa0.issue(st + kh * P2_SUB, wave, t, kh);
-            sa1.issue(st + kh * P2_SUB, wave + 4, t, kh);
-            sb0.issue(st + (2 + kh) * P2_SUB, wave, t, kh);
-            sb1.issue(st + (2 + kh) * P2_SUB, wave + 4, t, kh);
-        }
-    };
-    const unsigned offa = q_kc_off(wm * 128, lane), offb = q_kc_off(wn * 128, lane);
-    const int nt = g.K / 64;
-    request(smem, 0);
-    f32x4 acc[W4_QM][W4_QN];
-#pragma unroll
-    for (int i = 0; i < W4_QM; i++)
-#pragma unroll
-        for (int j = 0; j < W4_QN; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-    for (int t = 0; t < nt; t++) {
-        const char* cur = smem + (t & 1) * W4_STAGE;
-        char* nxt = smem + ((t + 1) & 1) * W4_STAGE;
-        // stage t has landed for everybody, and everybody has read stage t - 1 (the other buffer) into registers: refill it
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (t + 1 < nt) request(nxt, t + 1);
-        bf16x8 fa[2][W4_QM], fb[2][W4_QN];
-#pragma unroll
-        for (int kh = 0; kh < 2; kh++) {
-#pragma unroll
-            for (int i = 0; i < W4_QM; i++) fa[kh][i] = q_frag_kc(cur + kh * P2_SUB, offa, i);
-#pragma unroll
-            for (int j = 0; j < W4_QN; j++) fb[kh][j] = q_frag_kc(cur + (2 + kh) * P2_SUB, offb, j);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int kh = 0; kh < 2; kh++)
-#pragma unroll
-            for (int i = 0; i < W4_QM; i++)
-#pragma unroll
-                for (int j = 0; j < W4_QN; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kh][j], fa[kh][i], acc[i][j], 0, 0, 0);   // C^T
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    // ---- epilogue: C^T accumulators (lane: row 16 i + (l & 15), columns 16 j + 4 (l >> 4) .. + 3) -> the wave's own LDS part -> 16-byte
-    // row-contiguous stores
-    __syncthreads();
-    bf16_t* cw = reinterpret_cast<bf16_t*>(smem) + wave * 128 * W4_CPITCH;
-    const int c16 = lane & 15, g4 = lane >> 4;
-#pragma unroll
-    for (int j = 0; j < W4_QN; j++) {
-        f32x4 bq = {0.f, 0.f, 0.f, 0.f};
-        if (g.bias) bq = *reinterpret_cast<const f32x4*>(g.bias + tile_n * BIG + wn * 128 + 16 * j + 4 * g4);
-#pragma unroll
-        for (int i = 0; i < W4_QM; i++) {
-            const f32x4 v = acc[i][j] + bq;
-            u32x2 w = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
-            *reinterpret_cast<u32x2*>(cw + (16 * i + c16) * W4_CPITCH + 16 * j + 4 * g4) = w;
-        }
-    }
-    // (a wave reads back only what it wrote: no barrier)
-    bf16_t* C = reinterpret_cast<bf16_t*>(g.C);
-    const int rr = lane >> 4, cc = lane & 15;             // 4 rows x 16 chunks of 16 bytes per wave-instruction
-#pragma unroll 4
-    for (int r = 0; r < 128; r += 4) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(cw + (r + rr) * W4_CPITCH + 8 * cc);
-        const long row = (long)tile_m * BIG + wm * 128 + r + rr;
-        __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(C + row * g.ldc + tile_n * BIG + wn * 128 + 8 * cc));
-    }
-}
-
-// MH_GEMM_PP=0 keeps every launch on gemm_big_kernel (A/B switch; default: the ping-pong kernel)
-// which main loop the 256 x 256-tile launches use: 0 = gemm_big_kernel (register staging), 1 = gemm_pp_kernel (direct-to-LDS,
-// ping-pong), 2 = gemm_pq_kernel (the same, persistent: default).  env MH_GEMM_PP = 0 / 1 / 2, or mh_gemm_select_pp().
-static int g_pp = -1;
-static int pp_mode() {
-    if (g_pp < 0) { const char* e = getenv("MH_GEMM_PP"); g_pp = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2; }
-    return g_pp;
-}
-static bool pp_enabled() { return pp_mode() != 0; }
 static int pq_grid(long units) {
     static const int cus = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
     return (int)(units < cus ? units : cus);
@@ -1479,7 +1266,7 @@ static void pp_attr(K kern) {
 #define PP_LAUNCH_(TC, AKC, BKC, PART, EPI, grid, s, a)                                              \
     do {                                                                                             \
         const int var_ = pq_variant(a, sizeof(TC) == 2, PART, EPI);                                  \
-        const bool pq_ = pp_mode() == 2 && !(a).shared_chip && var_ >= 0;                            \
+        const bool pq_ = !(a).shared_chip && var_ >= 0;                                              \
         gemm_note_variant("%s<%s,%s,%s%s%s>", pq_ ? "gemm_pq_kernel" : "gemm_pp_kernel", gemm_tn<TC>(), \
                           gemm_tf(AKC), gemm_tf(BKC), (PART) ? ",part" : "", (EPI) == 0 ? "" : ((EPI) == 1 ? ",epi1" : ((EPI) == 2 ? ",epi2" : ",epi3"))); \
         if (pq_) {                                                                                   \
@@ -1499,77 +1286,30 @@ void launch_big(GemmArgs& a, int akc, int bkc, int batch, hipStream_t s) {
     a.tiles_m = (a.M + BIG - 1) / BIG;     // a ragged last row tile is allowed when A rows are K-contiguous
     a.tiles_n = a.N / BIG;
     dim3 grid(a.tiles_m * a.tiles_n, a.split_k, batch);
-    if (pp_enabled()) {
-        const long parts_ = (long)a.split_k * batch, mn_ = (long)a.M * a.N;
-        const bool partial_ = a.atomic && a.ws && a.M % BIG == 0 && a.ws_floats * 2 >= parts_ * mn_ && ((uintptr_t)a.ws & 15) == 0 && a.vecC &&
-                              a.sC1 == 0 && a.sC2 == 0 && parts_ >= 8;
-        if (!partial_) a.ws = nullptr;
-#define PP_DISPATCH_(PART)                                                                 \
-        do {                                                                               \
-            if (akc && bkc) PP_LAUNCH_(TC, true, true, PART, 0, grid, s, a);               \
-            else if (akc) PP_LAUNCH_(TC, true, false, PART, 0, grid, s, a);                \
-            else if (bkc) PP_LAUNCH_(TC, false, true, PART, 0, grid, s, a);                \
-            else PP_LAUNCH_(TC, false, false, PART, 0, grid, s, a);                        \
-        } while (0)
-        if constexpr (sizeof(TC) == 4) {
-            if (partial_) {
-                PP_DISPATCH_(true);
-                launch_fold((const float*)a.ws, (int)parts_, mn_, (float*)a.C, (long)a.ldc, a.N, s);
-                return;
-            }
-        }
-        PP_DISPATCH_(false);
-#undef PP_DISPATCH_
-        return;
-    }
     // reduction into one C: partial tiles in the caller's workspace when it is large enough, f32 atomics otherwise
-    gemm_note_variant("gemm_big_kernel<%s,%s,%s>", gemm_tn<TC>(), gemm_tf(akc), gemm_tf(bkc));
     const long parts = (long)a.split_k * batch, mn = (long)a.M * a.N;
     const bool partial = a.atomic && a.ws && a.M % BIG == 0 && a.ws_floats * 2 >= parts * mn && ((uintptr_t)a.ws & 15) == 0 && a.vecC &&
                          a.sC1 == 0 && a.sC2 == 0 && parts >= 8;
     if (!partial) a.ws = nullptr;
+#define PP_DISPATCH_(PART)                                                             \
+    do {                                                                               \
+        if (akc && bkc) PP_LAUNCH_(TC, true, true, PART, 0, grid, s, a);               \
+        else if (akc) PP_LAUNCH_(TC, true, false, PART, 0, grid, s, a);                \
+        else if (bkc) PP_LAUNCH_(TC, false, true, PART, 0, grid, s, a);                \
+        else PP_LAUNCH_(TC, false, false, PART, 0, grid, s, a);                        \
+    } while (0)
     if constexpr (sizeof(TC) == 4) {
         if (partial) {
-            if (akc && bkc) hipLaunchKernelGGL((gemm_big_kernel<TC, true, true, false, true>), grid, dim3(NTB), 0, s, a);
-            else if (akc) hipLaunchKernelGGL((gemm_big_kernel<TC, true, false, false, true>), grid, dim3(NTB), 0, s, a);
-            else if (bkc) hipLaunchKernelGGL((gemm_big_kernel<TC, false, true, false, true>), grid, dim3(NTB), 0, s, a);
-            else hipLaunchKernelGGL((gemm_big_kernel<TC, false, false, false, true>), grid, dim3(NTB), 0, s, a);
+            PP_DISPATCH_(true);
             launch_fold((const float*)a.ws, (int)parts, mn, (float*)a.C, (long)a.ldc, a.N, s);
             return;
         }
     }
-    if (akc && bkc) hipLaunchKernelGGL((gemm_big_kernel<TC, true, true>), grid, dim3(NTB), 0, s, a);
-    else if (akc) hipLaunchKernelGGL((gemm_big_kernel<TC, true, false>), grid, dim3(NTB), 0, s, a);
-    else if (bkc) hipLaunchKernelGGL((gemm_big_kernel<TC, false, true>), grid, dim3(NTB), 0, s, a);
-    else hipLaunchKernelGGL((gemm_big_kernel<TC, false, false>), grid, dim3(NTB), 0, s, a);
+    PP_DISPATCH_(false);
+#undef PP_DISPATCH_
 }
 
 }  // namespace
-
-
-// experiment entry (round 5): C bf16 [M, N] = A [M, K] B^T ([N, K] weights) + bias on the 4-wave kernel; M, N % 256 == 0, K % 64 == 0
-extern "C" int mh_gemm_w4(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
-                          mh_stream s) {
-    MH_REQUIRE(M > 0 && M % BIG == 0 && N % BIG == 0 && K % 64 == 0 && K >= 64 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 &&
-                   (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0),
-               "mh_gemm_w4: whole 256 x 256 x 64 tiles and 16-byte aligned rows (M=%d N=%d K=%d)", M, N, K);
-    GemmArgs a{};
-    a.A = A; a.B = B; a.C = C; a.bias = bias; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
-    a.tiles_m = M / BIG; a.tiles_n = N / BIG; a.alpha = 1.f;
-    static const bool attr = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_w4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS), true);
-    (void)attr;
-    hipLaunchKernelGGL(gemm_w4_kernel, dim3(a.tiles_m * a.tiles_n), dim3(W4_NT), W4_LDS, (hipStream_t)s, a);
-    MH_LAUNCH_CHECK("mh_gemm_w4");
-    return MH_OK;
-}
-
-// tuning switch (tools/bench_gemm_pp.py A/B in one process): 2 = persistent ping-pong kernel (default), 1 = ping-pong kernel,
-// 0 = gemm_big_kernel; returns the old value
-extern "C" int mh_gemm_select_pp(int mode) {
-    const int old = pp_mode();
-    if (mode >= 0) g_pp = mode > 2 ? 2 : mode;          // mode < 0: query only
-    return old;
-}
 
 // e4m3 operands (K contiguous, described in 2-byte units: K, lda, ldb, strides are HALF the byte counts): true when taken
 bool gemm_try_big_fp8(GemmArgs& a, int dtC, int batch, hipStream_t s) {
@@ -1580,8 +1320,8 @@ bool gemm_try_big_fp8(GemmArgs& a, int dtC, int batch, hipStream_t s) {
     a.tiles_n = a.N / BIG;
     dim3 grid(a.tiles_m * a.tiles_n, 1, batch);
     gemm_note_variant("gemm_big_kernel<%s,true,true,fp8>", dtC == MH_BF16 ? "bf16" : "float");
-    if (dtC == MH_BF16) hipLaunchKernelGGL((gemm_big_kernel<bf16_t, true, true, true>), grid, dim3(NTB), 0, s, a);
-    else hipLaunchKernelGGL((gemm_big_kernel<float, true, true, true>), grid, dim3(NTB), 0, s, a);
+    if (dtC == MH_BF16) hipLaunchKernelGGL((gemm_big_kernel<bf16_t>), grid, dim3(NTB), 0, s, a);
+    else hipLaunchKernelGGL((gemm_big_kernel<float>), grid, dim3(NTB), 0, s, a);
     return true;
 }
 
@@ -1597,9 +1337,7 @@ const char* gemm_big_epi(GemmArgs& a, int akc, int bkc, int dtC, int batch, hipS
     a.tiles_n = a.N / BIG;
     dim3 grid(a.tiles_m * a.tiles_n, 1, 1);
 #define EPI_LAUNCH_(TC, EPI) \
-    do { if (pp_enabled()) { if (bkc) PP_LAUNCH_(TC, true, true, false, EPI, grid, s, a); else PP_LAUNCH_(TC, true, false, false, EPI, grid, s, a); } \
-         else if (bkc) hipLaunchKernelGGL((gemm_big_kernel<TC, true, true, false, false, EPI>), grid, dim3(NTB), 0, s, a); \
-         else hipLaunchKernelGGL((gemm_big_kernel<TC, true, false, false, false, EPI>), grid, dim3(NTB), 0, s, a); } while (0)
+    do { if (bkc) PP_LAUNCH_(TC, true, true, false, EPI, grid, s, a); else PP_LAUNCH_(TC, true, false, false, EPI, grid, s, a); } while (0)
     switch (e.kind) {
     case MH_EPI_DROPADD:
         if (dtC != MH_F32 || !e.resid || !(e.p >= 0.f && e.p < 1.f) || (e.offset & 7) || ((uintptr_t)e.resid & 15)) return "DROPADD: f32 C, a 16-byte aligned residual, 0 <= p < 1, offset % 8 == 0";
@@ -1622,9 +1360,8 @@ const char* gemm_big_epi(GemmArgs& a, int akc, int bkc, int dtC, int batch, hipS
 }
 
 // plain bf16 product whose A and / or C rows are row windows of larger batches (mh_gemm_desc.a_rows_per_batch / c_rows_per_batch):
-// 0 = launched, otherwise why not.  Only the direct-to-LDS kernels take row windows without a fused epilogue.
+// 0 = launched, otherwise why not
 const char* gemm_big_window(GemmArgs& a, int akc, int bkc, int batch, hipStream_t s) {
-    if (!pp_enabled()) return "row windows without an epilogue need the direct-to-LDS kernels (MH_GEMM_PP != 0)";
     if (!(akc && a.M > BIG && a.M % BIG == 0 && a.N % BIG == 0 && a.K % 64 == 0 && a.split_k == 1 && a.k_per_split == a.K && !a.atomic && !a.accumulate &&
           !a.R && a.diag == 0.f && a.vecA && a.vecB && a.vecC && batch == 1))
         return "shape is not on the 256 x 256 kernel (K-contiguous bf16 A, M % 256 == 0, N % 256 == 0, K % 64 == 0, one batch, no split-K / accumulate / R / diag)";

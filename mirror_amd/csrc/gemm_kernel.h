@@ -50,14 +50,14 @@ struct GemmArgs {
     int tiles_m, tiles_n;
     int vecC;    // C rows are 16-B aligned (LDS-staged wide-store epilogue allowed)
     const void* R; float rcoef;   // optional addend rcoef * R, R laid out exactly like C (same dtype and strides)
-    float* ws; long ws_floats;    // split-K partial tiles go here instead of f32 atomics (gemm_big.hip), then a fold pass
-    const float* scale_a; const float* scale_b;   // fp8 operands (gemm_big.hip FP8 instance): alpha *= scale_a[0] * scale_b[0]
+    float* ws; long ws_floats;    // split-K partial tiles go here instead of f32 atomics (gemm_pp_kernel / gemm_pq_kernel), then a fold pass
+    const float* scale_a; const float* scale_b;   // fp8 operands (gemm_big.hip: gemm_big_kernel): alpha *= scale_a[0] * scale_b[0]
     int row_softmax;              // gemm_tile.hip, N == 384, bf16 C: C = softmax over each row of alpha * A B (the whole row is in one tile)
     int kseg; long sAk, sBk;      // C = sum over kseg operand pairs (A + s sAk, B + s sBk), K each (gemm_tile.hip only; 0 / 1: one pair)
-    mh_gemm_epi epi;              // fused epilogue (gemm_big.hip only; kind 0: none)
-    int a_rpb, a_skip;            // row-window remap of A (gemm_big.hip, K-contiguous A): flat row r -> r + (r / a_rpb) * a_skip
+    mh_gemm_epi epi;              // fused epilogue (gemm_big.hip: gemm_pp_kernel / gemm_pq_kernel; kind 0: none)
+    int a_rpb, a_skip;            // row-window remap of A (gemm_pp_kernel / gemm_pq_kernel, K-contiguous A): flat row r -> r + (r / a_rpb) * a_skip
     int shared_chip;              // mh_gemm_desc.shared_chip: no persistent kernel
-    int c_rpb, c_skip;            // row-window remap of C (gemm_big.hip, bf16 C): flat row r -> r + (r / c_rpb) * c_skip
+    int c_rpb, c_skip;            // row-window remap of C (gemm_pp_kernel / gemm_pq_kernel, bf16 C): flat row r -> r + (r / c_rpb) * c_skip
     int w_last;                   // index of the last row window (mh_gemm_desc.window_batches - 1; 1 << 30: unlimited): rows past it follow it
 };
 

@@ -70,6 +70,15 @@ def _mat(t: torch.Tensor):
     return t, rowmajor, ld, (st[0] if b1 > 1 else 0), (st[1] if b2 > 1 else 0)
 
 
+def _launch_gemm(d: GemmDesc) -> None:
+    """mh_gemm on the current stream, through the profiler when one is installed."""
+    prof = gemm_profiler
+    if prof is None:
+        _lib.call("mh_gemm", C.byref(d), stream=_stream())
+    else:
+        prof.launch(d, lambda: _lib.call("mh_gemm", C.byref(d), stream=_stream()))
+
+
 def gemm(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, *, alpha: float = 1.0,
          diag: float = 0.0, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, accumulate: bool = False,
          split_k: int = 1, mma: int = MH_F32, out_dtype: Optional[torch.dtype] = None,
@@ -165,11 +174,7 @@ def gemm(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, *
         ws = torch.empty((wsb // 4,), device=a.device, dtype=torch.float32)
         d.workspace, d.workspace_floats = ws.data_ptr(), ws.numel()
     d.shared_chip = int(shared_chip)
-    prof = gemm_profiler
-    if prof is None:
-        _lib.call("mh_gemm", C.byref(d), stream=_stream())
-    else:
-        prof.launch(d, lambda: _lib.call("mh_gemm", C.byref(d), stream=_stream()))
+    _launch_gemm(d)
     return out
 
 
@@ -224,12 +229,17 @@ def linear_fused(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
     if R != T and Bn > 1:
         d.a_rows_per_batch, d.a_row_skip = R, T - R
     d.epi = C.pointer(epi)
-    prof = gemm_profiler
-    if prof is None:
-        _lib.call("mh_gemm", C.byref(d), stream=_stream())
-    else:
-        prof.launch(d, lambda: _lib.call("mh_gemm", C.byref(d), stream=_stream()))
+    _launch_gemm(d)
     return out
+
+
+def _weight_view_ld(b2: torch.Tensor, who: str) -> tuple:
+    """(ldb, b_kc) of a 2-D weight view [K, N]."""
+    if b2.stride(0) == 1:            # W^T of a row-major [N, K] weight: contraction index contiguous
+        return b2.stride(1), 1
+    if b2.stride(1) == 1:            # row-major [K, N]
+        return b2.stride(0), 0
+    raise MirrorHipError(f"{who}: the weight view must have a unit stride")
 
 
 def gemm_rows_window(a3: torch.Tensor, b2: torch.Tensor, out3: torch.Tensor, r0: int, R: int, m_rows: Optional[int] = None,
@@ -253,12 +263,7 @@ def gemm_rows_window(a3: torch.Tensor, b2: torch.Tensor, out3: torch.Tensor, r0:
     d.A, d.B, d.C, d.bias = a3.data_ptr() + a_r0 * a3.stride(1) * 2, b2.data_ptr(), out3.data_ptr() + r0 * out3.stride(1) * 2, None
     d.M, d.N, d.K = (Bn * R if m_rows is None else int(m_rows)), N, Kd
     d.lda, d.ldc = a3.stride(1), out3.stride(1)
-    if b2.stride(0) == 1:            # W^T of a row-major [N, K] weight: contraction index contiguous
-        d.ldb, d.b_kc = b2.stride(1), 1
-    elif b2.stride(1) == 1:          # row-major [K, N]
-        d.ldb, d.b_kc = b2.stride(0), 0
-    else:
-        raise MirrorHipError("gemm_rows_window: the weight view must have a unit stride")
+    d.ldb, d.b_kc = _weight_view_ld(b2, "gemm_rows_window")
     d.a_kc = 1
     d.dtA, d.dtB, d.dtC, d.mma = MH_BF16, MH_BF16, MH_BF16, MH_BF16
     d.batch1 = d.batch2 = 1
@@ -269,11 +274,7 @@ def gemm_rows_window(a3: torch.Tensor, b2: torch.Tensor, out3: torch.Tensor, r0:
         if R != T:
             d.c_rows_per_batch, d.c_row_skip = R, T - R
     d.shared_chip = 1 if shared_chip else 0
-    prof = gemm_profiler
-    if prof is None:
-        _lib.call("mh_gemm", C.byref(d), stream=_stream())
-    else:
-        prof.launch(d, lambda: _lib.call("mh_gemm", C.byref(d), stream=_stream()))
+    _launch_gemm(d)
 
 
 def gemm_rows_ext_ok(Bn: int, T: int, r0: int, R: int, extra: int, Kd: int, N: int, a2: torch.Tensor, out2: torch.Tensor) -> bool:
@@ -283,8 +284,7 @@ def gemm_rows_ext_ok(Bn: int, T: int, r0: int, R: int, extra: int, Kd: int, N: i
     return (a2.dim() == 2 and out2.dim() == 2 and a2.dtype == bf and out2.dtype == bf and a2.is_cuda and R >= 256 and M > 512 and 0 <= extra < R
             and r0 + R == T and M % 256 <= extra
             and N % 256 == 0 and Kd % 64 == 0 and a2.stride(1) == 1 and out2.stride(1) == 1 and a2.stride(0) % 8 == 0 and out2.stride(0) % 8 == 0
-            and a2.data_ptr() % 16 == 0 and out2.data_ptr() % 16 == 0 and a2.shape[0] == Bn * T + extra and out2.shape[0] == Bn * T + extra
-            and int(_lib.load().mh_gemm_select_pp(-1)) != 0)
+            and a2.data_ptr() % 16 == 0 and out2.data_ptr() % 16 == 0 and a2.shape[0] == Bn * T + extra and out2.shape[0] == Bn * T + extra)
 
 
 def gemm_rows_ext(a2: torch.Tensor, b2: torch.Tensor, out2: torch.Tensor, Bn: int, T: int, r0: int, R: int, extra: int) -> int:
@@ -304,12 +304,7 @@ def gemm_rows_ext(a2: torch.Tensor, b2: torch.Tensor, out2: torch.Tensor, Bn: in
     d.A, d.B, d.C, d.bias = a2.data_ptr() + r0 * a2.stride(0) * 2, b2.data_ptr(), out2.data_ptr() + r0 * out2.stride(0) * 2, None
     d.M, d.N, d.K = M - tail, N, Kd
     d.lda, d.ldc = a2.stride(0), out2.stride(0)
-    if b2.stride(0) == 1:            # W^T of a row-major [N, K] weight: contraction index contiguous
-        d.ldb, d.b_kc = b2.stride(1), 1
-    elif b2.stride(1) == 1:          # row-major [K, N]
-        d.ldb, d.b_kc = b2.stride(0), 0
-    else:
-        raise MirrorHipError("gemm_rows_ext: the weight view must have a unit stride")
+    d.ldb, d.b_kc = _weight_view_ld(b2, "gemm_rows_ext")
     d.a_kc = 1
     d.dtA, d.dtB, d.dtC, d.mma = MH_BF16, MH_BF16, MH_BF16, MH_BF16
     d.batch1 = d.batch2 = 1
@@ -319,22 +314,17 @@ def gemm_rows_ext(a2: torch.Tensor, b2: torch.Tensor, out2: torch.Tensor, Bn: in
         d.c_rows_per_batch, d.c_row_skip = R, T - R
         d.window_batches = Bn          # the extra rows follow the last batch's window without a gap
     d.shared_chip = 1 if shared_chip else 0
-    prof = gemm_profiler
-    if prof is None:
-        _lib.call("mh_gemm", C.byref(d), stream=_stream())
-    else:
-        prof.launch(d, lambda: _lib.call("mh_gemm", C.byref(d), stream=_stream()))
+    _launch_gemm(d)
     return tail
 
 
 def gemm_rows_window_ok(a3: torch.Tensor, out3: torch.Tensor, r0: int, R: int, N: int) -> bool:
-    """shapes / build for which gemm_rows_window runs (the direct-to-LDS 256 x 256 kernels)."""
+    """shapes for which gemm_rows_window runs (the direct-to-LDS 256 x 256 kernels)."""
     bf = torch.bfloat16
     return (a3.dim() == 3 and out3.dim() == 3 and a3.dtype == bf and out3.dtype == bf and a3.is_cuda and R >= 256 and a3.shape[0] * R > 512
             and N % 256 == 0 and a3.shape[2] % 64 == 0 and a3.stride(2) == 1 and out3.stride(2) == 1 and a3.stride(1) % 8 == 0
             and out3.stride(1) % 8 == 0 and a3.data_ptr() % 16 == 0 and out3.data_ptr() % 16 == 0
-            and a3.stride(0) == a3.shape[1] * a3.stride(1) and out3.stride(0) == out3.shape[1] * out3.stride(1)
-            and int(_lib.load().mh_gemm_select_pp(-1)) != 0)
+            and a3.stride(0) == a3.shape[1] * a3.stride(1) and out3.stride(0) == out3.shape[1] * out3.stride(1))
 
 
 def epi_dropadd(resid: torch.Tensor, p: float, seed: int, offset: int, dev_base) -> "_lib.GemmEpi":
@@ -1568,17 +1558,6 @@ def dropout(x: torch.Tensor, p: float, seed: int, offset: int, out: Optional[tor
     _contig(x, "dropout input")
     y = out if out is not None else torch.empty_like(x)
     _lib.call("mh_dropout", _p(x), _p(y), x.numel(), p, seed, offset, _p(dev_base), dt(x), dt(y), stream=_stream())
-    return y
-
-
-def gemm_w4(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """(experiment) bf16 [M, N] = a [M, K] @ w[N, K]^T + bias on the four-wave 256 x 256 tile kernel (mh_gemm_w4)."""
-    _chk(a, w, bias, out)
-    M, Kd = a.shape
-    N = w.shape[0]
-    assert a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and a.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == Kd
-    y = out if out is not None else torch.empty((M, N), device=a.device, dtype=torch.bfloat16)
-    _lib.call("mh_gemm_w4", _p(a), _p(w), _p(y), _p(bias), M, N, Kd, a.stride(0), w.stride(0), y.stride(0), stream=_stream())
     return y
 
 

@@ -109,7 +109,7 @@ def test_gemm_large_tile_kernel(a_rm, b_t, out_dtype):
         # the library names the instance it launched (mh_gemm_variant_name)
         from mirror_amd import _lib
         name = _lib.load().mh_gemm_variant_name().decode()
-        assert name.startswith(("gemm_pq_kernel<", "gemm_pp_kernel<", "gemm_big_kernel<", "gemm_kernel<1,bf16,bf16,")), name
+        assert name.startswith(("gemm_pq_kernel<", "gemm_pp_kernel<", "gemm_kernel<1,bf16,bf16,")), name
         assert ("float" if out_dtype == torch.float32 else "bf16") in name.split(",", 3)[-1] or name.startswith("gemm_p"), name
         close(outr[:, :Mr], (ar.double() @ b.double()).float().to(out_dtype).double(), 0, 0, "large tile ragged M")
         assert bool((outr[:, Mr:] == 7.0).all()), "rows past M were written"
@@ -1319,23 +1319,6 @@ def test_step_glue_rownorm_clamp_adam():
         K.adam(p2, gr.to(DEV), m2, v2, None, 2e-5, 0.9, 0.999, 1e-8, 0.1, 0.001, clamp=(5, 0.0, 1.0), hole=(4, 8))
 
 
-@pytest.mark.parametrize("M,N,Kd", [(512, 256, 64), (1024, 512, 512), (768, 1024, 1536)])
-def test_gemm_four_wave_experiment_is_bit_equal_to_mh_gemm(M, N, Kd):
-    """mh_gemm_w4 (round 5 experiment: the 256 x 256 x 64 tile on four waves with 128 x 128 wave tiles) computes the same bf16 products in
-    the same k order as the 8-wave kernels behind mh_gemm: the results must be bit-identical, with and without a bias."""
-    gen = g(M + Kd)
-    a = torch.randn(M, Kd, generator=gen).to(DEV, torch.bfloat16)
-    w = (torch.randn(N, Kd, generator=gen) * 0.05).to(DEV, torch.bfloat16)
-    b = torch.randn(N, generator=gen).to(DEV)
-    for bias in (None, b):
-        ref = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
-        K.gemm(a, w.t(), out=ref, bias=bias, mma=MH_BF16)
-        got = K.gemm_w4(a, w, bias)
-        assert torch.equal(got, ref), float((got.float() - ref.float()).abs().max())
-    with pytest.raises(K.MirrorHipError):
-        K.gemm_w4(a[:, :Kd - 32].contiguous(), w[:, :Kd - 32].contiguous())
-
-
 def test_noise_draws_one_launch_uniform_and_normal():
     """mh_noise_draws: uniform [0, 1) on 24 bits and Box-Muller normals from the Philox dropout stream — a pure function of
     (seed, offset + device base, element), the moments of the distributions they stand for (torch.rand / torch.randn at
@@ -1678,6 +1661,7 @@ def test_fp8_quant_and_gemm(M, N, Kd, batch):
     """BASELINE config 5 pieces: per-tensor e4m3 quantisation (bit-exact against torch.float8_e4m3fn) and the fp8 MFMA product
     (f32 accumulate) with bias / ReLU, ragged M, a batch of row windows of a larger buffer.  The last shape is large enough for
     the 256-tile pipeline with the 32x32x64 f8f6f4 MFMA; the others run on the 128-tile kernel."""
+    big = (M, N, Kd, batch) == (4100, 512, 256, 4)        # the one shape on the large-tile kernel
     gen = g(101)
     e4 = torch.float8_e4m3fn
     x = (torch.randn(batch, M + 5, Kd, generator=gen) * 3).bfloat16()
@@ -1694,12 +1678,14 @@ def test_fp8_quant_and_gemm(M, N, Kd, batch):
     ref = torch.relu(xr.double() @ wq.cpu().view(e4).float().double().t() * float(sx) * float(sw) + bias.double())
     out = torch.full((batch, M + 1, N), -7.0, device=DEV)
     K.gemm_fp8(xq[:, 2:2 + M], sx, wq, sw, out[:, 1:], bias=bias.to(DEV), act=1)
+    assert K._lib.load().mh_gemm_variant_name().decode().startswith("gemm_big_kernel<") == big
     # products of e4m3 values are exact in f32, but the MFMA's 16-term dot product is not accumulated at full f32 precision
     # (measured: ~1e-4 relative to the row / column norms), hence the tolerance
     close(out[:, 1:], ref, 1e-3, 2e-2, "fp8 gemm")
     assert float(out[:, 0].max()) == -7.0                 # nothing written outside the window
     ob = torch.empty((batch, M, N), device=DEV, dtype=torch.bfloat16)
     K.gemm_fp8(xq[:, 2:2 + M], sx, wq, sw, ob)
+    assert K._lib.load().mh_gemm_variant_name().decode().startswith("gemm_big_kernel<") == big
     ref2 = xr.double() @ wq.cpu().view(e4).float().double().t() * float(sx) * float(sw)
     close(ob, ref2.float().bfloat16().double(), 2e-2, 2e-2, "fp8 gemm bf16 out")      # within one bf16 ulp
 

@@ -1,16 +1,16 @@
 #!/usr/bin/env python3
-"""A/B of the two 256 x 256-tile GEMM main loops (mh_gemm_select_pp) on the step's large shapes, interleaved in one process:
-correctness against an f32 torch product on a row sample, then microseconds / TFLOP/s per shape and kernel."""
+"""A/B of the two direct-to-LDS 256 x 256-tile GEMM kernels on the step's large shapes, interleaved in one process: the persistent
+kernel (pq, the default) against one workgroup per tile (pp, what a launch gets while K.shared_chip is set).  Correctness against an
+f32 torch product on a row sample, then microseconds / TFLOP/s per shape and kernel."""
 import os
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mirror_amd import _lib, kernels as K          # noqa: E402
+from mirror_amd import kernels as K                # noqa: E402
 from mirror_amd._lib import ACT_RELU, MH_BF16      # noqa: E402
 
-lib = _lib.load()
 dev, bf, f32 = "cuda", torch.bfloat16, torch.float32
 
 
@@ -38,26 +38,28 @@ def timeit(fn, reps=20):
     return e0.elapsed_time(e1) / reps * 1e3
 
 
-MODES = ((2, "pq"), (1, "pp"), (0, "reg"))
+MODES = ((False, "pq"), (True, "pp"))          # K.shared_chip -> kernel
 
 
 def run(name, make, flops, ref=None):
     res = {}
-    for rnd in range(2):
-        for mode, _ in MODES:
-            lib.mh_gemm_select_pp(mode)
-            fn = make()
-            out = fn()
-            torch.cuda.synchronize()
-            err = ref(out) if (ref is not None and rnd == 0) else None
-            us = timeit(fn)
-            res.setdefault(mode, []).append((us, err))
-    lib.mh_gemm_select_pp(2)
+    try:
+        for rnd in range(2):
+            for mode, _ in MODES:
+                K.shared_chip = mode
+                fn = make()
+                out = fn()
+                torch.cuda.synchronize()
+                err = ref(out) if (ref is not None and rnd == 0) else None
+                us = timeit(fn)
+                res.setdefault(mode, []).append((us, err))
+    finally:
+        K.shared_chip = False
     best = {m: min(u for u, _ in res[m]) for m, _ in MODES}
     line = f"{name:58s}"
     for m, nm in MODES:
         line += f" {nm} {best[m]:7.1f} us {flops / best[m] / 1e6:5.0f} TF/s |"
-    line += f" pq/reg x{best[0] / best[2]:4.2f} | err " + " ".join(f"{res[m][0][1]:.1e}" for m, _ in MODES)
+    line += f" pq/pp x{best[False] / best[True]:4.2f} | err " + " ".join(f"{res[m][0][1]:.1e}" for m, _ in MODES)
     print(line, flush=True)
 
 
