@@ -915,6 +915,22 @@ int mh_infonce_rows_bwd(const float* neg, int64_t ld, const float* pneg, const f
 int mh_infonce_fold(const float* dpos, const float* qn, const float* kn, const float* part, int nparts, float* dq, float* dk, int N,
                     int D, mh_stream s);
 
+/* ---------------------------------------------------------------- cross-modal retrieval (the zero-shot check of the alignment
+ * heads: recall@k and median rank, train_mirror.py:1382-1526)
+ * rank of each query's positive key among nk keys, by dot-product similarity:
+ * ranks[i] = 1 + #{ j != target[i] : !(dot(q_i, k_j) < dot(q_i, k_target[i])) }      (int32 [nq], initialised on s by this call)
+ * q [nq x D], k [nk x D] f32 contiguous; target int64 [nq] in [0, nk), or NULL = identity (needs nq == nk).
+ * Pessimistic on ties and NaN: a key that ties with the positive, or whose similarity (or the positive's) is NaN, counts
+ * against the query, so a collapsed encoder (all embeddings equal) scores rank nk everywhere, never rank 1.
+ * Every dot product, the positive's included, is the same k-ordered f32 fmaf chain (v_mfma_f32_32x32x2_f32, no split-K): a key row
+ * bit-identical to the positive's ties with it at every D.  Only the column j == target[i] is excluded, not its duplicates.
+ * A target outside [0, nk) is not clamped: no key is read for it and the query gets rank nk + 1.
+ * 1 <= nq, nk <= 2^20, 1 <= D <= 4096.  The nq x nk matrix is never written.  Deterministic (integer atomics only).
+ * workspace: mh_retrieval_workspace_bytes(nq, nk, D) bytes (O(nq): the positives' similarities), 4-byte aligned. */
+int mh_retrieval_ranks(const float* q, const float* k, int64_t nq, int64_t nk, int D, const int64_t* target, int32_t* ranks,
+                       void* workspace, mh_stream s);
+int64_t mh_retrieval_workspace_bytes(int64_t nq, int64_t nk, int D);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,10 +223,12 @@ _SIGS = {
     "mh_infonce_rows_fwd": [P, P, P, L, I, I, I, F, F, P, P, P, P],
     "mh_infonce_rows_bwd": [P, L, P, P, P, I, F, F, I, I, P, P],
     "mh_infonce_fold": [P, P, P, P, I, P, P, I, I],
+    "mh_retrieval_ranks": [P, P, L, L, I, P, P, P],
 }
 EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "mh_gemm_variant_name", "mh_device_ok", "mh_nys_attn3_ws_floats", "mh_rna_block_workspace_bytes",
                                  "mh_gemm_workspace_bytes", "mh_layernorm_bwd_workspace_bytes", "mh_nys_attn3_workspace_bytes",
-                                 "mh_pinv_chain_workspace_bytes", "mh_resconv_bwd_workspace_bytes", "mh_mask_apply_bwd_dbias_ok"])
+                                 "mh_pinv_chain_workspace_bytes", "mh_resconv_bwd_workspace_bytes", "mh_mask_apply_bwd_dbias_ok",
+                                 "mh_retrieval_workspace_bytes"])
 
 _lib = None
 
@@ -279,6 +281,8 @@ def load() -> C.CDLL:
     lib.mh_mask_apply_bwd_dbias_ok.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
     lib.mh_rna_block_workspace_bytes.restype = C.c_int64
     lib.mh_rna_block_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.mh_retrieval_workspace_bytes.restype = C.c_int64
+    lib.mh_retrieval_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int]
     for name, sig in _SIGS.items():
         fn = getattr(lib, name, None)
         if fn is None:      # entry points added within a generation (no argument list changed): an older build lacks them

@@ -1,0 +1,233 @@
+// Cross-modal retrieval ranks (recall@k / median rank of the CLIP-style alignment, train_mirror.py:1382-1526): for every query the
+// number of keys whose dot-product similarity is not below the positive's, WITHOUT the nq x nk similarity matrix.
+//
+// Two launches on the caller's stream, nothing allocated, nothing waits on the host (graph capturable):
+//   1. retr_pos_kernel: d[i] = q_i . k_target[i] as the k-ordered f32 fmaf chain from 0 that v_mfma_f32_32x32x2_f32 forms
+//      (one rounding per product), into the workspace; ranks[i] = 1.
+//   2. retr_tile_kernel: a workgroup owns a 128 x 128 tile of S = q k^T: 4 waves as 2 x 2, each 2 x 2 accumulators of 32 x 32, the K
+//      loop over D through a double-buffered LDS stage of 16 (the remainder in D zero-filled: fmaf(0, 0, acc) = acc, so the chain
+//      of step 1 is reproduced bit for bit).  No split-K.  Epilogue: compare every accumulator with its row's d, count per row
+//      with wave ballots (the 32 columns of a row half sit in 32 lanes), add the two column waves in LDS and issue ONE integer
+//      atomic per row and tile.  Rows >= nq, columns >= nk and the column j == target[i] are excluded by index.
+// A key row bit-identical to the positive's therefore ties with it exactly and counts against the query, as does every NaN.
+#include <math.h>
+
+#include "common.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int RT_TILE = 128;          // tile edge in rows of q and of k
+constexpr int RT_BK = 16;             // K step through LDS: 8 MFMAs of k = 2
+constexpr int RT_LD = RT_BK + 1;      // LDS row stride in floats: 32 rows at one k fall into 32 banks
+constexpr int RT_THREADS = 256;
+constexpr int RT_GROUP = 8;           // row tiles per group of the tile order (see retr_tile_kernel)
+constexpr int RT_QUADS = RT_TILE * RT_BK / 4 / RT_THREADS;   // 16-byte pieces of one operand tile per thread
+
+__global__ void __launch_bounds__(RT_THREADS) retr_pos_kernel(const float* __restrict__ q, const float* __restrict__ k, int nq, int nk,
+                                                              int D, const int64_t* __restrict__ target, int vec,
+                                                              float* __restrict__ d, int32_t* __restrict__ ranks) {
+    const int i = blockIdx.x * RT_THREADS + threadIdx.x;
+    if (i >= nq) return;
+    const int64_t t = target ? target[i] : (int64_t)i;
+    float acc = 0.f;
+    if (t < 0 || t >= nk) {
+        acc = __builtin_nanf("");     // no such key: nothing is read, every key counts against the query
+    } else {
+        const float* a = q + (int64_t)i * D;
+        const float* b = k + t * D;
+        int c = 0;
+        if (vec) {
+            for (; c + 4 <= D; c += 4) {
+                const f4_t x = *reinterpret_cast<const f4_t*>(a + c), y = *reinterpret_cast<const f4_t*>(b + c);
+                acc = fmaf(x[0], y[0], acc);
+                acc = fmaf(x[1], y[1], acc);
+                acc = fmaf(x[2], y[2], acc);
+                acc = fmaf(x[3], y[3], acc);
+            }
+        }
+        for (; c < D; c++) acc = fmaf(a[c], b[c], acc);
+    }
+    d[i] = acc;
+    ranks[i] = 1;
+}
+
+// this thread's pieces of rows [row0, row0 + 128) x columns [k0, k0 + 16) of x [n x D]; zero outside the matrix
+__device__ __forceinline__ void retr_load(f4_t (&r)[RT_QUADS], const float* __restrict__ x, int n, int D, int row0, int k0, int vec,
+                                          int tid) {
+#pragma unroll
+    for (int u = 0; u < RT_QUADS; u++) {
+        const int c = tid + u * RT_THREADS;
+        const int row = row0 + (c >> 2), kk = k0 + (c & 3) * 4;
+        f4_t v = {0.f, 0.f, 0.f, 0.f};
+        if (row < n) {
+            const float* p = x + (int64_t)row * D + kk;
+            if (vec && kk + 4 <= D) {
+                v = *reinterpret_cast<const f4_t*>(p);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                    if (kk + e < D) v[e] = p[e];
+            }
+        }
+        r[u] = v;
+    }
+}
+
+__device__ __forceinline__ void retr_store(const f4_t (&r)[RT_QUADS], float* __restrict__ tile, int tid) {
+#pragma unroll
+    for (int u = 0; u < RT_QUADS; u++) {
+        const int c = tid + u * RT_THREADS;
+        float* p = tile + (c >> 2) * RT_LD + (c & 3) * 4;
+#pragma unroll
+        for (int e = 0; e < 4; e++) p[e] = r[u][e];
+    }
+}
+
+__global__ void __launch_bounds__(RT_THREADS) retr_tile_kernel(const float* __restrict__ q, const float* __restrict__ k, int nq, int nk,
+                                                               int D, const int64_t* __restrict__ target, int vec, int tiles_m,
+                                                               int tiles_n, const float* __restrict__ d, int32_t* __restrict__ ranks) {
+    __shared__ float s_a[2][RT_TILE * RT_LD];
+    __shared__ float s_b[2][RT_TILE * RT_LD];
+    __shared__ float s_d[RT_TILE];
+    __shared__ int s_t[RT_TILE];
+    __shared__ int s_cnt[2][RT_TILE];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    // Blocks b and b + 8 share an XCD (and its L2): give each XCD a contiguous run of tile ids, and number the tiles in groups of
+    // RT_GROUP row tiles, rows fastest, so that the blocks in flight on one XCD share a few row panels and a few column panels.
+    const int nwg = gridDim.x;
+    const int xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+    const int per_group = RT_GROUP * tiles_n;
+    const int first_m = (wgid / per_group) * RT_GROUP;
+    const int gm = tiles_m - first_m < RT_GROUP ? tiles_m - first_m : RT_GROUP;
+    const int tile_m = first_m + (wgid % per_group) % gm, tile_n = (wgid % per_group) / gm;
+    const int row0 = tile_m * RT_TILE, col0 = tile_n * RT_TILE;
+
+    if (tid < RT_TILE) {
+        const int row = row0 + tid;
+        float dv = 0.f;
+        int t = -1;
+        if (row < nq) {
+            dv = d[row];
+            const int64_t t64 = target ? target[row] : (int64_t)row;
+            t = t64 >= 0 && t64 < nk ? (int)t64 : -1;
+        }
+        s_d[tid] = dv;
+        s_t[tid] = t;
+    }
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+
+    const int nt = (D + RT_BK - 1) / RT_BK;
+    f4_t ra[RT_QUADS], rb[RT_QUADS];
+    retr_load(ra, q, nq, D, row0, 0, vec, tid);
+    retr_load(rb, k, nk, D, col0, 0, vec, tid);
+    retr_store(ra, s_a[0], tid);
+    retr_store(rb, s_b[0], tid);
+    if (nt > 1) {
+        retr_load(ra, q, nq, D, row0, RT_BK, vec, tid);
+        retr_load(rb, k, nk, D, col0, RT_BK, vec, tid);
+    }
+    __syncthreads();
+
+    // lane l feeds A[row l & 31][k = l >> 5] and B[k = l >> 5][column l & 31] of each k = 2 step
+    const int frag = (lane & 31) * RT_LD + (lane >> 5);
+    for (int t = 0; t < nt; t++) {
+        const int cur = t & 1;
+        if (t + 1 < nt) {          // stage cur ^ 1 was last read before the barrier that ended step t - 1
+            retr_store(ra, s_a[cur ^ 1], tid);
+            retr_store(rb, s_b[cur ^ 1], tid);
+            if (t + 2 < nt) {
+                retr_load(ra, q, nq, D, row0, (t + 2) * RT_BK, vec, tid);
+                retr_load(rb, k, nk, D, col0, (t + 2) * RT_BK, vec, tid);
+            }
+        }
+        const float* at = s_a[cur] + wm * 64 * RT_LD + frag;
+        const float* bt = s_b[cur] + wn * 64 * RT_LD + frag;
+#pragma unroll
+        for (int s = 0; s < RT_BK / 2; s++) {
+            float af[2], bf[2];
+#pragma unroll
+            for (int i = 0; i < 2; i++) af[i] = at[i * 32 * RT_LD + 2 * s];
+#pragma unroll
+            for (int j = 0; j < 2; j++) bf[j] = bt[j * 32 * RT_LD + 2 * s];
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int j = 0; j < 2; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[j], acc[i][j], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+
+    // accumulator register r of lane l: column l & 31, row (r & 3) + 8 (r >> 2) + 4 (l >> 5) of its 32 x 32 block.  A ballot gives
+    // the 32 columns of that row in its low half (rows of l >> 5 == 0) and those of the row 4 below in its high half.  Lane L of
+    // the wave ends up with the count of the wave's row L.
+    const int half = lane >> 5;
+    int col[2];
+#pragma unroll
+    for (int j = 0; j < 2; j++) col[j] = col0 + wn * 64 + j * 32 + (lane & 31);
+    int mine = 0;
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int rl = i * 32 + (r & 3) + 8 * (r >> 2);      // wave-local row of the low half
+            const float dv = s_d[wm * 64 + rl + 4 * half];
+            const int tg = s_t[wm * 64 + rl + 4 * half];
+            int lo = 0, hi = 0;
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const bool beats = col[j] < nk && col[j] != tg && !(acc[i][j][r] < dv);
+                const unsigned long long m = __ballot(beats);
+                lo += __popc((unsigned)m);
+                hi += __popc((unsigned)(m >> 32));
+            }
+            if (lane == rl) mine = lo;
+            if (lane == rl + 4) mine = hi;
+        }
+    }
+    s_cnt[wn][wm * 64 + lane] = mine;
+    __syncthreads();
+    if (tid < RT_TILE) {
+        const int c = s_cnt[0][tid] + s_cnt[1][tid];
+        if (row0 + tid < nq && c) atomicAdd(&ranks[row0 + tid], c);
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t mh_retrieval_workspace_bytes(int64_t nq, int64_t nk, int D) {
+    (void)nk;
+    (void)D;
+    return nq > 0 ? nq * (int64_t)sizeof(float) : 0;     // the positives' similarities
+}
+
+extern "C" int mh_retrieval_ranks(const float* q, const float* k, int64_t nq, int64_t nk, int D, const int64_t* target, int32_t* ranks,
+                                  void* workspace, mh_stream s) {
+    MH_REQUIRE(q && k && ranks && workspace, "mh_retrieval_ranks: null pointer");
+    MH_REQUIRE(nq >= 1 && nq <= (1 << 20) && nk >= 1 && nk <= (1 << 20), "mh_retrieval_ranks: nq = %lld, nk = %lld outside [1, 2^20]",
+               (long long)nq, (long long)nk);
+    MH_REQUIRE(D >= 1 && D <= 4096, "mh_retrieval_ranks: D = %d outside [1, 4096]", D);
+    MH_REQUIRE(target || nq == nk, "mh_retrieval_ranks: no target needs nq == nk (got %lld, %lld)", (long long)nq, (long long)nk);
+    MH_REQUIRE(((uintptr_t)workspace & 3) == 0, "mh_retrieval_ranks: workspace must be 4-byte aligned");
+    const int vec = D % 4 == 0 && mh_quad_ok(q, 4) && mh_quad_ok(k, 4);
+    float* d = (float*)workspace;
+    hipLaunchKernelGGL(retr_pos_kernel, dim3(mh_cdiv(nq, RT_THREADS)), dim3(RT_THREADS), 0, (hipStream_t)s, q, k, (int)nq, (int)nk, D,
+                       target, vec, d, ranks);
+    MH_LAUNCH_CHECK("mh_retrieval_ranks");
+    const int tiles_m = mh_cdiv(nq, RT_TILE), tiles_n = mh_cdiv(nk, RT_TILE);
+    hipLaunchKernelGGL(retr_tile_kernel, dim3((unsigned)tiles_m * (unsigned)tiles_n), dim3(RT_THREADS), 0, (hipStream_t)s, q, k, (int)nq,
+                       (int)nk, D, target, vec, tiles_m, tiles_n, (const float*)d, ranks);
+    MH_LAUNCH_CHECK("mh_retrieval_ranks");
+    return MH_OK;
+}

@@ -577,15 +577,20 @@ class TrainEngine:
     LOSS_NAMES = ("loss", "alignment_loss", "wsi_retention_loss", "rna_retention_loss", "style_loss", "cluster_loss")
 
     def validate(self, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], noise: Optional[Sequence[dict]] = None,
-                 model: Optional[torch.nn.Module] = None) -> "OrderedDict[str, float]":
+                 model: Optional[torch.nn.Module] = None, retrieval=None) -> "OrderedDict[str, float]":
         """The reference's `validate()`: eval mode (dropout off, masking still on), no autograd, the six losses averaged
         over the loader weighted by batch size (utils.AverageMeter.update(loss, B)) and, under DDP, averaged over ranks
         (utils.reduce_tensor).  The running sums stay on the device: ONE host sync at the end instead of six `.item()`s
         per batch.  `noise[i]` optionally pins the random draws of batch i (parity tests).  The module's train / eval
         mode is restored on return (the reference leaves it in eval and flips it back in train_one_epoch).
         model: another module to validate with this engine's loss and masking, e.g. `model_ema.module` (the EMA weights,
-        train_mirror.py:1022-1037); the engine's model by default."""
+        train_mirror.py:1022-1037); the engine's model by default.
+        retrieval: a `retrieval.CrossModalRetrieval`; it is reset, fed the two alignment embeddings of every batch (this rank's rows,
+        also under gather_distributed) and its entries (recall@k, median rank, `r_mean`, ... over the union of all ranks' pairs)
+        are appended behind the six losses, e.g. for `CheckpointSaver(decreasing=False)` on `r_mean`.  None: nothing changes."""
         net = self.model if model is None else model
+        if retrieval is not None:
+            retrieval.reset()
         was_training = net.training
         net.eval()
         acc = torch.zeros(7, device=self.device, dtype=torch.float64)        # 6 weighted sums + the sample count
@@ -604,6 +609,8 @@ class TrainEngine:
                     finally:
                         net._align_gather = None
                     losses = self.loss_fn(*outs)
+                    if retrieval is not None:
+                        retrieval.update(outs[0], outs[7])      # the rank-local rows: the gathered ones only exist inside the loss
                     b = float(wsi.shape[0])
                     acc[:6] += torch.stack([x.detach().reshape(()) for x in losses]).double() * b
                     acc[6] += b
@@ -614,7 +621,11 @@ class TrainEngine:
             dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=self.pg)
         vals = acc.cpu()
         n = max(float(vals[6]), 1.0)
-        return OrderedDict((k, float(vals[j]) / n) for j, k in enumerate(self.LOSS_NAMES))
+        out = OrderedDict((k, float(vals[j]) / n) for j, k in enumerate(self.LOSS_NAMES))
+        if retrieval is not None:
+            from .metrics import sync_and_compute
+            out.update(sync_and_compute(retrieval, self.pg) if self.world > 1 else retrieval.compute())
+        return out
 
     # ------------------------------------------------------------------ optimizer state (resume_checkpoint, train_mirror.py:772-780)
     def _groups(self):

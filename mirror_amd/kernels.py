@@ -2283,3 +2283,37 @@ def infonce_fold(dpos, qn, kn, part: Optional[torch.Tensor], want_dq: bool, want
     dk = torch.empty((N, D), device=qn.device, dtype=torch.float32) if want_dk else None
     _lib.call("mh_infonce_fold", _p(dpos), _p(qn), _p(kn), _p(part) if want_dq else None, nparts, _p(dq), _p(dk), N, D, stream=_stream())
     return dq, dk
+
+
+# ----------------------------------------------------------------------------- cross-modal retrieval (csrc/retrieval.hip)
+def retrieval_ranks(q: torch.Tensor, k: torch.Tensor, target: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [nq] on the device (no sync): ranks[i] = 1 + #{j != target[i]: not (q[i] . k[j] < q[i] . k[target[i]])}, the rank of each
+    query's positive among the nk keys with ties and NaN counted against the query.  q f32 [nq, D], k f32 [nk, D] on the device;
+    target int32 / int64 [nq] (None: the identity, needs nq == nk).  A host `target` is range-checked here (ValueError) and copied
+    over; a device `target` is NOT checked (that would wait on the host) and the kernel clamps nothing: an entry outside [0, nk)
+    reads no key and gives rank nk + 1.  The [nq, nk] similarities are never stored: the only allocations are the result and an
+    f32 [nq] workspace."""
+    if q.dim() != 2 or k.dim() != 2 or q.shape[1] != k.shape[1]:
+        raise ValueError(f"retrieval_ranks: q [nq, D] and k [nk, D] must share D, got {tuple(q.shape)} and {tuple(k.shape)}")
+    nq, D = q.shape
+    nk = k.shape[0]
+    if target is None and nq != nk:
+        raise ValueError(f"retrieval_ranks: without a target the positives are the diagonal, which needs nq == nk (got {nq}, {nk})")
+    if target is not None:
+        if target.dim() != 1 or target.numel() != nq or target.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"retrieval_ranks: target must be int32 / int64 [{nq}], got {target.dtype} {tuple(target.shape)}")
+        if not target.is_cuda and nq and (int(target.min()) < 0 or int(target.max()) >= nk):
+            raise ValueError(f"retrieval_ranks: target holds entries outside [0, {nk})")
+    _chk(q, k)
+    if q.dtype != torch.float32 or k.dtype != torch.float32:
+        raise MirrorHipError(f"retrieval_ranks: q and k must be f32 (ranks decided by a bf16 rounding are not a metric), got {q.dtype}, {k.dtype}")
+    if not (1 <= nq <= (1 << 20)) or not (1 <= nk <= (1 << 20)) or not (1 <= D <= 4096):
+        raise MirrorHipError(f"retrieval_ranks: nq = {nq}, nk = {nk} (1..2^20), D = {D} (1..4096)")
+    q, k = q.detach().contiguous(), k.detach().contiguous()
+    if target is not None:
+        target = target.to(device=q.device, dtype=torch.int64, non_blocking=True).contiguous()
+    ranks = torch.empty((nq,), device=q.device, dtype=torch.int32)
+    ws_bytes = int(_lib.load().mh_retrieval_workspace_bytes(nq, nk, D))
+    ws = torch.empty(((ws_bytes + 3) // 4,), device=q.device, dtype=torch.float32)
+    _lib.call("mh_retrieval_ranks", _p(q), _p(k), nq, nk, D, _p(target), _p(ranks), _p(ws), stream=_stream())
+    return ranks

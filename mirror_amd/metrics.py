@@ -207,9 +207,10 @@ def _gather_var(t: torch.Tensor, group, via_host: bool) -> List[torch.Tensor]:
     return [o[:s].to(t.device) for o, s in zip(outs, sizes)]
 
 
-def sync_and_compute(metric, process_group=None) -> torch.Tensor:
+def sync_and_compute(metric, process_group=None):
     """torcheval.metrics.toolkit.sync_and_compute: merge the metric's state over the ranks of `process_group` (torch.distributed)
-    and compute it on every rank.  The caller's metric is left as it was.  On a gloo group the state goes through the host."""
+    and compute it on every rank.  The caller's metric is left as it was.  On a gloo group the state goes through the host.
+    Also takes a `retrieval.CrossModalRetrieval` (both embedding sets are gathered; the result is its OrderedDict)."""
     import copy
 
     import torch.distributed as dist
@@ -234,6 +235,17 @@ def sync_and_compute(metric, process_group=None) -> torch.Tensor:
         y = torch.cat(metric.targets) if metric.targets else torch.empty((0,), dtype=torch.int64, device=metric.device)
         merged.inputs = _gather_var(x, process_group, via_host)
         merged.targets = _gather_var(y, process_group, via_host)
+        return merged.compute()
+    from .retrieval import CrossModalRetrieval
+    if isinstance(metric, CrossModalRetrieval):
+        # every rank ranks over the UNION: the gallery size is part of the metric, so per-rank values averaged afterwards would be
+        # another (easier) metric.  A rank without samples learns the width from the others.
+        D = torch.tensor([metric.wsi[0].shape[1] if metric.wsi else 0], dtype=torch.int64, device="cpu" if via_host else metric.device)
+        dist.all_reduce(D, op=dist.ReduceOp.MAX, group=process_group)
+        empty = torch.empty((0, int(D)), dtype=torch.float32, device=metric.device)
+        w, r = metric._cat() if metric.wsi else (empty, empty)
+        merged.wsi = [t for t in _gather_var(w, process_group, via_host) if t.shape[0]]
+        merged.rna = [t for t in _gather_var(r, process_group, via_host) if t.shape[0]]
         return merged.compute()
     raise TypeError(f"sync_and_compute: unsupported metric {type(metric).__name__}")
 

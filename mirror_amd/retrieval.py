@@ -1,0 +1,129 @@
+"""Zero-shot cross-modal retrieval of the alignment heads: for each slide, where its own RNA profile ranks among all validation
+profiles, and the reverse (recall@1/5/10, median and mean rank).  Unlike the alignment loss these do not depend on `logit_scale`
+(positive, so irrelevant to ranks), the batch size, the world size or `gather_distributed`: only on the gallery.
+
+The ranks come from `mh_retrieval_ranks` (csrc/retrieval.hip): a fused exact-f32 MFMA product with a comparing epilogue, so the
+[n, n] similarity matrix never exists.  The rule is pessimistic: a key that ties with the positive, or a NaN on either side,
+counts against the query, so a collapsed encoder scores rank n everywhere, never rank 1.
+
+Not built: more than one positive per query, bf16 keys, both directions from one pass over the similarities.
+"""
+from __future__ import annotations
+
+from collections import OrderedDict
+from typing import Iterable, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import kernels as K
+from ._lib import MirrorHipError
+
+__all__ = ["retrieval_ranks", "summarize_ranks", "CrossModalRetrieval"]
+
+
+def _l2(x: torch.Tensor) -> torch.Tensor:
+    """Rows scaled to unit length by mh_l2norm_fwd (F.normalize's eps), as InfoNCE normalises its operands."""
+    x = x.detach().contiguous()
+    rows, D = x.shape
+    y, _ = K.l2norm_fwd(x, rows, D, D, 1e-12, torch.float32)
+    return y
+
+
+def retrieval_ranks(query: torch.Tensor, key: torch.Tensor, target: Optional[torch.Tensor] = None,
+                    normalize: bool = False) -> torch.Tensor:
+    """int32 [nq] on the device, no host sync: the rank (1 = best) of key[target[i]] among all keys by query[i] . key[j]; `target`
+    None pairs row i with row i.  normalize=True compares cosines (both sides through mh_l2norm_fwd first), which is what
+    `InfoNCE` trains; the default compares the raw dot products, as `ClipLoss` does with the projected embeddings.
+    See kernels.retrieval_ranks for the checks and the pessimistic tie / NaN rule."""
+    if normalize:
+        if query.dim() != 2 or key.dim() != 2:
+            raise ValueError(f"retrieval_ranks: query and key must be [n, D], got {tuple(query.shape)} and {tuple(key.shape)}")
+        K._chk(query, key)
+        if query.dtype != torch.float32 or key.dtype != torch.float32:
+            raise MirrorHipError(f"retrieval_ranks: query and key must be f32, got {query.dtype}, {key.dtype}")
+        if query.shape[0] and key.shape[0] and query.shape[1] == key.shape[1] and query.shape[1] >= 1:
+            query, key = _l2(query), _l2(key)
+    return K.retrieval_ranks(query, key, target)
+
+
+def summarize_ranks(ranks, ks: Sequence[int] = (1, 5, 10)) -> "OrderedDict[str, float]":
+    """`r@{k}` = the fraction of ranks <= k for every k of `ks`, then `medr` (np.median) and `meanr`, from a host array of ranks."""
+    r = np.asarray(ranks).reshape(-1)
+    if r.size == 0:
+        raise ValueError("summarize_ranks: no ranks")
+    out: "OrderedDict[str, float]" = OrderedDict()
+    for k in ks:
+        out[f"r@{int(k)}"] = float(np.mean(r <= int(k)))
+    out["medr"] = float(np.median(r))
+    out["meanr"] = float(np.mean(r.astype(np.float64)))
+    return out
+
+
+class CrossModalRetrieval:
+    """Slide -> RNA and RNA -> slide retrieval over every pair accumulated so far, shaped like the classes of `metrics`:
+    `update(wsi_emb, rna_emb)` keeps f32 copies on the device and never waits on the host; `compute()` launches both directions,
+    reads the two rank vectors back in one sync and returns an OrderedDict of `wsi2rna_r@k..`, `wsi2rna_medr`, `wsi2rna_meanr`,
+    the same for `rna2wsi_`, `r_mean` (the mean of all r@k over both directions: the scalar to select checkpoints on) and
+    `retrieval_n` (the gallery size, which the values depend on).  Recalls are fractions in [0, 1]."""
+
+    def __init__(self, ks: Sequence[int] = (1, 5, 10), normalize: bool = False, device=None):
+        ks = tuple(int(k) for k in ks)
+        if not ks or any(k < 1 for k in ks):
+            raise ValueError(f"ks must be positive ranks, got {ks}")
+        d = torch.device("cuda") if device is None else torch.device(device)
+        if d.type != "cuda":
+            raise MirrorHipError(f"mirror_amd metrics keep their state on a HIP device, got {d}")
+        self.ks = ks
+        self.normalize = bool(normalize)
+        self.device = d
+        self.wsi: List[torch.Tensor] = []             # f32 [n_i, D] per update
+        self.rna: List[torch.Tensor] = []
+
+    def update(self, wsi_emb: torch.Tensor, rna_emb: torch.Tensor) -> "CrossModalRetrieval":
+        """wsi_emb, rna_emb: the two alignment embeddings [B, D] of the same B pairs, row i with row i."""
+        if wsi_emb.dim() != 2 or tuple(wsi_emb.shape) != tuple(rna_emb.shape):
+            raise ValueError(f"wsi_emb and rna_emb must both be [B, D], got {tuple(wsi_emb.shape)} and {tuple(rna_emb.shape)}")
+        if not (wsi_emb.is_floating_point() and rna_emb.is_floating_point()):
+            raise ValueError(f"embeddings must be floating point, got {wsi_emb.dtype} and {rna_emb.dtype}")
+        if self.wsi and self.wsi[0].shape[1] != wsi_emb.shape[1]:
+            raise ValueError(f"embedding width changed from {self.wsi[0].shape[1]} to {wsi_emb.shape[1]}")
+        for store, x in ((self.wsi, wsi_emb), (self.rna, rna_emb)):
+            store.append(x.detach().to(device=self.device, dtype=torch.float32, non_blocking=True, copy=True))
+        return self
+
+    def _cat(self):
+        w = self.wsi[0] if len(self.wsi) == 1 else torch.cat(self.wsi)
+        r = self.rna[0] if len(self.rna) == 1 else torch.cat(self.rna)
+        return w, r
+
+    def compute(self) -> "OrderedDict[str, float]":
+        n = sum(t.shape[0] for t in self.wsi)
+        if n == 0:
+            raise ValueError("CrossModalRetrieval.compute(): no samples (call update() first)")
+        w, r = self._cat()
+        if self.normalize:
+            w, r = _l2(w), _l2(r)
+        both = torch.stack((K.retrieval_ranks(w, r), K.retrieval_ranks(r, w))).cpu().numpy()
+        out: "OrderedDict[str, float]" = OrderedDict()
+        recalls = []
+        for name, ranks in (("wsi2rna", both[0]), ("rna2wsi", both[1])):
+            for k, v in summarize_ranks(ranks, self.ks).items():
+                out[f"{name}_{k}"] = v
+                if k.startswith("r@"):
+                    recalls.append(v)
+        out["r_mean"] = float(np.mean(recalls))
+        out["retrieval_n"] = n
+        return out
+
+    def reset(self) -> "CrossModalRetrieval":
+        self.wsi, self.rna = [], []
+        return self
+
+    def merge_state(self, metrics: Iterable["CrossModalRetrieval"]) -> "CrossModalRetrieval":
+        for m in metrics:
+            if m.wsi and self.wsi and m.wsi[0].shape[1] != self.wsi[0].shape[1]:
+                raise ValueError(f"cannot merge retrieval states of widths {m.wsi[0].shape[1]} and {self.wsi[0].shape[1]}")
+            self.wsi.extend(t.to(self.device) for t in m.wsi)
+            self.rna.extend(t.to(self.device) for t in m.rna)
+        return self
