@@ -580,6 +580,13 @@ int mh_ce_rows_bwd(const float* G, int64_t ldg, const float* scale, float scale_
  * (a row window of a larger buffer: the WSI target is encoder_output[:, 1:], models/mirror.py:700) */
 int mh_mse_masked_fwd(const void* pred, const void* tgt, const float* mask, float* acc, int64_t rows, int D,
                       int64_t rows_per_batch, int64_t tgt_bs, int dt_p, int dt_t, mh_stream s);
+/* The same sums in an order that does not depend on the run: mh_mse_masked_fwd adds its blocks' partial sums with float atomics
+ * in whatever order the blocks arrive, so acc[0] of the same inputs moves by an ulp between launches (a validation loss that is
+ * not bit-reproducible).  Here every block leaves its pair in workspace (MH_MSE_FWD_WS_FLOATS f32, 4-byte aligned, nothing to
+ * zero) and a second launch of one wave adds them in block order onto acc.  Two launches, nothing allocated, no host wait. */
+#define MH_MSE_FWD_WS_FLOATS 2048
+int mh_mse_masked_fwd_ordered(const void* pred, const void* tgt, const float* mask, float* acc, int64_t rows, int D,
+                              int64_t rows_per_batch, int64_t tgt_bs, int dt_p, int dt_t, float* workspace, mh_stream s);
 /* dpred[rows, D] (dt_dp) = g[0] * gmul * 2*mask*(p-t)/(D*acc[1]) (gmul: the term's loss weight, host constant); dtgt[rows, D] (dt_t) = -dpred, not written when NULL.
  * colsum_ws [cs_blocks, D] f32 (may be NULL; bf16 pred / f32 target / bf16 dpred, D a multiple of 256 up to 1024): the launch runs cs_blocks blocks and block i
  * leaves the column sums of the dpred rows it wrote in row i (every row is written, nothing to zero): mh_colsum over that table is the
@@ -930,6 +937,21 @@ int mh_infonce_fold(const float* dpos, const float* qn, const float* kn, const f
 int mh_retrieval_ranks(const float* q, const float* k, int64_t nq, int64_t nk, int D, const int64_t* target, int32_t* ranks,
                        void* workspace, mh_stream s);
 int64_t mh_retrieval_workspace_bytes(int64_t nq, int64_t nk, int D);
+/* The same rank with SEVERAL positives per query (a sample with several slides: every slide of it is paired with the same RNA row).
+ * Group ids are arbitrary int64 values compared for equality only, all 64 bits.  With s_ij = dot(q_i, k_j) (the same fmaf chain) and
+ * P_i = { j : kgroup[j] == qgroup[i] }:
+ *   d_i      = max_{j in P_i} s_ij, the best positive; NaN if P_i is empty or any s_ij, j in P_i, is NaN
+ *   ranks[i] = 1 + #{ j not in P_i, kcount[j] != 0 : !(s_ij < d_i) }                  (int32 [nq], initialised on s by this call)
+ * kcount: uint8 [nk] or NULL (every key counts).  It never removes a positive from P_i, it only says which non-positives can count
+ * (e.g. one row per group: a gallery of distinct samples).  A key of ANOTHER group that is a bit-identical copy of the best positive
+ * ties and counts; a copy inside the own group never counts.  An empty P_i gives 1 + the number of counted keys.
+ * kgroup_sorted int64 [nk]: kgroup in ascending order; kperm int64 [nk]: the key row each sorted position came from (what a sort of
+ * kgroup returns).  An entry of kperm outside [0, nk) reads no key and makes its group's d_i NaN.
+ * Same limits, the same two launches, nothing allocated, no host wait, deterministic; workspace: mh_retrieval_workspace_bytes(nq, nk, D)
+ * bytes as above.  With all-distinct ids on a square problem and kcount NULL the ranks equal mh_retrieval_ranks' with target NULL. */
+int mh_retrieval_ranks_grouped(const float* q, const float* k, int64_t nq, int64_t nk, int D, const int64_t* qgroup,
+                               const int64_t* kgroup, const int64_t* kgroup_sorted, const int64_t* kperm, const uint8_t* kcount,
+                               int32_t* ranks, void* workspace, mh_stream s);
 
 #ifdef __cplusplus
 }

@@ -179,6 +179,7 @@ _SIGS = {
     "mh_ce_rows_fwd": [P, L, P, F, I, I, I, F, P, P, P],
     "mh_ce_rows_bwd": [P, L, P, F, P, P, I, F, P, P, I, I, I],
     "mh_mse_masked_fwd": [P, P, P, P, L, I, L, L, I, I],
+    "mh_mse_masked_fwd_ordered": [P, P, P, P, L, I, L, L, I, I, P],
     "mh_mse_masked_bwd": [P, P, P, P, P, F, P, P, L, I, L, L, I, I, I, P, I],
     "mh_fanout_bwd": [P, P, F, P, P, I, I, I, I],
     "mh_gather_rows": [P, P, P, L, L, L, I],
@@ -224,6 +225,7 @@ _SIGS = {
     "mh_infonce_rows_bwd": [P, L, P, P, P, I, F, F, I, I, P, P],
     "mh_infonce_fold": [P, P, P, P, I, P, P, I, I],
     "mh_retrieval_ranks": [P, P, L, L, I, P, P, P],
+    "mh_retrieval_ranks_grouped": [P, P, L, L, I, P, P, P, P, P, P, P],
 }
 EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "mh_gemm_variant_name", "mh_device_ok", "mh_nys_attn3_ws_floats", "mh_rna_block_workspace_bytes",
                                  "mh_gemm_workspace_bytes", "mh_layernorm_bwd_workspace_bytes", "mh_nys_attn3_workspace_bytes",

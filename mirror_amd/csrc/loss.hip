@@ -72,13 +72,25 @@ extern "C" int mh_ce_rows_bwd(const float* G, int64_t ldg, const float* scale, f
 }
 
 // ------------------------------------------------------------------ masked MSE (retention losses)
+// a block's pair: onto acc with float atomics (part == nullptr; the order of the blocks decides the last bit), or into its own slot
+// of part for mse_fold_kernel to add in block order
+__device__ __forceinline__ void mse_block_out(float* __restrict__ acc, float* __restrict__ part, float num, float den) {
+    if (part) {
+        part[2 * blockIdx.x] = num;
+        part[2 * blockIdx.x + 1] = den;
+    } else {
+        atomicAdd(acc, num);
+        atomicAdd(acc + 1, den);
+    }
+}
+
 // acc[0] += sum_r mask[r] * (1/D) sum_d (p-t)^2 ; acc[1] += sum_r mask[r]; one wave per row, grid-stride.
 // pred is [rows, D] contiguous; row r of the target sits at tgt + (r / rpb) * tgt_bs + (r % rpb) * D (a row window of a
 // larger [B, T, D] buffer: the WSI target is encoder_output[:, 1:], models/mirror.py:700).
 template <typename TP, typename TT, bool VEC>
 __global__ __launch_bounds__(256) void mse_masked_fwd_kernel(const TP* __restrict__ pred, const TT* __restrict__ tgt,
                                                              const float* __restrict__ mask, float* __restrict__ acc, long rows, int D,
-                                                             long rpb, long tgt_bs) {
+                                                             long rpb, long tgt_bs, float* __restrict__ part) {
     __shared__ float red[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long nw = (long)gridDim.x * 4;
@@ -121,13 +133,14 @@ __global__ __launch_bounds__(256) void mse_masked_fwd_kernel(const TP* __restric
     }
     num = block_sum256(num, red);
     den = block_sum256(lane == 0 ? den : 0.f, red);
-    if (threadIdx.x == 0) { atomicAdd(acc, num); atomicAdd(acc + 1, den); }
+    if (threadIdx.x == 0) mse_block_out(acc, part, num, den);
 }
 
 // D == 1 (RNA retention loss: the channel axis is the masked axis): a flat reduction, one element per thread iteration
 template <typename TP, typename TT>
 __global__ __launch_bounds__(256) void mse_masked_fwd_flat_kernel(const TP* __restrict__ pred, const TT* __restrict__ tgt,
-                                                                  const float* __restrict__ mask, float* __restrict__ acc, long n) {
+                                                                  const float* __restrict__ mask, float* __restrict__ acc, long n,
+                                                                  float* __restrict__ part) {
     __shared__ float red[4];
     float num = 0.f, den = 0.f;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
@@ -137,7 +150,22 @@ __global__ __launch_bounds__(256) void mse_masked_fwd_flat_kernel(const TP* __re
     }
     num = block_sum256(num, red);
     den = block_sum256(den, red);
-    if (threadIdx.x == 0) { atomicAdd(acc, num); atomicAdd(acc + 1, den); }
+    if (threadIdx.x == 0) mse_block_out(acc, part, num, den);
+}
+
+// acc += the blocks' pairs of part in block order: one wave, lane l takes blocks l, l + 64, ... in turn, then a fixed butterfly
+__global__ __launch_bounds__(64) void mse_fold_kernel(const float* __restrict__ part, int nb, float* __restrict__ acc) {
+    float num = 0.f, den = 0.f;
+    for (int b = threadIdx.x; b < nb; b += 64) {
+        num += part[2 * b];
+        den += part[2 * b + 1];
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        num += __shfl_xor(num, o);
+        den += __shfl_xor(den, o);
+    }
+    if (threadIdx.x == 0) { acc[0] += num; acc[1] += den; }
 }
 
 // dpred = k mask (p - t) in TD; dtgt = -dpred in TT when the caller wants it materialised (nullptr: not written)
@@ -248,34 +276,57 @@ __global__ __launch_bounds__(256) void mse_masked_bwd_cs_kernel(const TP* __rest
     }
 }
 
-extern "C" int mh_mse_masked_fwd(const void* pred, const void* tgt, const float* mask, float* acc, int64_t rows, int D,
-                                 int64_t rows_per_batch, int64_t tgt_bs, int dt_p, int dt_t, mh_stream s) {
-    if (rows == 0) return MH_OK;
+// part == nullptr: the atomics of mh_mse_masked_fwd; otherwise the blocks' pairs go to part and *nblocks says how many there are
+static int mse_masked_fwd_launch(const void* pred, const void* tgt, const float* mask, float* acc, int64_t rows, int D,
+                                 int64_t rows_per_batch, int64_t tgt_bs, int dt_p, int dt_t, float* part, int* nblocks, mh_stream s) {
     MH_REQUIRE(rows_per_batch > 0, "mh_mse_masked_fwd: rows_per_batch must be positive");
     if (D == 1 && tgt_bs == rows_per_batch) {       // contiguous [rows] vectors
         dim3 gf((unsigned)min((long)mh_cdiv(rows, 256), 64L));
-#define MSEFL(TP, TT) hipLaunchKernelGGL((mse_masked_fwd_flat_kernel<TP, TT>), gf, dim3(256), 0, (hipStream_t)s, (const TP*)pred, (const TT*)tgt, mask, acc, (long)rows)
+#define MSEFL(TP, TT) hipLaunchKernelGGL((mse_masked_fwd_flat_kernel<TP, TT>), gf, dim3(256), 0, (hipStream_t)s, (const TP*)pred, (const TT*)tgt, mask, acc, (long)rows, part)
         if (dt_p == MH_F32 && dt_t == MH_F32) { MSEFL(float, float); }
         else if (dt_p == MH_BF16 && dt_t == MH_BF16) { MSEFL(bf16_t, bf16_t); }
         else if (dt_p == MH_F32) { MSEFL(float, bf16_t); }
         else { MSEFL(bf16_t, float); }
 #undef MSEFL
         MH_LAUNCH_CHECK("mh_mse_masked_fwd");
+        *nblocks = (int)gf.x;
         return MH_OK;
     }
     dim3 grid((unsigned)min((long)mh_cdiv(rows, 16), 1024L));
     const bool vec = D % 4 == 0 && tgt_bs % 4 == 0 && mh_quad_ok(pred, mh_dt_size(dt_p)) && mh_quad_ok(tgt, mh_dt_size(dt_t));
 #define MSEF(TP, TT)                                                                                                              \
-    if (vec) hipLaunchKernelGGL((mse_masked_fwd_kernel<TP, TT, true>), grid, dim3(256), 0, (hipStream_t)s, (const TP*)pred, (const TT*)tgt, mask, acc, (long)rows, D, (long)rows_per_batch, (long)tgt_bs); \
-    else hipLaunchKernelGGL((mse_masked_fwd_kernel<TP, TT, false>), grid, dim3(256), 0, (hipStream_t)s, (const TP*)pred, (const TT*)tgt, mask, acc, (long)rows, D, (long)rows_per_batch, (long)tgt_bs)
+    if (vec) hipLaunchKernelGGL((mse_masked_fwd_kernel<TP, TT, true>), grid, dim3(256), 0, (hipStream_t)s, (const TP*)pred, (const TT*)tgt, mask, acc, (long)rows, D, (long)rows_per_batch, (long)tgt_bs, part); \
+    else hipLaunchKernelGGL((mse_masked_fwd_kernel<TP, TT, false>), grid, dim3(256), 0, (hipStream_t)s, (const TP*)pred, (const TT*)tgt, mask, acc, (long)rows, D, (long)rows_per_batch, (long)tgt_bs, part)
     if (dt_p == MH_F32 && dt_t == MH_F32) { MSEF(float, float); }
     else if (dt_p == MH_BF16 && dt_t == MH_BF16) { MSEF(bf16_t, bf16_t); }
     else if (dt_p == MH_F32) { MSEF(float, bf16_t); }
     else { MSEF(bf16_t, float); }
 #undef MSEF
     MH_LAUNCH_CHECK("mh_mse_masked_fwd");
+    *nblocks = (int)grid.x;
     return MH_OK;
 }
+
+extern "C" int mh_mse_masked_fwd(const void* pred, const void* tgt, const float* mask, float* acc, int64_t rows, int D,
+                                 int64_t rows_per_batch, int64_t tgt_bs, int dt_p, int dt_t, mh_stream s) {
+    if (rows == 0) return MH_OK;
+    int nb = 0;
+    return mse_masked_fwd_launch(pred, tgt, mask, acc, rows, D, rows_per_batch, tgt_bs, dt_p, dt_t, nullptr, &nb, s);
+}
+
+extern "C" int mh_mse_masked_fwd_ordered(const void* pred, const void* tgt, const float* mask, float* acc, int64_t rows, int D,
+                                         int64_t rows_per_batch, int64_t tgt_bs, int dt_p, int dt_t, float* workspace, mh_stream s) {
+    if (rows == 0) return MH_OK;
+    MH_REQUIRE(workspace && ((uintptr_t)workspace & 3) == 0, "mh_mse_masked_fwd_ordered: workspace must be a 4-byte aligned pointer");
+    int nb = 0;
+    const int rc = mse_masked_fwd_launch(pred, tgt, mask, acc, rows, D, rows_per_batch, tgt_bs, dt_p, dt_t, workspace, &nb, s);
+    if (rc != MH_OK) return rc;
+    MH_REQUIRE(2 * nb <= MH_MSE_FWD_WS_FLOATS, "mh_mse_masked_fwd_ordered: %d blocks exceed the workspace", nb);
+    hipLaunchKernelGGL(mse_fold_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, (const float*)workspace, nb, acc);
+    MH_LAUNCH_CHECK("mh_mse_masked_fwd_ordered");
+    return MH_OK;
+}
+
 
 extern "C" int mh_mse_masked_bwd(const void* pred, const void* tgt, const float* mask, const float* acc, const float* g,
                                  float gmul, void* dpred, void* dtgt, int64_t rows, int D, int64_t rows_per_batch, int64_t tgt_bs,

@@ -576,7 +576,7 @@ class TrainEngine:
     # ------------------------------------------------------------------ validation (train_mirror.py:1382-1526)
     LOSS_NAMES = ("loss", "alignment_loss", "wsi_retention_loss", "rna_retention_loss", "style_loss", "cluster_loss")
 
-    def validate(self, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], noise: Optional[Sequence[dict]] = None,
+    def validate(self, loader: Iterable[Tuple[torch.Tensor, ...]], noise: Optional[Sequence[dict]] = None,
                  model: Optional[torch.nn.Module] = None, retrieval=None) -> "OrderedDict[str, float]":
         """The reference's `validate()`: eval mode (dropout off, masking still on), no autograd, the six losses averaged
         over the loader weighted by batch size (utils.AverageMeter.update(loss, B)) and, under DDP, averaged over ranks
@@ -587,7 +587,10 @@ class TrainEngine:
         train_mirror.py:1022-1037); the engine's model by default.
         retrieval: a `retrieval.CrossModalRetrieval`; it is reset, fed the two alignment embeddings of every batch (this rank's rows,
         also under gather_distributed) and its entries (recall@k, median rank, `r_mean`, ... over the union of all ranks' pairs)
-        are appended behind the six losses, e.g. for `CheckpointSaver(decreasing=False)` on `r_mean`.  None: nothing changes."""
+        are appended behind the six losses, e.g. for `CheckpointSaver(decreasing=False)` on `r_mean`.  None: nothing changes.
+        A batch may carry a third item: an integer [B] tensor, or a dict with the key "group" (what a
+        `DeviceSlideBank(targets={"group": ids})` batch yields), naming the sample each slide belongs to.  With `retrieval` it goes to
+        `retrieval.update(..., group=)` (several slides of one sample: see CrossModalRetrieval); without, it is ignored."""
         net = self.model if model is None else model
         if retrieval is not None:
             retrieval.reset()
@@ -599,7 +602,9 @@ class TrainEngine:
             Fn._fp8_state["sites"] = self._fp8_sites      # this engine's call sites (no tick: the exact two-pass quantisation runs)
         try:
             with torch.no_grad():
-                for i, (wsi, rna) in enumerate(loader):
+                for i, batch in enumerate(loader):
+                    wsi, rna = batch[0], batch[1]
+                    extra = batch[2] if len(batch) > 2 else None
                     wsi = wsi.to(self.device, non_blocking=True)
                     rna = rna.to(self.device, non_blocking=True)
                     net._align_gather = self._align_gather
@@ -610,7 +615,8 @@ class TrainEngine:
                         net._align_gather = None
                     losses = self.loss_fn(*outs)
                     if retrieval is not None:
-                        retrieval.update(outs[0], outs[7])      # the rank-local rows: the gathered ones only exist inside the loss
+                        group = extra["group"] if isinstance(extra, dict) else extra
+                        retrieval.update(outs[0], outs[7], group)      # the rank-local rows: the gathered ones only exist inside the loss
                     b = float(wsi.shape[0])
                     acc[:6] += torch.stack([x.detach().reshape(()) for x in losses]).double() * b
                     acc[6] += b

@@ -1696,11 +1696,18 @@ def _tgt_rows(tgt: torch.Tensor, rows: int, D: int):
     raise MirrorHipError(f"masked-MSE target must be contiguous or a row window, got strides {tgt.stride()}")
 
 
+MSE_FWD_WS_FLOATS = 2048      # MH_MSE_FWD_WS_FLOATS of include/mirror_hip.h
+
+
 def mse_masked_fwd(pred, tgt, mask, acc, rows, D):
+    """acc[0] += sum_r mask[r] * mean_D (pred - tgt)^2, acc[1] += sum_r mask[r], the blocks' partial sums added in block order
+    (mh_mse_masked_fwd_ordered): the same inputs give the same bits on every launch."""
     _chk(pred, tgt, mask, acc)
     assert pred.is_contiguous() and tgt.numel() == pred.numel()
     rpb, tbs = _tgt_rows(tgt, rows, D)
-    _lib.call("mh_mse_masked_fwd", _p(pred), _p(tgt), _p(mask), _p(acc), rows, D, rpb, tbs, dt(pred), dt(tgt), stream=_stream())
+    ws = torch.empty((MSE_FWD_WS_FLOATS,), device=pred.device, dtype=torch.float32)
+    _lib.call("mh_mse_masked_fwd_ordered", _p(pred), _p(tgt), _p(mask), _p(acc), rows, D, rpb, tbs, dt(pred), dt(tgt), _p(ws),
+              stream=_stream())
 
 
 MSE_CS_BLOCKS = 1024      # blocks (= rows of the column-sum table) of mse_masked_bwd(colsum_ws=...)
@@ -2316,4 +2323,55 @@ def retrieval_ranks(q: torch.Tensor, k: torch.Tensor, target: Optional[torch.Ten
     ws_bytes = int(_lib.load().mh_retrieval_workspace_bytes(nq, nk, D))
     ws = torch.empty(((ws_bytes + 3) // 4,), device=q.device, dtype=torch.float32)
     _lib.call("mh_retrieval_ranks", _p(q), _p(k), nq, nk, D, _p(target), _p(ranks), _p(ws), stream=_stream())
+    return ranks
+
+
+def _retrieval_ids(ids: torch.Tensor, n: int, what: str) -> None:
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 1 or ids.numel() != n or ids.dtype not in (torch.int32, torch.int64):
+        got = f"{ids.dtype} {tuple(ids.shape)}" if isinstance(ids, torch.Tensor) else type(ids).__name__
+        raise ValueError(f"retrieval_ranks_grouped: {what} must be int32 / int64 [{n}], got {got}")
+
+
+def retrieval_ranks_grouped(q: torch.Tensor, k: torch.Tensor, qgroup: torch.Tensor, kgroup: torch.Tensor,
+                            kcount: Optional[torch.Tensor] = None, key_order=None) -> torch.Tensor:
+    """int32 [nq] on the device (no sync): the rank of the BEST positive of each query among the keys of other groups.  The positives
+    of query i are the keys j with kgroup[j] == qgroup[i] (ids compared for equality only, all 64 bits; int32 ids are widened):
+        d[i] = max over them of q[i] . k[j]  (NaN if there is none, or if one of them is NaN),
+        ranks[i] = 1 + #{j of another group with kcount[j] != 0: not (q[i] . k[j] < d[i])}.
+    kcount (bool or integer [nk], None: every key counts) never removes a positive; it only says which other keys can count.  Ties and
+    NaN count against the query as in retrieval_ranks; a copy of the best positive in the query's own group does not.  q f32 [nq, D],
+    k f32 [nk, D] on the device; the ids may come from the host.  The keys are ordered by group with one stable device sort (no sync);
+    key_order = torch.sort(kgroup as int64 on the device, stable=True) hands over a sort the caller already has."""
+    if q.dim() != 2 or k.dim() != 2 or q.shape[1] != k.shape[1]:
+        raise ValueError(f"retrieval_ranks_grouped: q [nq, D] and k [nk, D] must share D, got {tuple(q.shape)} and {tuple(k.shape)}")
+    nq, D = q.shape
+    nk = k.shape[0]
+    _retrieval_ids(qgroup, nq, "qgroup")
+    _retrieval_ids(kgroup, nk, "kgroup")
+    if kcount is not None and (not isinstance(kcount, torch.Tensor) or kcount.dim() != 1 or kcount.numel() != nk
+                               or kcount.is_floating_point() or kcount.is_complex()):
+        got = f"{kcount.dtype} {tuple(kcount.shape)}" if isinstance(kcount, torch.Tensor) else type(kcount).__name__
+        raise ValueError(f"retrieval_ranks_grouped: kcount must be a bool / integer [{nk}], got {got}")
+    _chk(q, k)
+    if q.dtype != torch.float32 or k.dtype != torch.float32:
+        raise MirrorHipError(f"retrieval_ranks_grouped: q and k must be f32 (ranks decided by a bf16 rounding are not a metric), got {q.dtype}, {k.dtype}")
+    if not (1 <= nq <= (1 << 20)) or not (1 <= nk <= (1 << 20)) or not (1 <= D <= 4096):
+        raise MirrorHipError(f"retrieval_ranks_grouped: nq = {nq}, nk = {nk} (1..2^20), D = {D} (1..4096)")
+    q, k = q.detach().contiguous(), k.detach().contiguous()
+    qgroup = qgroup.to(device=q.device, dtype=torch.int64, non_blocking=True).contiguous()
+    kgroup = kgroup.to(device=q.device, dtype=torch.int64, non_blocking=True).contiguous()
+    if kcount is not None:
+        kcount = (kcount.to(device=q.device, non_blocking=True) != 0).to(torch.uint8).contiguous()
+    if key_order is None:
+        key_order = torch.sort(kgroup, stable=True)
+    sgroup, perm = key_order
+    for t, what in ((sgroup, "sorted ids"), (perm, "permutation")):
+        if t.dtype != torch.int64 or tuple(t.shape) != (nk,) or t.device != q.device:
+            raise ValueError(f"retrieval_ranks_grouped: key_order's {what} must be int64 [{nk}] on {q.device}")
+    sgroup, perm = sgroup.contiguous(), perm.contiguous()
+    ranks = torch.empty((nq,), device=q.device, dtype=torch.int32)
+    ws_bytes = int(_lib.load().mh_retrieval_workspace_bytes(nq, nk, D))
+    ws = torch.empty(((ws_bytes + 3) // 4,), device=q.device, dtype=torch.float32)
+    _lib.call("mh_retrieval_ranks_grouped", _p(q), _p(k), nq, nk, D, _p(qgroup), _p(kgroup), _p(sgroup), _p(perm), _p(kcount), _p(ranks),
+              _p(ws), stream=_stream())
     return ranks

@@ -210,7 +210,8 @@ def _gather_var(t: torch.Tensor, group, via_host: bool) -> List[torch.Tensor]:
 def sync_and_compute(metric, process_group=None):
     """torcheval.metrics.toolkit.sync_and_compute: merge the metric's state over the ranks of `process_group` (torch.distributed)
     and compute it on every rank.  The caller's metric is left as it was.  On a gloo group the state goes through the host.
-    Also takes a `retrieval.CrossModalRetrieval` (both embedding sets are gathered; the result is its OrderedDict)."""
+    Also takes a `retrieval.CrossModalRetrieval` (both embedding sets, and the group ids if it has them, are gathered; the result is
+    its OrderedDict)."""
     import copy
 
     import torch.distributed as dist
@@ -240,12 +241,21 @@ def sync_and_compute(metric, process_group=None):
     if isinstance(metric, CrossModalRetrieval):
         # every rank ranks over the UNION: the gallery size is part of the metric, so per-rank values averaged afterwards would be
         # another (easier) metric.  A rank without samples learns the width from the others.
-        D = torch.tensor([metric.wsi[0].shape[1] if metric.wsi else 0], dtype=torch.int64, device="cpu" if via_host else metric.device)
+        # The same for the group ids: a rank with samples either has them or not, and all such ranks must agree.
+        D = torch.tensor([metric.wsi[0].shape[1] if metric.wsi else 0, int(bool(metric.group)), int(bool(metric.wsi) and not metric.group)],
+                         dtype=torch.int64, device="cpu" if via_host else metric.device)
         dist.all_reduce(D, op=dist.ReduceOp.MAX, group=process_group)
-        empty = torch.empty((0, int(D)), dtype=torch.float32, device=metric.device)
+        D, grouped, plain = (int(v) for v in D.cpu())
+        if grouped and plain:
+            raise ValueError("sync_and_compute: some ranks fed the retrieval metric group ids and others did not")
+        empty = torch.empty((0, D), dtype=torch.float32, device=metric.device)
         w, r = metric._cat() if metric.wsi else (empty, empty)
         merged.wsi = [t for t in _gather_var(w, process_group, via_host) if t.shape[0]]
         merged.rna = [t for t in _gather_var(r, process_group, via_host) if t.shape[0]]
+        merged.group = []
+        if grouped:       # ids mean the same on every rank: a sample whose slides sit on different ranks is one group of the union
+            g = torch.cat(metric.group) if metric.group else torch.empty((0,), dtype=torch.int64, device=metric.device)
+            merged.group = [t for t in _gather_var(g, process_group, via_host) if t.shape[0]]
         return merged.compute()
     raise TypeError(f"sync_and_compute: unsupported metric {type(metric).__name__}")
 

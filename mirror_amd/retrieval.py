@@ -6,7 +6,12 @@ The ranks come from `mh_retrieval_ranks` (csrc/retrieval.hip): a fused exact-f32
 [n, n] similarity matrix never exists.  The rule is pessimistic: a key that ties with the positive, or a NaN on either side,
 counts against the query, so a collapsed encoder scores rank n everywhere, never rank 1.
 
-Not built: more than one positive per query, bf16 keys, both directions from one pass over the similarities.
+Several positives per query (`mh_retrieval_ranks_grouped`): the pretraining set has one item per SLIDE and looks its RNA row up by the
+sample barcode, so a sample with three slides is in a validation set three times with the same RNA vector.  Given a group id per
+pair (the sample's row in the RNA table), a query's positives are all keys of its group and its rank is that of the best of them
+among the keys of other groups; the slide -> RNA gallery is the distinct samples, and RNA -> slide counts each sample once.
+
+Not built: bf16 keys, both directions from one pass over the similarities.
 """
 from __future__ import annotations
 
@@ -19,7 +24,7 @@ import torch
 from . import kernels as K
 from ._lib import MirrorHipError
 
-__all__ = ["retrieval_ranks", "summarize_ranks", "CrossModalRetrieval"]
+__all__ = ["retrieval_ranks", "summarize_ranks", "first_of_group", "CrossModalRetrieval"]
 
 
 def _l2(x: torch.Tensor) -> torch.Tensor:
@@ -31,11 +36,22 @@ def _l2(x: torch.Tensor) -> torch.Tensor:
 
 
 def retrieval_ranks(query: torch.Tensor, key: torch.Tensor, target: Optional[torch.Tensor] = None,
-                    normalize: bool = False) -> torch.Tensor:
+                    query_group: Optional[torch.Tensor] = None, key_group: Optional[torch.Tensor] = None,
+                    key_count: Optional[torch.Tensor] = None, normalize: bool = False) -> torch.Tensor:
     """int32 [nq] on the device, no host sync: the rank (1 = best) of key[target[i]] among all keys by query[i] . key[j]; `target`
     None pairs row i with row i.  normalize=True compares cosines (both sides through mh_l2norm_fwd first), which is what
     `InfoNCE` trains; the default compares the raw dot products, as `ClipLoss` does with the projected embeddings.
-    See kernels.retrieval_ranks for the checks and the pessimistic tie / NaN rule."""
+    See kernels.retrieval_ranks for the checks and the pessimistic tie / NaN rule.
+    query_group [nq], key_group [nk] (integer ids, both or neither; not together with `target`): the positives of query i are all
+    keys of its group and the rank is that of the best of them among the keys of OTHER groups for which key_count [nk] (None: all)
+    is not 0; see kernels.retrieval_ranks_grouped."""
+    grouped = query_group is not None or key_group is not None
+    if grouped and target is not None:
+        raise ValueError("retrieval_ranks: `target` names one positive per query, the groups name several: pass one or the other")
+    if grouped and (query_group is None or key_group is None):
+        raise ValueError("retrieval_ranks: query_group and key_group go together")
+    if key_count is not None and not grouped:
+        raise ValueError("retrieval_ranks: key_count needs query_group and key_group")
     if normalize:
         if query.dim() != 2 or key.dim() != 2:
             raise ValueError(f"retrieval_ranks: query and key must be [n, D], got {tuple(query.shape)} and {tuple(key.shape)}")
@@ -44,6 +60,8 @@ def retrieval_ranks(query: torch.Tensor, key: torch.Tensor, target: Optional[tor
             raise MirrorHipError(f"retrieval_ranks: query and key must be f32, got {query.dtype}, {key.dtype}")
         if query.shape[0] and key.shape[0] and query.shape[1] == key.shape[1] and query.shape[1] >= 1:
             query, key = _l2(query), _l2(key)
+    if grouped:
+        return K.retrieval_ranks_grouped(query, key, query_group, key_group, key_count)
     return K.retrieval_ranks(query, key, target)
 
 
@@ -60,12 +78,33 @@ def summarize_ranks(ranks, ks: Sequence[int] = (1, 5, 10)) -> "OrderedDict[str, 
     return out
 
 
+def first_of_group(sorted_ids, perm):
+    """bool [n] in the original order: True on the first row of every group, from a STABLE ascending sort of the ids (the sorted
+    ids and the permutation, as torch.sort or numpy's argsort(kind="stable") give them).  Torch tensors or numpy arrays."""
+    if isinstance(sorted_ids, torch.Tensor):
+        head = torch.ones_like(sorted_ids, dtype=torch.bool)
+        head[1:] = sorted_ids[1:] != sorted_ids[:-1]
+        return torch.zeros_like(head).scatter_(0, perm, head)
+    sorted_ids, perm = np.asarray(sorted_ids), np.asarray(perm)
+    head = np.ones(sorted_ids.shape, dtype=bool)
+    head[1:] = sorted_ids[1:] != sorted_ids[:-1]
+    out = np.zeros(sorted_ids.shape, dtype=bool)
+    out[perm] = head
+    return out
+
+
 class CrossModalRetrieval:
     """Slide -> RNA and RNA -> slide retrieval over every pair accumulated so far, shaped like the classes of `metrics`:
     `update(wsi_emb, rna_emb)` keeps f32 copies on the device and never waits on the host; `compute()` launches both directions,
     reads the two rank vectors back in one sync and returns an OrderedDict of `wsi2rna_r@k..`, `wsi2rna_medr`, `wsi2rna_meanr`,
     the same for `rna2wsi_`, `r_mean` (the mean of all r@k over both directions: the scalar to select checkpoints on) and
-    `retrieval_n` (the gallery size, which the values depend on).  Recalls are fractions in [0, 1]."""
+    `retrieval_n` (the gallery size, which the values depend on).  Recalls are fractions in [0, 1].
+
+    With `update(..., group=ids)` (every update, or none) pairs of one group are slides of one sample.  wsi2rna: every slide is a
+    query, its positives are its group's RNA rows and the gallery is the first RNA row of each of the G groups.  rna2wsi: the keys
+    are all slides, a query's positives are its group's slides, and the ranks are summarised over the first row of each group, so a
+    sample counts once however many slides it has.  `retrieval_groups` = G follows `retrieval_n` = the number of slides.  With
+    all-distinct ids every value equals the ungrouped one."""
 
     def __init__(self, ks: Sequence[int] = (1, 5, 10), normalize: bool = False, device=None):
         ks = tuple(int(k) for k in ks)
@@ -79,15 +118,26 @@ class CrossModalRetrieval:
         self.device = d
         self.wsi: List[torch.Tensor] = []             # f32 [n_i, D] per update
         self.rna: List[torch.Tensor] = []
+        self.group: List[torch.Tensor] = []           # int64 [n_i] per update, or none at all
 
-    def update(self, wsi_emb: torch.Tensor, rna_emb: torch.Tensor) -> "CrossModalRetrieval":
-        """wsi_emb, rna_emb: the two alignment embeddings [B, D] of the same B pairs, row i with row i."""
+    def update(self, wsi_emb: torch.Tensor, rna_emb: torch.Tensor, group: Optional[torch.Tensor] = None) -> "CrossModalRetrieval":
+        """wsi_emb, rna_emb: the two alignment embeddings [B, D] of the same B pairs, row i with row i.  group: an integer [B]
+        tensor on the device or the host, the sample each pair belongs to (ids that mean the same on every rank)."""
         if wsi_emb.dim() != 2 or tuple(wsi_emb.shape) != tuple(rna_emb.shape):
             raise ValueError(f"wsi_emb and rna_emb must both be [B, D], got {tuple(wsi_emb.shape)} and {tuple(rna_emb.shape)}")
         if not (wsi_emb.is_floating_point() and rna_emb.is_floating_point()):
             raise ValueError(f"embeddings must be floating point, got {wsi_emb.dtype} and {rna_emb.dtype}")
         if self.wsi and self.wsi[0].shape[1] != wsi_emb.shape[1]:
             raise ValueError(f"embedding width changed from {self.wsi[0].shape[1]} to {wsi_emb.shape[1]}")
+        if group is not None and (not isinstance(group, torch.Tensor) or group.dim() != 1 or group.numel() != wsi_emb.shape[0]
+                                  or group.dtype not in (torch.int32, torch.int64)):
+            got = f"{group.dtype} {tuple(group.shape)}" if isinstance(group, torch.Tensor) else type(group).__name__
+            raise ValueError(f"group must be an int32 / int64 [{wsi_emb.shape[0]}] tensor, got {got}")
+        if self.wsi and (group is not None) != bool(self.group):
+            raise ValueError("either every update() passes `group` or none does: this one " +
+                             ("does, the earlier ones did not" if group is not None else "does not, the earlier ones did"))
+        if group is not None:
+            self.group.append(group.detach().to(device=self.device, dtype=torch.int64, non_blocking=True, copy=True))
         for store, x in ((self.wsi, wsi_emb), (self.rna, rna_emb)):
             store.append(x.detach().to(device=self.device, dtype=torch.float32, non_blocking=True, copy=True))
         return self
@@ -104,7 +154,17 @@ class CrossModalRetrieval:
         w, r = self._cat()
         if self.normalize:
             w, r = _l2(w), _l2(r)
-        both = torch.stack((K.retrieval_ranks(w, r), K.retrieval_ranks(r, w))).cpu().numpy()
+        groups = None
+        if self.group:
+            g = self.group[0] if len(self.group) == 1 else torch.cat(self.group)
+            order = torch.sort(g, stable=True)
+            first = first_of_group(*order)
+            both = torch.stack((K.retrieval_ranks_grouped(w, r, g, g, first, key_order=order),
+                                K.retrieval_ranks_grouped(r, w, g, g, None, key_order=order), first.to(torch.int32))).cpu().numpy()
+            heads = both[2] != 0
+            both, groups = (both[0], both[1][heads]), int(heads.sum())
+        else:
+            both = torch.stack((K.retrieval_ranks(w, r), K.retrieval_ranks(r, w))).cpu().numpy()
         out: "OrderedDict[str, float]" = OrderedDict()
         recalls = []
         for name, ranks in (("wsi2rna", both[0]), ("rna2wsi", both[1])):
@@ -114,16 +174,21 @@ class CrossModalRetrieval:
                     recalls.append(v)
         out["r_mean"] = float(np.mean(recalls))
         out["retrieval_n"] = n
+        if groups is not None:
+            out["retrieval_groups"] = groups
         return out
 
     def reset(self) -> "CrossModalRetrieval":
-        self.wsi, self.rna = [], []
+        self.wsi, self.rna, self.group = [], [], []
         return self
 
     def merge_state(self, metrics: Iterable["CrossModalRetrieval"]) -> "CrossModalRetrieval":
         for m in metrics:
             if m.wsi and self.wsi and m.wsi[0].shape[1] != self.wsi[0].shape[1]:
                 raise ValueError(f"cannot merge retrieval states of widths {m.wsi[0].shape[1]} and {self.wsi[0].shape[1]}")
+            if m.wsi and self.wsi and bool(m.group) != bool(self.group):
+                raise ValueError("cannot merge a retrieval state with group ids and one without")
             self.wsi.extend(t.to(self.device) for t in m.wsi)
             self.rna.extend(t.to(self.device) for t in m.rna)
+            self.group.extend(t.to(self.device) for t in m.group)
         return self
