@@ -798,23 +798,6 @@ def _linear_rows_bwd(ctx_needs, x, wa, w, b, r0, R, prec, dy, dx_dtype=None, def
 _DROP_IN_LN_BWD = True      # (test hook, round 5) to_out's Dropout backward + bias gradient inside the LayerNorm backward that produces its dy
 
 
-class _DropSite:
-    """Hand-over between ToOutDropAddFn and the LayerNorm that reads its output: the forward leaves the Dropout's stream coordinates, the
-    LayerNorm's backward (whose dx is the Dropout's upstream gradient) leaves grad = (data_ptr of that dx, masked bf16 gradient, its column
-    sums [N] f32) for ToOutDropAddFn.backward."""
-    __slots__ = ("p", "seed", "offset", "base", "shape", "grad")
-
-    def __init__(self):
-        self.p = self.seed = self.offset = self.base = self.shape = self.grad = None
-
-    def fill(self, p, seed, offset, base, shape):
-        self.p, self.seed, self.offset, self.base, self.shape = p, seed, offset, base, tuple(shape)
-
-
-# (the site travels ON the output tensor — `out._drop_site`, read by LayerNormFn.forward — not in a table keyed by its address: a stale
-#  address entry could meet an unrelated tensor once the allocator recycles the block, ADVICE r4)
-
-
 class _Link:
     __slots__ = ()
 
@@ -823,6 +806,57 @@ class _Link:
         v = getattr(self, name)
         setattr(self, name, None)
         return v
+
+
+# Test hook in the style of _dropout_tap: while this is a list, every _Handover appends (which, "offered" | "accepted" | "rejected").
+_handover_tap: Optional[list] = None
+
+
+class _Handover(_Link):
+    """A by-product of a gradient tensor g (a masked bf16 copy, column sums), left by the backward node whose kernel wrote g for the node
+    whose backward receives it.  offer(g, *by) comes behind the last torch-side write to g; claim(dy) gives `by` back once, and only
+    when dy is g untouched: same storage address, shape, strides and dtype, and the version counter g had at the offer.  `held` keeps g
+    alive until then, so its address cannot be recycled, and autograd cannot sum another consumer's gradient into it in place (it does
+    that only to a buffer nobody else holds): the sum arrives as another tensor, and an in-place hook at another version.  Raw kernel
+    launches do not move the version counter.  On None the taker runs its own pass."""
+    __slots__ = ("which", "held")
+
+    def __init__(self, which: str):
+        self.which, self.held = which, None
+
+    def offer(self, g: torch.Tensor, *by) -> None:
+        self.held = (g, g._version, by)
+        if _handover_tap is not None:
+            _handover_tap.append((self.which, "offered"))
+
+    def claim(self, dy: torch.Tensor):
+        held = self.take("held")
+        if held is None:
+            return None
+        g, version, by = held
+        ok = (dy.data_ptr() == g.data_ptr() and dy.shape == g.shape and dy.stride() == g.stride() and dy.dtype == g.dtype
+              and dy._version == version)
+        if _handover_tap is not None:
+            _handover_tap.append((self.which, "accepted" if ok else "rejected"))
+        return by if ok else None
+
+
+class _DropSite(_Handover):
+    """Hand-over between ToOutDropAddFn and the LayerNorm that reads its output: the forward leaves the Dropout's stream coordinates, the
+    LayerNorm's backward (whose dx is the Dropout's upstream gradient) offers (masked bf16 gradient, its column sums [N] f32) with that
+    dx for ToOutDropAddFn.backward to claim."""
+    __slots__ = ("p", "seed", "offset", "base", "shape")
+
+    def __init__(self):
+        super().__init__("drop")
+        self.p = self.seed = self.offset = self.base = self.shape = None
+
+    def fill(self, p, seed, offset, base, shape):
+        self.p, self.seed, self.offset, self.base, self.shape = p, seed, offset, base, tuple(shape)
+
+
+# (the site travels ON the output tensor — `out._drop_site`, read by LayerNormFn.forward — not in a table keyed by its address: a stale
+#  address entry could meet an unrelated tensor once the allocator recycles the block, ADVICE r4)
 
 
 class NystromLink(_Link):
@@ -847,7 +881,11 @@ class NystromLink(_Link):
 
 class ResidualLink(_Link):
     """Hand-over between the residual add of a pre-norm block x + f(LN(x)) (AddFn, DropoutAddFn, ToOutDropAddFn) and that LayerNorm,
-    made by the block: the add's backward leaves x's gradient tensor in `grad`, the norm's backward adds its own dx INTO it."""
+    made by the block: the add's backward leaves x's gradient tensor in `grad`, the norm's backward adds its own dx INTO it.
+    Precondition: x has exactly two consumers, this add and this norm.  The norm returns no gradient of its own, so autograd hands the
+    add's tensor on with the norm's share already in it.  With a third consumer autograd sums that tensor with the third gradient, and
+    where it does so before the norm's backward has run, the sum misses the norm's share: the link is not sound then, and nothing here
+    detects it (_ReluSlot only operates inside this link)."""
     __slots__ = ("grad",)
 
     def __init__(self):
@@ -892,30 +930,25 @@ class ToOutDropAddFn(Function):
         core, wa, w, b = ctx.saved_tensors
         dy = dy.contiguous()
         db_done, fused_db = None, False
-        site, handed = ctx.site, None
-        if site is not None and site.grad is not None:
-            handed, site.grad = site.grad, None
-            if handed[0] != dy.data_ptr() or tuple(handed[1].shape) != tuple(dy.shape):
-                handed = None       # dy is not the LayerNorm's dx alone (another consumer's gradient was summed in): the plain pass below
+        want_db = b is not None and ctx.needs_input_grad[3]
+        # None when dy is not the LayerNorm's dx alone (another consumer's gradient was summed in, a hook touched it): the plain pass below
+        handed = None if ctx.site is None else ctx.site.claim(dy)
         if handed is not None:
             # the LayerNorm backward that produced dy already wrote the masked bf16 gradient and its column sums (mh_layernorm_bwd_drop)
-            gb = handed[1]
-            if b is not None and ctx.needs_input_grad[3]:
+            gb, cs = handed
+            if want_db:
                 dbuf, sunk = _gbuf(b, (dy.shape[-1],))
-                dbuf.add_(handed[2])
+                dbuf.add_(cs)
                 db_done, fused_db = _gret(b, dbuf, sunk), True
         else:
             gb = torch.empty(dy.shape, device=dy.device, dtype=ctx.prec.act)
-        if handed is not None:
-            pass
-        elif (b is not None and ctx.needs_input_grad[3] and dy.dtype == f32 and gb.dtype == bf16
-                and K.dropout_lite_colsum_ok(dy.shape[-1])):
-            # the same pass leaves the bias gradient (column sums of the masked bf16 gradient): no mh_colsum launch over it
-            dbuf, sunk = _gbuf(b, (dy.shape[-1],))
-            K.dropout_lite_colsum(dy, ctx.p, ctx.seed, ctx.offset, ctx.base, gb, dbuf)
-            db_done, fused_db = _gret(b, dbuf, sunk), True
-        else:
-            K.dropout_lite(dy, ctx.p, ctx.seed, ctx.offset, ctx.base, out=gb)       # masked, scaled gradient of the projection output
+            if want_db and dy.dtype == f32 and gb.dtype == bf16 and K.dropout_lite_colsum_ok(dy.shape[-1]):
+                # the same pass leaves the bias gradient (column sums of the masked bf16 gradient): no mh_colsum launch over it
+                dbuf, sunk = _gbuf(b, (dy.shape[-1],))
+                K.dropout_lite_colsum(dy, ctx.p, ctx.seed, ctx.offset, ctx.base, gb, dbuf)
+                db_done, fused_db = _gret(b, dbuf, sunk), True
+            else:
+                K.dropout_lite(dy, ctx.p, ctx.seed, ctx.offset, ctx.base, out=gb)       # masked, scaled gradient of the projection output
         if ctx.res is not None:
             ctx.res.grad = dy         # the block's LayerNorm accumulates its dx into the residual gradient (ResidualLink)
         needs = list(ctx.needs_input_grad[1:4])
@@ -941,22 +974,14 @@ def to_out_dropout_add(resid, core, w, b, r0: int, R: int, p: float, training: b
     return dropout_add(resid, y, p, training, lite=True, res=res)
 
 
-class _ColsumToken:
-    """Hand-over slot from the pass that writes a Linear's output gradient to that Linear's backward: `ws` [blocks, N] f32 holds the
-    per-block column sums of the gradient tensor whose data_ptr is `ptr` (mh_mse_masked_bwd(colsum_ws=...))."""
-    __slots__ = ("ws", "ptr")
-
-    def __init__(self):
-        self.ws = None
-        self.ptr = 0
-
-
 class HeadSqErrFn(Function):
     """pred = x[:, r0:r0+R] @ W^T + b (bf16) with the masked squared error against `tgt` accumulated by the same launch
     (mh_gemm_epi SQERR): retention_head + the WSI retention MSE of MIRRORLoss.forward (models/mirror.py:698-699,
     losses/mirror_loss.py:98-103).  The accumulator (mh_mse_masked_fwd's [sum of row means, masked rows]) rides on the
-    returned prediction as `pred._sq = (acc, tgt, mask)`; MaskedMSEFn / MirrorLossTermsFn use it instead of their forward
-    pass when they are handed the same target and mask.  The backward is LinearRowsFn's."""
+    returned prediction as `pred._sq = (acc, tgt, mask, their versions)`; MaskedMSEFn / MirrorLossTermsFn use it instead of their
+    forward pass when they are handed the same target and mask, unwritten since (_sq_of).  The backward is LinearRowsFn's; cs_tok
+    (a _Handover, `pred._sq_cs`): the masked-MSE backward that writes dy offers its per-block column sums [blocks, N] f32 with it
+    (mh_mse_masked_bwd(colsum_ws=...))."""
 
     @staticmethod
     def forward(ctx, x, w, b, r0, R, prec, tgt, mask, acc, cs_tok=None):
@@ -978,16 +1003,13 @@ class HeadSqErrFn(Function):
             dy = dy.contiguous()
         if dy.dtype != prec.act:
             dy = K.cast(dy, prec.act)
-        db_table, tok = None, ctx.cs_tok
-        if tok is not None and tok.ws is not None:
-            # the masked-MSE backward that wrote exactly this dy left its column sums per block: that small table is folded into the bias
-            # gradient instead of reading dy again (a dy that is not that tensor — a second consumer of pred — takes the plain colsum).
-            # The fold stays where the colsum launch stood, BEHIND the two products: in front of them it is the one child of the MSE
-            # kernel on this stream, the ragged-row fork moves behind it, and the replayed graph then starts the whole RNA / heads
-            # backward ~1 ms later (device probes, profiles/r05_h_*: +1.2 % of the step for a 7 us launch)
-            if tok.ptr == dy.data_ptr():
-                db_table = tok.ws
-            tok.ws = None
+        # the masked-MSE backward that wrote exactly this dy left its column sums per block: that small table is folded into the bias
+        # gradient instead of reading dy again (a dy that is not that tensor — a second consumer of pred — takes the plain colsum).
+        # The fold stays where the colsum launch stood, BEHIND the two products: in front of them it is the one child of the MSE
+        # kernel on this stream, the ragged-row fork moves behind it, and the replayed graph then starts the whole RNA / heads
+        # backward ~1 ms later (device probes, profiles/r05_h_*: +1.2 % of the step for a 7 us launch)
+        got = None if ctx.cs_tok is None else ctx.cs_tok.claim(dy)
+        db_table = None if got is None else got[0]
         dx, dw, db = _linear_rows_bwd(ctx.needs_input_grad[0:3], x, wa, w, b, ctx.r0, ctx.R, prec, dy, db_table=db_table)
         return dx, dw, db, None, None, None, None, None, None, None
 
@@ -1001,9 +1023,9 @@ def head_sqerr(x, w, b, r0: int, R: int, prec: Precision, tgt, mask):
             and mask.dtype == f32 and mask.is_contiguous() and tuple(mask.shape) == (x.shape[0], R) and R % 256 == 0
             and torch.is_grad_enabled() and K.linear_fused_ok(x, shadow(w, prec), (r0, R))):
         acc = zeros((2,), x.device)
-        tok = _ColsumToken() if (b is not None and _BIAS_IN_PRODUCER) else None
+        tok = _Handover("colsum") if (b is not None and _BIAS_IN_PRODUCER) else None
         y = HeadSqErrFn.apply(x, w, b, r0, R, prec, tgt, mask, acc, tok)
-        y._sq = (acc, tgt, mask)
+        y._sq = (acc, tgt, mask, tgt._version, mask._version)
         y._sq_cs = tok
         return y
     return LinearRowsFn.apply(x, w, b, r0, R, prec, prec.act)
@@ -1016,21 +1038,23 @@ def _cs_of(pred, acc):
 
 
 def _mse_bwd_cs(tok, pred, tgt, dp, D):
-    """(colsum_ws or None): arm the hand-over slot for dp when the kernel can leave the sums."""
+    """(colsum_ws or None): offer the sums with dp when the kernel can leave them."""
     if tok is None or not K.mse_masked_bwd_colsum_ok(pred, tgt, dp, D):
         return None
-    tok.ws, tok.ptr = torch.empty((K.MSE_CS_BLOCKS, D), device=dp.device, dtype=f32), dp.data_ptr()
-    return tok.ws
+    ws = torch.empty((K.MSE_CS_BLOCKS, D), device=dp.device, dtype=f32)
+    tok.offer(dp, ws)
+    return ws
 
 
 def _sq_of(pred, tgt, mask):
-    """The accumulator a HeadSqErrFn launch left for exactly this (prediction, target, mask) triple, or None."""
+    """The accumulator a HeadSqErrFn launch left for exactly this (prediction, target, mask) triple, or None.  The tuple on pred holds
+    the target and the mask (their addresses cannot be recycled) and the versions they had at that launch (their contents can drift)."""
     sq = getattr(pred, "_sq", None)
     if sq is None:
         return None
-    acc, t0, m0 = sq
-    if (t0.data_ptr() == tgt.data_ptr() and tuple(t0.shape) == tuple(tgt.shape) and t0.stride() == tgt.stride()
-            and m0.data_ptr() == mask.data_ptr() and tuple(m0.shape) == tuple(mask.shape)):
+    acc, t0, m0, tv, mv = sq
+    if (t0.data_ptr() == tgt.data_ptr() and tuple(t0.shape) == tuple(tgt.shape) and t0.stride() == tgt.stride() and t0._version == tv
+            and m0.data_ptr() == mask.data_ptr() and tuple(m0.shape) == tuple(mask.shape) and m0._version == mv):
         return acc
     return None
 
@@ -1184,7 +1208,7 @@ class LayerNormFn(Function):
                 if rows < T:
                     gbd[:, rows:].zero_()        # rows the norm never read: their gradient (and its Dropout backward) is zero
                 drop = (gbd, site.p, site.seed, site.offset, site.base, cs)
-                site.grad = (dx.data_ptr(), gbd, cs)
+                site.offer(dx, gbd, cs)      # behind dx's fill above: the launch below does not move dx's version
         K.layernorm_bwd(dy[:, pad:], x, gamma.detach(), mean, rstd, dx, dg, db, Bn, rows, D, T * D, (pad + rows) * D, fan=fan, drop=drop)
         return dx, _gret(gamma, dg, sunk_g), _gret(beta, db, sunk_b), None, None, None, None, None, None, None, None, None
 
@@ -1299,6 +1323,15 @@ class NormQkvLmFn(Function):
         db, sunk_b = _gbuf(beta, (D,))
         dy = dxe[:P].view(Bn, n_p, D)
         gadd = dxe[P:].view(Bn, m, D)
+        rmask, lscale = ctx.rmask, ctx.lscale
+
+        def own_dx(dg, db):      # this norm's dx as a tensor of its own
+            dx = torch.empty_like(x)
+            if rows < T:
+                dx[:, rows:].zero_()         # only the rows the norm never read (a zeros_like of [B, T, D] is a 268 MB fill at config 4)
+            K.layernorm_bwd(dy[:, pad:], x, gamma.detach(), mean, rstd, dx, dg, db, Bn, rows, D, T * D, n_p * D, gadd=gadd, pad=pad, l=l,
+                            row_mask=rmask, lm_scale=lscale)
+            return dx
         G = None if ctx.res is None else ctx.res.take("grad")
         if G is not None and G.numel() == x.numel() and G.dtype == x.dtype and G.is_contiguous():
             # x = Fc1SeqFn's sequence [cls | relu(_fc1(wsi))] (layer 1): the rows behind the cls row leave as the ReLU-masked bf16 gradient
@@ -1309,18 +1342,28 @@ class NormQkvLmFn(Function):
             if nrelu is not None and x.dtype == f32 and prec.act == bf16 and rows == T == nrelu + 1 and ctx.needs_input_grad[0]:
                 dh = torch.empty((Bn, nrelu, D), device=x.device, dtype=bf16)
                 if fc1_b is not None and fc1_b.requires_grad and _BIAS_IN_PRODUCER:
-                    rdb = _gbuf(fc1_b, (D,))      # _fc1's bias gradient = the column sums of dh: a third partial row of this launch
-                rslot.grad = (G.data_ptr(), dh, rdb)
+                    # _fc1's bias gradient = the column sums of dh: a third partial row of this launch, into a buffer of its own —
+                    # Fc1SeqFn.backward adds it to the bias gradient once it has accepted the hand-over
+                    rdb = zeros((D,), x.device)
+                rslot.offer(G, dh, rdb)      # (the launch below accumulates into G: no torch-side write behind this point)
+                # that launch leaves the ReLU rows of G without this norm's share (it goes to dh alone): a taker that rejects dh asks for
+                # it.  Until Fc1SeqFn.backward takes it (the next node but for parameter accumulations) the closure holds x, dxe, mean and
+                # rstd on the slot; after a backward that raised in between, until the graph dies
+                seen = G._version
+
+                def redo():
+                    if G._version != seen:
+                        raise K.MirrorHipError("Fc1SeqFn.backward: the gradient of the sequence was edited in place (a hook?) after layer 1's "
+                                               "LayerNorm backward left its share of the ReLU rows out of it: not supported with "
+                                               "_RELU_IN_LN_BWD (see _ReluSlot)")
+                    return own_dx(zeros((D,), x.device), zeros((D,), x.device))
+                rslot.redo = redo
             K.layernorm_bwd(dy[:, pad:], x, gamma.detach(), mean, rstd, G.view(x.shape), dg, db, Bn, rows, D, T * D, n_p * D,
-                            accumulate_dx=True, gadd=gadd, pad=pad, l=l, relu_out=dh, relu_first=1, relu_db=None if rdb is None else rdb[0],
-                            row_mask=ctx.rmask, lm_scale=ctx.lscale)
+                            accumulate_dx=True, gadd=gadd, pad=pad, l=l, relu_out=dh, relu_first=1, relu_db=rdb,
+                            row_mask=rmask, lm_scale=lscale)
             dx = None
         else:
-            dx = torch.empty_like(x)
-            if rows < T:
-                dx[:, rows:].zero_()         # only the rows the norm never read (a zeros_like of [B, T, D] is a 268 MB fill at config 4)
-            K.layernorm_bwd(dy[:, pad:], x, gamma.detach(), mean, rstd, dx, dg, db, Bn, rows, D, T * D, n_p * D, gadd=gadd, pad=pad, l=l,
-                            row_mask=ctx.rmask, lm_scale=ctx.lscale)
+            dx = own_dx(dg, db)
         return dx, _gret(gamma, dg, sunk_g), _gret(beta, db, sunk_b), None, None, None, None, dw, None, None, None, None, None
 
 
@@ -1384,14 +1427,20 @@ class KeyMask:
 _LM_ROWS = True       # test hook (tests/test_fused_epilogue_gpu.py): False = the landmark kernels on q | k instead of NormQkvLmFn
 _RELU_SQUARE_PAD = True      # (test hook, round 5) ... also when the sequence carries square-pad rows (N no square: config 4, template)
 _RELU_IN_LN_BWD = True      # (test hook, round 5) _fc1's ReLU backward inside layer 1's LayerNorm backward
-class _ReluSlot:
+class _ReluSlot(_Handover):
     """Hand-over between Fc1SeqFn and the LayerNorm + to_qkv node that reads its sequence (carried on the tensor: `seq._relu_slot`):
-    rows 1 .. n of the sequence are a ReLU's output; grad = (data_ptr of the sequence's f32 gradient buffer, the bf16 ReLU-masked gradient
-    layer 1's LayerNorm backward wrote, (bias-gradient buffer, came_from_sink) or None)."""
-    __slots__ = ("n", "bias", "grad")
+    rows 1 .. n of the sequence are a ReLU's output; layer 1's LayerNorm backward offers (the bf16 ReLU-masked gradient it wrote, its
+    column sums [D] f32 or None) with the sequence's f32 gradient buffer for Fc1SeqFn.backward to claim.  That launch writes its share of
+    rows 1 .. n to the bf16 tensor ONLY: redo() runs the plain backward again and returns the norm's dx [B, 1 + n, D] f32, which a
+    taker that rejects the hand-over adds to those rows of what it received.  That is right where what it received holds the buffer's
+    values (a copy, the sum with another consumer's gradient).  Not supported while _RELU_IN_LN_BWD is on: a hook on the sequence that
+    changes its gradient's values — the norm's share of the ReLU rows never passes through it.  redo() raises when the buffer was
+    edited in place; a hook that returns other values out of place (g * 2) cannot be told from a sum and goes wrong silently."""
+    __slots__ = ("n", "bias", "redo")
 
     def __init__(self):
-        self.n = self.bias = self.grad = None
+        super().__init__("relu")
+        self.n = self.bias = self.redo = None
 
 
 def layer_norm_landmarks_ok(x, rows: int, pad: int, l: int, prec: Precision) -> bool:
@@ -1685,18 +1734,17 @@ class Fc1SeqFn(Function):
         D = wa.shape[0]
         dseq = dseq.contiguous()
         # layer 1's LayerNorm backward already wrote relu'(x) * dx as bf16 (rows 1 .. N of dseq are then stale: only the cls row is read
-        # below) and, with it, this Linear's bias gradient (the column sums of that tensor)
-        dh = db_have = None
-        if ctx.slot is not None and ctx.slot.grad is not None:
-            (gptr, gdh, gdb), ctx.slot.grad = ctx.slot.grad, None
-            if gptr == dseq.data_ptr():
-                dh, db_have = gdh, gdb
+        # below) and, with it, this Linear's bias gradient (the column sums of that tensor, in a buffer of their own)
+        redo = None if ctx.slot is None else ctx.slot.take("redo")
+        dh, hdb = (None if ctx.slot is None else ctx.slot.claim(dseq)) or (None, None)
         dcls, sunk_c = _gbuf_n(ctx.cls, (D,))
         if dh is not None:
             K.seq_finish_bwd(dseq, dcls, N + add_len, 0)      # the cls row only: the square-pad rows' fold happens on the handed-over rows
         else:
-            if add_len:
-                dseq = dseq.clone()  # the fold below is in place; autograd owns the incoming buffer
+            if add_len or redo is not None:
+                dseq = dseq.clone()  # the writes below are in place; autograd owns the incoming buffer
+            if redo is not None:     # a rejected hand-over: rows 1 .. lack the LayerNorm's share (see _ReluSlot for what this covers)
+                dseq[:, 1:] += redo()[:, 1:]
             K.seq_finish_bwd(dseq, dcls, N, add_len)
         dcls = _gret(ctx.cls, dcls, sunk_c)
         if dh is not None and tuple(dh.shape) != (Bn, N + add_len, D):
@@ -1714,12 +1762,12 @@ class Fc1SeqFn(Function):
             K.gemm(dh.reshape(Bn * N, D).t(), xa.reshape(Bn * N, Fd), out=dw, accumulate=True,
                    split_k=_split_k_for(Bn * N, D, Fd), mma=prec.mma)
         dw = _gret(w, dw, sunk_w)
-        if db_have is not None:
-            db = _gret(b, *db_have)
+        db, sunk_b = _gbuf(b, (D,))
+        if hdb is not None:
+            db.add_(hdb)         # only now that the hand-over is accepted: a rejected one must leave nothing in the gradient arena
         else:
-            db, sunk_b = _gbuf(b, (D,))
             K.colsum(dh.reshape(Bn * N, D), db)
-            db = _gret(b, db, sunk_b)
+        db = _gret(b, db, sunk_b)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = K.gemm(dh if dh.is_contiguous() else dh.contiguous(), wa, mma=prec.mma, out_dtype=f32)

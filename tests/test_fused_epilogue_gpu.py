@@ -461,7 +461,13 @@ def test_whole_model_round5_fusions_on_off(monkeypatch):
         torch.cuda.synchronize()
         return [float(x) for x in losses], {k: p.grad.detach().clone() for k, p in model.named_parameters()}
 
+    tap = []
+    monkeypatch.setattr(Fn, "_handover_tap", tap)       # the fused paths are the ones that run: every hand-over offered is accepted
     base_l, base_g = run()
+    monkeypatch.setattr(Fn, "_handover_tap", None)
+    offered = sorted(w for w, what in tap if what == "offered")
+    assert sorted(w for w, what in tap if what == "accepted") == offered and set(offered) == {"relu", "drop", "colsum"}, tap
+    assert not [t for t in tap if t[1] == "rejected"], tap
     relu_keys = ("wsi_encoder._fc1.0.weight", "wsi_encoder._fc1.0.bias", "wsi_encoder.cls_token")
     bias_keys = tuple(k for k in base_g if k in ("wsi_encoder._fc1.0.bias", "wsi_encoder.retention_embed.bias",
                                                  "wsi_encoder.retention_head.bias"))
