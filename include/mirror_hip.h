@@ -952,6 +952,27 @@ int64_t mh_retrieval_workspace_bytes(int64_t nq, int64_t nk, int D);
 int mh_retrieval_ranks_grouped(const float* q, const float* k, int64_t nq, int64_t nk, int D, const int64_t* qgroup,
                                const int64_t* kgroup, const int64_t* kgroup_sorted, const int64_t* kperm, const uint8_t* kcount,
                                int32_t* ranks, void* workspace, mh_stream s);
+/* The neighbours themselves: for every query the kk eligible keys with the largest s_ij = dot(q_i, k_j), the same fmaf chain as above
+ * (val is that chain bit for bit, so top-k and ranks are decided by the same numbers whatever the tiling or `parts`).
+ *   idx int32 [nq x kk], val f32 [nq x kk]; slot 0 is the best.  The order is total: the larger s_ij first, equal s_ij by the SMALLER j.
+ *   Key j is eligible for query i unless s_ij is NaN, or (with group ids) kgroup[j] == qgroup[i], compared on all 64 bits.
+ *   Slots beyond the number of eligible keys hold idx = -1, val = -inf (kk > nk is allowed; a NaN query gets all -1).
+ * qgroup int64 [nq], kgroup int64 [nk]: both or neither (NULL), 8-byte aligned.  Leave-one-out over one set: the ids 0 .. n - 1.
+ * 1 <= kk <= 64; nq, nk, D as above.  The nq x nk matrix is never written; nothing is allocated, no host wait, no atomics: deterministic.
+ * The keys are walked in `parts` strips of 128-key tiles, each keeping a list per query, merged by the same order in a second launch.
+ * parts = 0: chosen from nq, nk and the CU count; parts > 0: as given, at most the number of key tiles.  The result does not depend on it.
+ * workspace: mh_retrieval_topk_workspace_bytes(nq, nk, D, kk, parts) bytes (the strips' lists, 8 nq parts kk), 8-byte aligned. */
+int mh_retrieval_topk(const float* q, const float* k, int64_t nq, int64_t nk, int D, int kk, const int64_t* qgroup, const int64_t* kgroup,
+                      int parts, int32_t* idx, float* val, void* workspace, mh_stream s);
+int64_t mh_retrieval_topk_workspace_bytes(int64_t nq, int64_t nk, int D, int kk, int parts);
+/* The kNN vote on a top-k result: idx / val [nq x kk] as above, labels int64 [nk] (8-byte aligned) of the bank, scores f32 [nq x C]:
+ *   w_is        = exp((val[i, s] - val[i, 0]) * inv_temperature)        (val[i, 0] is the row's maximum: exp stays in (0, 1])
+ *   score[i, c] = sum_s [labels[idx[i, s]] == c] w_is / sum_s' w_is'    (both sums in slot order, s' over the contributing slots)
+ * Empty slots (idx < 0; idx >= nk is not read) and labels outside [0, C) contribute nothing; a row without contribution is all zeros,
+ * every other row sums to 1.  inv_temperature = 0 is the unweighted vote.  1 <= kk <= 64, 1 <= C <= 1024, 0 <= inv_temperature < inf.
+ * One wave per query, a fixed order of additions, no atomics. */
+int mh_knn_scores(const int32_t* idx, const float* val, const int64_t* labels, int64_t nq, int64_t nk, int kk, int C,
+                  float inv_temperature, float* scores, mh_stream s);
 
 #ifdef __cplusplus
 }

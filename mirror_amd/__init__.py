@@ -2,7 +2,8 @@
 
 Host side mirrors the reference's Python surface (`models.mirror`, `losses.MIRRORLoss`,
 `losses.InfoNCE`; the survival losses and metric of train_survival.py in `losses` and `survival`; the subtyping losses
-and metrics of train_subtyping.py in `losses` and `metrics`; the zero-shot retrieval metrics of the alignment heads in `retrieval`);
+and metrics of train_subtyping.py in `losses` and `metrics`; the zero-shot retrieval metrics and top-k
+neighbours of the alignment heads in `retrieval`; the kNN probe of frozen embeddings in `knn`);
 all arithmetic runs in hand-written HIP kernels behind the C ABI of `include/mirror_hip.h` (`mirror_amd/lib/libmirror_hip.so`).  There is no CPU fallback.
 """
 from ._lib import MirrorHipError, LIB_PATH  # noqa: F401

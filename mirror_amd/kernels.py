@@ -2326,10 +2326,10 @@ def retrieval_ranks(q: torch.Tensor, k: torch.Tensor, target: Optional[torch.Ten
     return ranks
 
 
-def _retrieval_ids(ids: torch.Tensor, n: int, what: str) -> None:
+def _retrieval_ids(ids: torch.Tensor, n: int, what: str, who: str = "retrieval_ranks_grouped") -> None:
     if not isinstance(ids, torch.Tensor) or ids.dim() != 1 or ids.numel() != n or ids.dtype not in (torch.int32, torch.int64):
         got = f"{ids.dtype} {tuple(ids.shape)}" if isinstance(ids, torch.Tensor) else type(ids).__name__
-        raise ValueError(f"retrieval_ranks_grouped: {what} must be int32 / int64 [{n}], got {got}")
+        raise ValueError(f"{who}: {what} must be int32 / int64 [{n}], got {got}")
 
 
 def retrieval_ranks_grouped(q: torch.Tensor, k: torch.Tensor, qgroup: torch.Tensor, kgroup: torch.Tensor,
@@ -2375,3 +2375,76 @@ def retrieval_ranks_grouped(q: torch.Tensor, k: torch.Tensor, qgroup: torch.Tens
     _lib.call("mh_retrieval_ranks_grouped", _p(q), _p(k), nq, nk, D, _p(qgroup), _p(kgroup), _p(sgroup), _p(perm), _p(kcount), _p(ranks),
               _p(ws), stream=_stream())
     return ranks
+
+
+# ----------------------------------------------------------------------------- top-k retrieval and the kNN vote (csrc/retrieval_topk.hip)
+def retrieval_topk(q: torch.Tensor, k: torch.Tensor, kk: int, qgroup: Optional[torch.Tensor] = None,
+                   kgroup: Optional[torch.Tensor] = None, parts: int = 0):
+    """(val f32 [nq, kk], idx int32 [nq, kk]) on the device (no sync): for every query the kk eligible keys with the largest q[i] . k[j],
+    best first, equal similarities by the smaller key index.  Key j is eligible for query i unless the similarity is NaN or, with
+    qgroup [nq] / kgroup [nk] (int32 / int64, both or neither; int32 ids are widened, the host's are copied over), kgroup[j] == qgroup[i].
+    Slots beyond the eligible keys hold idx -1, val -inf.  val is the f32 fmaf chain retrieval_ranks decides by, bit for bit.
+    q f32 [nq, D], k f32 [nk, D] on the device, 1 <= kk <= 64 (kk > nk is allowed).  parts: the number of key strips (0: the library
+    chooses; the result does not depend on it).  The [nq, nk] similarities are never stored: the allocations are the two results and
+    the strips' lists [nq, parts, kk]."""
+    if q.dim() != 2 or k.dim() != 2 or q.shape[1] != k.shape[1]:
+        raise ValueError(f"retrieval_topk: q [nq, D] and k [nk, D] must share D, got {tuple(q.shape)} and {tuple(k.shape)}")
+    nq, D = q.shape
+    nk = k.shape[0]
+    if isinstance(kk, bool) or not isinstance(kk, int) or not (1 <= kk <= 64):
+        raise ValueError(f"retrieval_topk: kk must be an int in [1, 64], got {kk!r}")
+    if isinstance(parts, bool) or not isinstance(parts, int) or parts < 0:
+        raise ValueError(f"retrieval_topk: parts must be an int >= 0, got {parts!r}")
+    if (qgroup is None) != (kgroup is None):
+        raise ValueError("retrieval_topk: qgroup and kgroup go together")
+    if qgroup is not None:
+        _retrieval_ids(qgroup, nq, "qgroup", "retrieval_topk")
+        _retrieval_ids(kgroup, nk, "kgroup", "retrieval_topk")
+    _chk(q, k)
+    if q.dtype != torch.float32 or k.dtype != torch.float32:
+        raise MirrorHipError(f"retrieval_topk: q and k must be f32 (neighbours decided by a bf16 rounding are not a metric), got {q.dtype}, {k.dtype}")
+    if not (1 <= nq <= (1 << 20)) or not (1 <= nk <= (1 << 20)) or not (1 <= D <= 4096):
+        raise MirrorHipError(f"retrieval_topk: nq = {nq}, nk = {nk} (1..2^20), D = {D} (1..4096)")
+    q, k = q.detach().contiguous(), k.detach().contiguous()
+    if qgroup is not None:
+        qgroup = qgroup.to(device=q.device, dtype=torch.int64, non_blocking=True).contiguous()
+        kgroup = kgroup.to(device=q.device, dtype=torch.int64, non_blocking=True).contiguous()
+    idx = torch.empty((nq, kk), device=q.device, dtype=torch.int32)
+    val = torch.empty((nq, kk), device=q.device, dtype=torch.float32)
+    ws_bytes = int(_lib.load().mh_retrieval_topk_workspace_bytes(nq, nk, D, kk, parts))
+    ws = torch.empty(((ws_bytes + 7) // 8,), device=q.device, dtype=torch.int64)
+    _lib.call("mh_retrieval_topk", _p(q), _p(k), nq, nk, D, kk, _p(qgroup), _p(kgroup), parts, _p(idx), _p(val), _p(ws), stream=_stream())
+    return val, idx
+
+
+def knn_scores(idx: torch.Tensor, val: torch.Tensor, labels: torch.Tensor, num_classes: int, inv_temperature: float) -> torch.Tensor:
+    """f32 [nq, C] on the device (no sync): the temperature-weighted vote of a retrieval_topk result,
+        score[i, c] = sum_s [labels[idx[i, s]] == c] exp((val[i, s] - val[i, 0]) inv_temperature) / the row's total,
+    summed in slot order.  Empty slots (idx -1) and labels outside [0, C) contribute nothing, a row without contribution is all zeros,
+    every other row sums to 1; inv_temperature = 0 is the unweighted vote.  idx int32 [nq, kk], val f32 [nq, kk] on the device, labels
+    int32 / int64 [nk] (the bank's; the host's are copied over), 1 <= kk <= 64, 1 <= C <= 1024."""
+    if not isinstance(idx, torch.Tensor) or not isinstance(val, torch.Tensor) or idx.dim() != 2 or tuple(idx.shape) != tuple(val.shape):
+        raise ValueError("knn_scores: idx and val must both be [nq, kk]")
+    if idx.dtype != torch.int32 or val.dtype != torch.float32:
+        raise ValueError(f"knn_scores: idx must be int32 and val f32, got {idx.dtype}, {val.dtype}")
+    nq, kk = idx.shape
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 1 or labels.dtype not in (torch.int32, torch.int64):
+        got = f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, torch.Tensor) else type(labels).__name__
+        raise ValueError(f"knn_scores: labels must be an int32 / int64 [nk] tensor, got {got}")
+    nk = labels.numel()
+    C = num_classes
+    if isinstance(C, bool) or not isinstance(C, int) or not (1 <= C <= 1024):
+        raise ValueError(f"knn_scores: num_classes must be an int in [1, 1024], got {C!r}")
+    if not (1 <= kk <= 64):
+        raise ValueError(f"knn_scores: kk = {kk} outside [1, 64]")
+    inv_t = float(inv_temperature)
+    if not (0.0 <= inv_t < float("inf")):
+        raise ValueError(f"knn_scores: inv_temperature must be finite and >= 0, got {inv_temperature!r}")
+    _chk(idx, val)
+    if not (1 <= nq <= (1 << 20)) or not (1 <= nk <= (1 << 20)):
+        raise MirrorHipError(f"knn_scores: nq = {nq}, nk = {nk} (1..2^20)")
+    idx, val = idx.contiguous(), val.detach().contiguous()
+    labels = labels.to(device=idx.device, dtype=torch.int64, non_blocking=True).contiguous()
+    scores = torch.empty((nq, C), device=idx.device, dtype=torch.float32)
+    _lib.call("mh_knn_scores", _p(idx), _p(val), _p(labels), nq, nk, kk, C, inv_t, _p(scores), stream=_stream())
+    return scores

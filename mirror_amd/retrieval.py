@@ -11,7 +11,10 @@ sample barcode, so a sample with three slides is in a validation set three times
 pair (the sample's row in the RNA table), a query's positives are all keys of its group and its rank is that of the best of them
 among the keys of other groups; the slide -> RNA gallery is the distinct samples, and RNA -> slide counts each sample once.
 
-Not built: bf16 keys, both directions from one pass over the similarities.
+The neighbours themselves (`mh_retrieval_topk`, csrc/retrieval_topk.hip): the same product with a selecting epilogue, for qualitative
+review, hard-negative mining and the kNN probe of `mirror_amd.knn`; `retrieval_topk` below and `CrossModalRetrieval.topk`.
+
+Not built: bf16 keys, both directions from one pass over the similarities, more than 64 neighbours.
 """
 from __future__ import annotations
 
@@ -24,7 +27,7 @@ import torch
 from . import kernels as K
 from ._lib import MirrorHipError
 
-__all__ = ["retrieval_ranks", "summarize_ranks", "first_of_group", "CrossModalRetrieval"]
+__all__ = ["retrieval_ranks", "retrieval_topk", "summarize_ranks", "first_of_group", "CrossModalRetrieval"]
 
 
 def _l2(x: torch.Tensor) -> torch.Tensor:
@@ -63,6 +66,28 @@ def retrieval_ranks(query: torch.Tensor, key: torch.Tensor, target: Optional[tor
     if grouped:
         return K.retrieval_ranks_grouped(query, key, query_group, key_group, key_count)
     return K.retrieval_ranks(query, key, target)
+
+
+def retrieval_topk(query: torch.Tensor, key: torch.Tensor, k: int, query_group: Optional[torch.Tensor] = None,
+                   key_group: Optional[torch.Tensor] = None, normalize: bool = False, parts: int = 0):
+    """(values f32 [nq, k], indices int32 [nq, k]) on the device, no host sync: for every query the k keys with the largest
+    query[i] . key[j], best first, equal similarities by the smaller key index.  normalize=True compares cosines (both sides through
+    mh_l2norm_fwd first), as `retrieval_ranks` does.  query_group [nq], key_group [nk] (integer ids, both or neither): a key of the
+    query's own group is left out, so `arange(n)` on both sides is leave-one-out over one set and a patient id leaves out the
+    patient's other slides.  A key whose similarity is NaN is never listed; slots beyond the eligible keys hold index -1 and value
+    -inf.  1 <= k <= 64.  The values are the numbers `retrieval_ranks` decides by, bit for bit; `parts` (the number of key strips,
+    0: chosen by the library) does not change the result.  See kernels.retrieval_topk for the checks."""
+    if (query_group is None) != (key_group is None):
+        raise ValueError("retrieval_topk: query_group and key_group go together")
+    if normalize:
+        if query.dim() != 2 or key.dim() != 2:
+            raise ValueError(f"retrieval_topk: query and key must be [n, D], got {tuple(query.shape)} and {tuple(key.shape)}")
+        K._chk(query, key)
+        if query.dtype != torch.float32 or key.dtype != torch.float32:
+            raise MirrorHipError(f"retrieval_topk: query and key must be f32, got {query.dtype}, {key.dtype}")
+        if query.shape[0] and key.shape[0] and query.shape[1] == key.shape[1] and query.shape[1] >= 1:
+            query, key = _l2(query), _l2(key)
+    return K.retrieval_topk(query, key, k, query_group, key_group, parts)
 
 
 def summarize_ranks(ranks, ks: Sequence[int] = (1, 5, 10)) -> "OrderedDict[str, float]":
@@ -177,6 +202,28 @@ class CrossModalRetrieval:
         if groups is not None:
             out["retrieval_groups"] = groups
         return out
+
+    def topk(self, k: int, direction: str = "wsi2rna", exclude_own_group: bool = False):
+        """(values f32 [n, k], indices int32 [n, k]) on the device, no host sync: for every accumulated slide the k RNA profiles it
+        retrieves ("wsi2rna"), or for every RNA profile the k slides ("rna2wsi"), best first; indices count the accumulated pairs in
+        update() order.  By default nothing is excluded, so a query's positive appears where it ranks.  exclude_own_group=True leaves
+        the query's own sample out of its list: every pair of its group with group ids, its own pair without.  The state and
+        compute() are untouched."""
+        if direction not in ("wsi2rna", "rna2wsi"):
+            raise ValueError(f'direction must be "wsi2rna" or "rna2wsi", got {direction!r}')
+        if sum(t.shape[0] for t in self.wsi) == 0:
+            raise ValueError("CrossModalRetrieval.topk(): no samples (call update() first)")
+        w, r = self._cat()
+        if self.normalize:
+            w, r = _l2(w), _l2(r)
+        g = None
+        if exclude_own_group:
+            if self.group:
+                g = self.group[0] if len(self.group) == 1 else torch.cat(self.group)
+            else:
+                g = torch.arange(w.shape[0], device=self.device, dtype=torch.int64)
+        query, key = (w, r) if direction == "wsi2rna" else (r, w)
+        return K.retrieval_topk(query, key, k, g, g)
 
     def reset(self) -> "CrossModalRetrieval":
         self.wsi, self.rna, self.group = [], [], []
