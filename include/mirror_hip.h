@@ -452,6 +452,12 @@ int mh_ppeg_fwd(const void* x, void* y, const float* merged, const float* bsum, 
 /* dmerged[tap][c] += sum dout*x(shifted); dbsum[c] += sum dout  (f32 atomics) */
 int mh_ppeg_wgrad(const void* x, const void* dout, float* dmerged, float* dbsum, int B, int S, int D,
                   int dt_x, int dt_o, mh_stream s);
+/* PPEG's whole backward in one pass over dy and x (f32, [B, 1+S*S, D]): dx = the adjoint filter over dy (cls row copied), dmerged / dbsum
+ * += as mh_ppeg_wgrad.  drop_out != NULL: x came out of a Dropout on the lite stream (p, seed, offset, dev_base as mh_dropout_lite, D % 8
+ * == 0) — drop_out (bf16, same shape) = that Dropout's backward of dx and drop_db [D] += its column sums, as mh_dropout_lite_colsum. */
+int mh_ppeg_bwd(const float* x, const float* dy, const float* merged, float* dx, float* dmerged, float* dbsum, int B, int S,
+                int D, void* drop_out, float* drop_db, float p, uint64_t seed, uint64_t offset, const uint64_t* dev_base,
+                mh_stream s);
 /* dw7 [D,1,7,7] += dmerged^T, dw5 [D,1,5,5] += its centre 5x5, dw3 [D,1,3,3] += its centre 3x3, db7 / db5 / db3 [D] += dbsum:
  * the gradients of the three depthwise kernels PPEG sums (models/mirror.py:324-331) from the merged kernel's gradient
  * (dmerged is tap-major [49, D] as mh_ppeg_wgrad writes it).  Accumulates: the caller owns the zeroing. */

@@ -508,6 +508,262 @@ extern "C" int mh_ppeg_wgrad(const void* x, const void* dout, float* dmerged, fl
     return MH_OK;
 }
 
+// ------------------------------------------------------------------ the whole backward in one walk over the grid
+// Data gradient (the adjoint filter over dy), filter gradient (dy x x), bias gradient (sum of dy) and — when the tensor PPEG read came
+// out of a Dropout ([3P] to_out of layer 1) — that Dropout's backward (masked, scaled bf16 copy of dx and its column sums), from ONE
+// read of dy and x.  The data gradient is ppeg_rows2_kernel's input-stationary form: dy row sy (with its 3-column halo) adds its seven
+// filter rows into the seven partial dx rows sy - 3 .. sy + 3.  The same ten dy columns serve the filter gradient: x row r pairs with dy
+// rows r - 3 .. r + 3, so a ring of seven x rows (the thread's 4 centre columns only, kept in LDS) meets every dy row as it passes,
+//     dmerged[ky][kx] += dy[sy][cx - kx + 3] * x[sy + ky - 3][cx]   over the strip's own x pixels (cx = the thread's columns).
+// A thread owns ONE channel: the channel-pair form would hold 2 x (49 taps + 49 weights + 28 partial rows + 28 ring + 20 dy) = 348
+// registers, one wave per SIMD with spills.  The multiply-adds are still v_pk_fma_f32, paired along x (data gradient: two pixels) and
+// along kx (filter gradient: two taps), 182 packed + 28 plain per row step instead of 392.
+// Workgroup = 64 channels (lanes) x 4 ADJACENT x-tiles of one (batch, strip) (waves): their halo columns are each other's centre
+// columns.  The four partial filters are summed through LDS and leave as one atomic per (tap, channel) and workgroup.
+// Dropout: one drop16_keep8 block covers 8 channels, so the 4 pixels x 64 channels a wave writes per row step are 32 blocks.  Every
+// second row step lane l draws the block of (row = l / 32, pixel = l / 8 % 4, channel group = l % 8) for the NEXT TWO dx rows, and
+// the lanes fetch their bit with one cross-lane read per pixel: 1/16 draw per element instead of 1.
+#define PB_X 4
+// acc += a[ha] * b (a[ha] to both halves) and acc += (a.y, a.x) * b[hb]: the compiler builds every splat and swap of a v_pk_fma_f32 operand
+// with moves (one or two per multiply-add); the instruction's op_sel bits select the halves for nothing.  ha / hb are constants after unrolling.
+__device__ __forceinline__ void pb_fma_splat_a(pp2& acc, pp2 a, int ha, pp2 b) {
+    if (ha) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(a), "v"(b));
+    else asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "+v"(acc) : "v"(a), "v"(b));
+}
+__device__ __forceinline__ void pb_fma_swap_a_splat_b(pp2& acc, pp2 a, pp2 b, int hb) {
+    if (hb) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[0,1,1]" : "+v"(acc) : "v"(a), "v"(b));
+    else asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[0,0,1]" : "+v"(acc) : "v"(a), "v"(b));
+}
+template <int N> struct pb_ic { static constexpr int value = N; };
+template <bool DROP>
+__global__ __launch_bounds__(256, 2) void ppeg_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ merged,
+                                                          float* __restrict__ dx, float* __restrict__ dmerged, float* __restrict__ dbsum,
+                                                          int S, int D, int nb, int pr, bf16_t* __restrict__ drop_out,
+                                                          float* __restrict__ drop_db, float p, uint64_t seed, uint64_t offset,
+                                                          const uint64_t* __restrict__ dev_base) {
+    // the x ring lives in LDS (each thread reads back only what it wrote: no barrier), 28 registers that two waves per SIMD do not have;
+    // the reduction at the end reuses the space
+    __shared__ __attribute__((aligned(16))) float smem[3 * 51 * 64 > 7 * 256 * PB_X ? 3 * 51 * 64 : 7 * 256 * PB_X];
+    f4_t* ring = reinterpret_cast<f4_t*>(smem) + threadIdx.x;       // slot s at ring[s * 256]
+    float (*red)[51][64] = reinterpret_cast<float (*)[51][64]>(smem);
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tiles_x = (S + PB_X - 1) / PB_X, xgroups = (tiles_x + 3) / 4, strips = (S + pr - 1) / pr, cblocks = (D + 63) / 64;
+    // XCD-aware order as in ppeg_rows2_kernel: the x-groups of one (batch, strip, channel block) run back to back on ONE XCD
+    const int groups = cblocks * strips * nb;
+    const int L = blockIdx.x;
+    int xg, grp;
+    if (groups % 8 == 0) { const int q = L >> 3; xg = q % xgroups; grp = (q / xgroups) * 8 + (L & 7); }
+    else { xg = L % xgroups; grp = L / xgroups; }
+    const int cb = grp % cblocks, sb = grp / cblocks;
+    const int c = cb * 64 + lane;
+    const bool cok = c < D;                  // dead lanes walk along on channel 0 (they serve the cross-lane reads) and store nothing
+    const int xt = xg * 4 + wave;
+    const bool wlive = xt < tiles_x;         // wave-uniform
+    const int y0 = (sb % strips) * pr, x0 = xt * PB_X;
+    const int rows = min(pr, S - y0);
+    const long b = sb / strips;
+    const long n = 1 + (long)S * S;
+    const long boff = b * n * D + cb * 64;     // workgroup-uniform: row addresses stay scalar, the lane adds cl
+    const int cl = cok ? lane : 0;
+    uint32_t thr = 0;
+    float scale = 1.f;
+    uint64_t blk0 = 0;
+    const int D8 = D >> 3;
+    if (DROP) {
+        if (dev_base) offset += *dev_base & ~7ull;
+        thr = drop16_thr(p);
+        scale = drop16_scale(thr);
+        blk0 = (offset >> 3) + (uint64_t)(b * n) * (uint64_t)D8 + (uint64_t)(cb * 8);      // block of (row 0 of this batch, channel cb * 64)
+    }
+    pp2 wp[25];                              // the adjoint filter: wp[u] = taps (2u, 2u + 1) of merged read backwards
+    float dm6[7];
+    pp2 dmp[7][3];                           // dmp[ky][q] = taps (ky, 2q) and (ky, 2q + 1), dm6[ky] = tap (ky, 6)
+#pragma unroll
+    for (int t = 0; t < 50; t++) wp[t >> 1][t & 1] = t < 49 ? merged[(48 - t) * D + cb * 64 + cl] : 0.f;
+#pragma unroll
+    for (int ky = 0; ky < 7; ky++) { dm6[ky] = 0.f; dmp[ky][0] = dmp[ky][1] = dmp[ky][2] = (pp2){0.f, 0.f}; }
+    float bacc = 0.f, dsum = 0.f;
+    if (wlive) {
+        const float* xb = x + boff;
+        const float* gb = dy + boff;
+        float* ob = dx + boff;
+        bf16_t* qb = DROP ? drop_out + boff : nullptr;
+        if (y0 == 0 && x0 == 0) {            // cls token passes through (and through the Dropout)
+            const float v = gb[cl];
+            if (cok) ob[cl] = v;
+            if (DROP) {
+                const uint32_t keep = drop16_keep8(blk0 + (uint64_t)(lane >> 3), seed, thr);
+                const bf16_t o = f2bf((keep >> (lane & 7)) & 1u ? __fmul_rn(v, scale) : 0.f);
+                if (cok) { qb[cl] = o; dsum += bf2f(o); }
+            }
+        }
+        // rows in flight: TWO row steps ahead (one step of multiply-adds is shorter than the memory latency under load).  The loads are
+        // unconditional, from addresses clamped into the grid — a load under a branch costs the exact vmcnt bookkeeping, and with it the
+        // second row in flight; the zero padding is applied when a row is taken into ce / co and the ring
+        float nb[2][PB_X + 6];
+        f4_t xq[2];
+        pp2 ce[5], co[4], acc[7][2];         // dy columns (2u, 2u + 1) and (2u + 1, 2u + 2) of the row in hand; dx pixels (2h, 2h + 1)
+        auto load_dy = [&](float (&dst)[PB_X + 6], int sy) {      // a row outside the grid is never used (the step skips its products)
+            const float* row = gb + (1 + (long)min(max(sy, 0), S - 1) * S) * D + cl;
+#pragma unroll
+            for (int u = 0; u < PB_X + 6; u++) dst[u] = row[(long)min(max(x0 - 3 + u, 0), S - 1) * D];
+        };
+        auto load_x = [&](f4_t& dst, int r) {      // row r of this strip (rows past its end are never used)
+            const float* row = xb + (1 + (long)(y0 + min(r, rows - 1)) * S) * D + cl;
+#pragma unroll
+            for (int i = 0; i < PB_X; i++) dst[i] = row[(long)min(x0 + i, S - 1) * D];
+        };
+        auto col = [&](const float (&src)[PB_X + 6], int u) { return (x0 - 3 + u >= 0 && x0 - 3 + u < S) ? src[u] : 0.f; };
+#pragma unroll
+        for (int r = 0; r < 7; r++)
+#pragma unroll
+            for (int h = 0; h < 2; h++) acc[r][h] = (pp2){0.f, 0.f};
+        uint32_t keep2 = 0;
+        const int steps = rows + 6;          // dy rows y0 - 3 .. y0 + rows + 2
+        load_dy(nb[0], y0 - 3);
+        load_x(xq[0], 0);
+        load_dy(nb[1], y0 - 2);              // (steps >= 7)
+        load_x(xq[1], 1);
+        for (int kb = 0; kb < steps; kb += 14) {
+            // 14 row steps spelled out (the seven slots of the rings x the two rows in flight): `#pragma unroll` gives up on a body this long,
+            // and a rolled loop would index the register arrays at run time
+            auto step = [&](auto jc) __attribute__((always_inline)) -> bool {
+                constexpr int j = decltype(jc)::value;
+                const int k = kb + j;
+                if (k >= steps) return false;
+                const int sy = y0 - 3 + k;
+#pragma unroll
+                for (int u = 0; u < 5; u++) ce[u] = (pp2){col(nb[j & 1], 2 * u), col(nb[j & 1], 2 * u + 1)};
+#pragma unroll
+                for (int u = 0; u < 4; u++) co[u] = (pp2){col(nb[j & 1], 2 * u + 1), col(nb[j & 1], 2 * u + 2)};
+                {
+                    f4_t xm;
+#pragma unroll
+                    for (int i = 0; i < PB_X; i++) xm[i] = x0 + i < S ? xq[j & 1][i] : 0.f;
+                    ring[(j % 7) * 256] = xm;          // x row k of the strip lives in slot k % 7
+                }
+                load_dy(nb[j & 1], sy + 2);  // two row steps ahead; unconditional (the last two steps of a strip fetch clamped rows again for
+                load_x(xq[j & 1], k + 2);    // nothing): a load that may not have been issued cannot be counted past by s_waitcnt
+                if (sy >= 0 && sy < S) {     // a row of zero padding adds nothing
+                    if (k >= 3 && k < rows + 3) bacc += (co[1][0] + co[1][1]) + (co[2][0] + co[2][1]);
+#pragma unroll
+                    for (int ky = 0; ky < 7; ky++) {
+                        const int o = k - ky;                          // dx row (of the strip) this filter row lands in
+                        if (o >= 0 && o < rows) {
+#pragma unroll
+                            for (int kx = 0; kx < 7; kx++)
+#pragma unroll
+                                for (int h = 0; h < 2; h++)      // pixels (2h, 2h + 1) read columns (2h + kx, 2h + kx + 1)
+                                    pb_fma_splat_a(acc[(j - ky + 14) % 7][h], wp[(ky * 7 + kx) >> 1], (ky * 7 + kx) & 1, (kx & 1) ? co[h + kx / 2] : ce[h + kx / 2]);
+                        }
+                    }
+#pragma unroll
+                    for (int ky = 0; ky < 7; ky++) {
+                        const int r = k + ky - 6;                      // x row (of the strip) this dy row meets at filter row ky
+                        if (r >= 0 && r < rows) {
+                            const f4_t xv = ring[((j + ky + 1) % 7) * 256];
+#pragma unroll
+                            for (int i = 0; i < PB_X; i++) {
+                                const pp2 xp = (i & 2) ? (pp2){xv[2], xv[3]} : (pp2){xv[0], xv[1]};
+#pragma unroll
+                                for (int q = 0; q < 3; q++) {    // taps (2q, 2q + 1) read columns (i + 6 - 2q, i + 5 - 2q): a pair, swapped
+                                    const int a = i + 5 - 2 * q;
+                                    pb_fma_swap_a_splat_b(dmp[ky][q], (a & 1) ? co[a / 2] : ce[a / 2], xp, i & 1);
+                                }
+                                asm("v_fmac_f32 %0, %1, %2" : "+v"(dm6[ky]) : "v"((i & 1) ? ce[i / 2][1] : ce[i / 2][0]), "v"(xv[i]));
+                            }
+                        }
+                    }
+                }
+                const int od = k - 6;        // this dx row has seen all seven dy rows
+                if (od >= 0) {
+                    const long prow = 1 + (long)(y0 + od) * S + x0;
+                    if (DROP) {
+                        if ((k & 1) == 0) {  // od = 0 falls on an even step: rows od (lanes 0..31) and od + 1 (lanes 32..63)
+                            const uint64_t r = (uint64_t)(prow + (long)(lane >> 5) * S + ((lane >> 3) & 3));
+                            keep2 = drop16_keep8(blk0 + r * (uint64_t)D8 + (uint64_t)(lane & 7), seed, thr);
+                        }
+                        uint32_t kp[PB_X];
+#pragma unroll
+                        for (int i = 0; i < PB_X; i++) kp[i] = (uint32_t)__shfl((int)keep2, ((k & 1) << 5) + i * 8 + (lane >> 3));
+#pragma unroll
+                        for (int i = 0; i < PB_X; i++) {
+                            const float v = acc[(j + 1) % 7][i >> 1][i & 1];
+                            const bf16_t o = f2bf((kp[i] >> (lane & 7)) & 1u ? __fmul_rn(v, scale) : 0.f);     // two roundings, as mh_dropout_lite
+                            if (cok && x0 + i < S) {
+                                ob[(prow + i) * D + cl] = v;
+                                qb[(prow + i) * D + cl] = o;
+                                dsum += bf2f(o);                        // the sums are those of the ROUNDED values
+                            }
+                        }
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < PB_X; i++)
+                            if (cok && x0 + i < S) ob[(prow + i) * D + cl] = acc[(j + 1) % 7][i >> 1][i & 1];
+                    }
+                }
+#pragma unroll
+                for (int h = 0; h < 2; h++) acc[(j + 1) % 7][h] = (pp2){0.f, 0.f};      // slot of dx row k + 1
+                return true;
+            };
+            if (!(step(pb_ic<0>{}) && step(pb_ic<1>{}) && step(pb_ic<2>{}) && step(pb_ic<3>{}) && step(pb_ic<4>{}) && step(pb_ic<5>{}) &&
+                  step(pb_ic<6>{}) && step(pb_ic<7>{}) && step(pb_ic<8>{}) && step(pb_ic<9>{}) && step(pb_ic<10>{}) && step(pb_ic<11>{}) &&
+                  step(pb_ic<12>{}) && step(pb_ic<13>{})))
+                break;
+        }
+    }
+    auto tap = [&](int t) { return t % 7 == 6 ? dm6[t / 7] : dmp[t / 7][(t % 7) >> 1][t % 7 & 1]; };
+    __syncthreads();                         // the ring is done with
+    if (wave > 0) {
+#pragma unroll
+        for (int t = 0; t < 49; t++) red[wave - 1][t][lane] = tap(t);
+        red[wave - 1][49][lane] = bacc;
+        red[wave - 1][50][lane] = dsum;
+    }
+    __syncthreads();
+    if (wave == 0 && cok) {
+#pragma unroll
+        for (int t = 0; t < 49; t++) atomicAdd(dmerged + t * D + c, tap(t) + red[0][t][lane] + red[1][t][lane] + red[2][t][lane]);
+        atomicAdd(dbsum + c, bacc + red[0][49][lane] + red[1][49][lane] + red[2][49][lane]);
+        if (DROP) {
+            const float t = dsum + red[0][50][lane] + red[1][50][lane] + red[2][50][lane];
+            if (t != 0.f) atomicAdd(drop_db + c, t);
+        }
+    }
+}
+
+extern "C" int mh_ppeg_bwd(const float* x, const float* dy, const float* merged, float* dx, float* dmerged, float* dbsum, int B, int S,
+                           int D, void* drop_out, float* drop_db, float p, uint64_t seed, uint64_t offset, const uint64_t* dev_base,
+                           mh_stream s) {
+    MH_REQUIRE(S >= 1 && D >= 1, "mh_ppeg_bwd: bad shape S=%d D=%d", S, D);
+    MH_REQUIRE(x && dy && merged && dx && dmerged && dbsum, "mh_ppeg_bwd: null pointer");
+    MH_REQUIRE(!drop_out || (drop_db && D % 8 == 0 && (offset & 7) == 0 && p >= 0.f && p < 1.f && ((uintptr_t)drop_out & 1) == 0),
+               "mh_ppeg_bwd: the Dropout site needs D %% 8 == 0 (D=%d), offset %% 8 == 0, 0 <= p < 1 and a bias-gradient destination", D);
+    if (B == 0) return MH_OK;
+    // rows per strip: two workgroups fit a CU, so the launch runs in rounds of 512; equal strips of at most 64 rows, the count with the
+    // fewest (rounds x row steps of a strip, 6 of them halo); the longer strips on a tie (fewer atomics)
+    int pr = S;
+    {
+        const long per = (long)mh_cdiv(D, 64) * mh_cdiv(mh_cdiv(S, PB_X), 4) * B;
+        long best = -1;
+        for (int st = 1; st <= mh_cdiv(S, 8); st++) {
+            const int rows = mh_cdiv(S, st);
+            if (rows > 64) continue;
+            const long cost = (long)mh_cdiv(per * mh_cdiv(S, rows), 512) * (rows + 6);
+            if (best < 0 || cost < best) { best = cost; pr = rows; }
+        }
+    }
+    const dim3 grid(mh_cdiv(D, 64) * mh_cdiv(S, pr) * mh_cdiv(mh_cdiv(S, PB_X), 4) * B);
+    if (drop_out)
+        hipLaunchKernelGGL(ppeg_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)s, x, dy, merged, dx, dmerged, dbsum, S, D, B, pr,
+                           (bf16_t*)drop_out, drop_db, p, seed, offset, dev_base);
+    else
+        hipLaunchKernelGGL(ppeg_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)s, x, dy, merged, dx, dmerged, dbsum, S, D, B, pr,
+                           (bf16_t*)nullptr, (float*)nullptr, 0.f, (uint64_t)0, (uint64_t)0, (const uint64_t*)nullptr);
+    MH_LAUNCH_CHECK("mh_ppeg_bwd");
+    return MH_OK;
+}
+
 // ------------------------------------------------------------------ merged gradient -> the six parameter gradients
 // The forward folds the 7x7, 5x5 and 3x3 depthwise kernels (and their biases) into one 7x7 (mh_ppeg_merge), so the gradient
 // of the merged kernel IS the 7x7's, its centre 5x5 the 5x5's, its centre 3x3 the 3x3's, and all three biases get dbsum

@@ -1789,6 +1789,10 @@ class PPEGFn(Function):
 
     @staticmethod
     def forward(ctx, x, w7, b7, w5, b5, w3, b3, S):
+        # x = resid + Dropout(to_out(.)) of layer 1: this node's dx is that Dropout's upstream gradient (see backward)
+        ctx.drop_site = getattr(x, "_drop_site", None) if (_DROP_IN_LN_BWD and x.dtype == f32 and x.is_contiguous()) else None
+        if ctx.drop_site is not None and ctx.drop_site.shape != tuple(x.shape):
+            ctx.drop_site = None
         x = x.contiguous()
         merged, bsum = K.ppeg_merge(w7.detach(), w5.detach(), w3.detach(), b7.detach(), b5.detach(), b3.detach())
         ctx.save_for_backward(x, merged, bsum)
@@ -1800,10 +1804,22 @@ class PPEGFn(Function):
         x, merged, bsum = ctx.saved_tensors
         S = ctx.S
         dy = dy.contiguous()
-        dx = K.ppeg(dy, merged, bsum, S, flip=True)
         dm = zeros(tuple(merged.shape), merged.device)
         dbs = zeros(tuple(bsum.shape), bsum.device)
-        K.ppeg_wgrad(x, dy, dm, dbs, S)
+        D = x.shape[-1]
+        if K.ppeg_bwd_ok(x, dy, merged, D):
+            # data, filter and bias gradient from one read of dy and x (mh_ppeg_bwd); with a site also layer 1's to_out Dropout backward
+            site, drop = ctx.drop_site, None
+            if site is not None and K.ppeg_bwd_ok(x, dy, merged, D, site.offset):
+                gbd = torch.empty(x.shape, device=x.device, dtype=bf16)
+                cs = zeros((D,), x.device)
+                drop = (gbd, site.p, site.seed, site.offset, site.base, cs)
+            dx = K.ppeg_bwd(x, dy, merged, dm, dbs, S, drop=drop)
+            if drop is not None:
+                site.offer(dx, gbd, cs)      # raw launches do not move dx's version: the offer may follow the one that wrote it
+        else:
+            dx = K.ppeg(dy, merged, bsum, S, flip=True)
+            K.ppeg_wgrad(x, dy, dm, dbs, S)
         # merged gradient -> the six parameter gradients in one accumulating launch (straight into the engine's arena)
         bufs = [_gbuf(p, tuple(p.shape)) for p in ctx.params]
         K.ppeg_grad_scatter(dm, dbs, *[bufs[i][0] for i in (0, 2, 4, 1, 3, 5)])

@@ -1278,6 +1278,38 @@ def ppeg_wgrad(x, dout, dmerged, dbsum, S: int) -> None:
     _lib.call("mh_ppeg_wgrad", _p(x), _p(dout), _p(dmerged), _p(dbsum), B, S, D, dt(x), dt(dout), stream=_stream())
 
 
+def ppeg_bwd_ok(x, dy, merged, D: int, drop_offset: Optional[int] = None) -> bool:
+    """mh_ppeg_bwd takes contiguous f32 x / dy of one shape; with a Dropout site also a D that mh_dropout_lite_colsum takes."""
+    f = torch.float32
+    return (x.dtype == f and dy.dtype == f and merged.dtype == f and x.shape == dy.shape and x.is_contiguous() and dy.is_contiguous()
+            and all(t.data_ptr() % 16 == 0 for t in (x, dy, merged))
+            and (drop_offset is None or (dropout_lite_colsum_ok(D) and drop_offset % 8 == 0)))
+
+
+def ppeg_bwd(x, dy, merged, dmerged, dbsum, S: int, drop=None) -> torch.Tensor:
+    """PPEG's backward in one launch (mh_ppeg_bwd): returns dx (f32, cls row passed through); dmerged [49, D] / dbsum [D] += the merged
+    filter's and the summed bias' gradients.  drop = (out bf16 of x's shape, p, seed, offset, dev_base, db [D] f32): x came out of a
+    Dropout on the lite stream — out = that Dropout's backward of dx, db += out's column sums (as dropout_lite_colsum of dx)."""
+    _chk(x, dy, merged, dmerged, dbsum)
+    B, n, D = x.shape
+    if n != 1 + S * S or not ppeg_bwd_ok(x, dy, merged, D) or tuple(merged.shape) != (49, D):
+        raise MirrorHipError("ppeg_bwd: contiguous 16-byte aligned f32 x / dy [B, 1 + S * S, D] and the merged filter [49, D]")
+    for t, m in ((dmerged, 49 * D), (dbsum, D)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != m:
+            raise MirrorHipError(f"ppeg_bwd: expected a contiguous f32 accumulator of {m} elements, got {tuple(t.shape)} {t.dtype}")
+    dx = torch.empty_like(x)
+    out, p, seed, off, base, db = drop if drop is not None else (None, 0.0, 0, 0, None, None)
+    if drop is not None:
+        _chk(out, base, db)
+        if not (ppeg_bwd_ok(x, dy, merged, D, off) and out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape == x.shape
+                and db.dtype == torch.float32 and db.is_contiguous() and db.numel() == D):
+            raise MirrorHipError("ppeg_bwd: the Dropout site needs a contiguous bf16 output of x's shape, an f32 [D] bias gradient, "
+                                 "offset % 8 == 0 and a D that dropout_lite_colsum takes")
+    _lib.call("mh_ppeg_bwd", _p(x), _p(dy), _p(merged), _p(dx), _p(dmerged), _p(dbsum), B, S, D, _p(out), _p(db), float(p), int(seed),
+              int(off), _p(base), stream=_stream())
+    return dx
+
+
 def ppeg_grad_scatter(dmerged, dbsum, dw7, dw5, dw3, db7, db5, db3) -> None:
     """The six PPEG parameter gradients += their share of the merged kernel's gradient (dmerged [49, D], dbsum [D])."""
     D = dbsum.numel()
