@@ -514,6 +514,12 @@ typedef struct {
 int mh_rna_block_fwd(const mh_rna_block* blk, mh_stream s);
 int mh_rna_block_bwd(const mh_rna_block* blk, mh_stream s);
 int64_t mh_rna_block_workspace_bytes(int B, int D, int Hh);
+/* Host only.  LDS bytes of the largest of the nine GEMM launches of both directions (forward contractions D, D, D, Hh; data
+ * gradients over D, Hh, D, 3 D; the weight-gradient tile), and the admission rule built on it: 1 when mh_rna_block_fwd AND
+ * mh_rna_block_bwd accept the geometry (every launch fits the LDS budget and the limits above hold), else 0.  Both entry
+ * points refuse a geometry that does not fit before they launch anything. */
+int64_t mh_rna_block_lds_bytes(int B, int D, int Hh);
+int mh_rna_block_fits(int B, int D, int Hh, int H);
 
 int mh_headattn_fwd(const void* qkv, void* out, float* attn, int B, int H, int hd, int dt, mh_stream s);
 int mh_headattn_bwd(const void* qkv, const float* attn, const void* dout, void* dqkv, int B, int H, int hd,
@@ -669,7 +675,9 @@ int mh_symkl_bwd(const float* w, const float* r, const float* g, float* dw, floa
  * rna retention, style (wsi), style (rna), cluster}.
  *   forward : out[8] = {total, alignment, wsi retention, rna retention, style_w + style_r, cluster, style_w, style_r};
  *             wsi_acc = the {num, den} pair mh_mse_masked_fwd accumulated on the same stream BEFORE this call (NULL: 0);
- *             scratch = 8 floats zeroed by the caller (kept for the backward), save = B*B + 2B floats (kept as well).
+ *             scratch = 8 + Bc + 64 floats, the first 8 zeroed by the caller (kept for the backward; behind the 8 words every
+ *             block of a shared term keeps its partial sum, added in a fixed order: the same operands give the same bits on
+ *             every launch), save = B*B + 2B floats (kept as well).
  *   backward: the upstream of term i is weight[i] * g_total[0] + (g_terms ? g_terms[i] : 0); every d_* of a term that is
  *             present is overwritten.  The WSI retention gradient stays mh_mse_masked_bwd(g = g_total, gmul = weight[1]).
  * has_align = 0: the alignment term was computed by the caller over the gathered batch (align_ext, one float, may be

@@ -231,6 +231,7 @@ _SIGS = {
     "mh_knn_scores": [P, P, P, L, L, I, I, F, P],
 }
 EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "mh_gemm_variant_name", "mh_device_ok", "mh_nys_attn3_ws_floats", "mh_rna_block_workspace_bytes",
+                                 "mh_rna_block_lds_bytes", "mh_rna_block_fits",
                                  "mh_gemm_workspace_bytes", "mh_layernorm_bwd_workspace_bytes", "mh_nys_attn3_workspace_bytes",
                                  "mh_pinv_chain_workspace_bytes", "mh_resconv_bwd_workspace_bytes", "mh_mask_apply_bwd_dbias_ok",
                                  "mh_retrieval_workspace_bytes", "mh_retrieval_topk_workspace_bytes"])
@@ -286,6 +287,12 @@ def load() -> C.CDLL:
     lib.mh_mask_apply_bwd_dbias_ok.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
     lib.mh_rna_block_workspace_bytes.restype = C.c_int64
     lib.mh_rna_block_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    if not hasattr(lib, "mh_rna_block_fits"):
+        raise MirrorHipError(f"{LIB_PATH} lacks mh_rna_block_fits: rebuild the library (`make -C mirror_amd/csrc`, or __graft_entry__.build())")
+    lib.mh_rna_block_lds_bytes.restype = C.c_int64
+    lib.mh_rna_block_lds_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.mh_rna_block_fits.restype = C.c_int
+    lib.mh_rna_block_fits.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.mh_retrieval_workspace_bytes.restype = C.c_int64
     lib.mh_retrieval_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int]
     if not hasattr(lib, "mh_retrieval_topk_workspace_bytes"):

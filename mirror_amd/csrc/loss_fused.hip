@@ -8,6 +8,9 @@
 // Block roles (256 threads): [0, Bc) one prototype-score row each; then the alignment block, the two style blocks and NMSE
 // blocks of the flat RNA MSE.  The forward's last block to finish (device-scope counter in the zeroed scratch) folds the
 // terms into out[8] = {total, alignment, wsi retention, rna retention, style (sum), cluster, style_w, style_r}.
+// A term that several blocks share (the cluster rows, the RNA MSE) is NOT added up with float atomics, whose order is the blocks'
+// order of arrival: every block stores its partial sum in a slot of its own behind the eight scratch words and the last block
+// adds the slots in one fixed order, so the same operands give the same bits on every launch (validate() promises that).
 #include "common.h"
 
 namespace {
@@ -16,8 +19,9 @@ constexpr int NMSE = 32;       // blocks of the flat RNA MSE (4 elements per thr
 constexpr int SK_E = 16;       // prototype scores per thread held in registers (P <= 4096; longer rows re-read global memory)
 constexpr int BMAX = 32;       // alignment block: B x B logits, B <= 32 (the batch of one rank)
 
-// scratch words (zeroed by the caller): partial sums and the completion counter
-enum { A_ALIGN = 0, A_RNUM = 1, A_RDEN = 2, A_STW = 3, A_STR = 4, A_CLU = 5, A_COUNT = 7 };
+// scratch words (zeroed by the caller): the terms and the completion counter; behind them the per-block slots (written before
+// they are read: no zeroing): Bc cluster rows, then NMSE numerators and NMSE denominators of the RNA MSE
+enum { A_ALIGN = 0, A_RNUM = 1, A_RDEN = 2, A_STW = 3, A_STR = 4, A_CLU = 5, A_COUNT = 7, A_SLOTS = 8 };
 
 __device__ __forceinline__ float dev_load(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -86,7 +90,7 @@ __global__ __launch_bounds__(256) void loss_terms_fwd_kernel(mh_loss_terms d) {
             }
         }
         s = block_sum256(s, red);
-        if (tid == 0) atomicAdd(d.scratch + A_CLU, (0.5f / d.Bc) * s);
+        if (tid == 0) d.scratch[A_SLOTS + role] = (0.5f / d.Bc) * s;
     } else if ((role -= d.Bc) == 0) {                   // ---- alignment
         if (d.has_align) {
             const int B = d.B, D = d.D, ldw = D + 1, ldg = B + 1;
@@ -173,27 +177,41 @@ __global__ __launch_bounds__(256) void loss_terms_fwd_kernel(mh_loss_terms d) {
         }
         num = block_sum256(num, red);
         den = block_sum256(den, red);
-        if (tid == 0) { atomicAdd(d.scratch + A_RNUM, num); atomicAdd(d.scratch + A_RDEN, den); }
+        if (tid == 0) { d.scratch[A_SLOTS + d.Bc + b] = num; d.scratch[A_SLOTS + d.Bc + NMSE + b] = den; }
     }
     // ---- the last block to get here folds the terms (every block's sums are device-visible before its counter tick)
+    __shared__ int last;
     if (tid == 0) {
         __threadfence();
-        const unsigned done = atomicAdd(reinterpret_cast<unsigned*>(d.scratch + A_COUNT), 1u);
-        if (done == gridDim.x - 1) {
-            __threadfence();
-            const float align = dev_load(d.scratch + A_ALIGN);
-            const float wsi = d.wsi_acc ? d.wsi_acc[0] / d.wsi_acc[1] : 0.f;     // written by the launch before this one
-            const float rna = dev_load(d.scratch + A_RNUM) / dev_load(d.scratch + A_RDEN);
-            const float sw = dev_load(d.scratch + A_STW), sr = dev_load(d.scratch + A_STR), clu = dev_load(d.scratch + A_CLU);
-            d.out[0] = d.weight[0] * align + d.weight[1] * wsi + d.weight[2] * rna + d.weight[3] * sw + d.weight[4] * sr + d.weight[5] * clu;
-            d.out[1] = align;
-            d.out[2] = wsi;
-            d.out[3] = rna;
-            d.out[4] = sw + sr;
-            d.out[5] = clu;
-            d.out[6] = sw;
-            d.out[7] = sr;
-        }
+        last = atomicAdd(reinterpret_cast<unsigned*>(d.scratch + A_COUNT), 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    // the shared terms: each thread adds its slots in index order, the block reduction is a fixed tree
+    float clu = 0.f;
+    for (int i = tid; i < d.Bc; i += 256) clu += dev_load(d.scratch + A_SLOTS + i);
+    float rnum = tid < NMSE ? dev_load(d.scratch + A_SLOTS + d.Bc + tid) : 0.f;
+    float rden = tid < NMSE ? dev_load(d.scratch + A_SLOTS + d.Bc + NMSE + tid) : 0.f;
+    clu = block_sum256(clu, red);
+    rnum = block_sum256(rnum, red);
+    rden = block_sum256(rden, red);
+    if (tid == 0) {
+        const float align = dev_load(d.scratch + A_ALIGN);
+        const float wsi = d.wsi_acc ? d.wsi_acc[0] / d.wsi_acc[1] : 0.f;     // written by the launch before this one
+        const float rna = rnum / rden;
+        const float sw = dev_load(d.scratch + A_STW), sr = dev_load(d.scratch + A_STR);
+        d.scratch[A_RNUM] = rnum;
+        d.scratch[A_RDEN] = rden;                                            // the backward's normaliser
+        d.scratch[A_CLU] = clu;
+        d.out[0] = d.weight[0] * align + d.weight[1] * wsi + d.weight[2] * rna + d.weight[3] * sw + d.weight[4] * sr + d.weight[5] * clu;
+        d.out[1] = align;
+        d.out[2] = wsi;
+        d.out[3] = rna;
+        d.out[4] = sw + sr;
+        d.out[5] = clu;
+        d.out[6] = sw;
+        d.out[7] = sr;
     }
 }
 

@@ -603,6 +603,27 @@ extern "C" int64_t mh_rna_block_workspace_bytes(int B, int D, int Hh) {
     return al(2L * B * Hh) + 3 * al(4L * B * D) + al(2L * B * D) + al(6L * B * D);
 }
 
+// The admission rule: LDS of the largest of the nine GEMM launches of both directions.  A launch stages its whole operand
+// image — MT * 16 rows of (contraction + PADK) bf16 — plus the cross-wave reduction scratch (fwd_lds); the contraction is K in
+// the forward (D, D, D, Hh for qkv, proj, fc1, fc2) and the Linear's output width M in a data gradient (D, Hh, D, 3 D for
+// fc2, fc1, proj, qkv); a backward grid holds at least its weight-gradient tile (launch_bwd).
+constexpr size_t RNA_LDS_BUDGET = 158 * 1024;
+static size_t rna_lds_bytes(int B, int D, int Hh) {
+    const int MT = B <= 16 ? 1 : 2;
+    const int contraction[8] = {D, D, D, Hh, D, Hh, D, 3 * D};
+    size_t need = 32 * 64 * 4 + 32 * 256 * 4;
+    for (int k : contraction)
+        if (fwd_lds(MT, k) > need) need = fwd_lds(MT, k);
+    return need;
+}
+
+extern "C" int64_t mh_rna_block_lds_bytes(int B, int D, int Hh) { return (int64_t)rna_lds_bytes(B, D, Hh); }
+
+extern "C" int mh_rna_block_fits(int B, int D, int Hh, int H) {
+    return B >= 1 && B <= 32 && D > 0 && Hh > 0 && D % 32 == 0 && Hh % 32 == 0 && H >= 1 && H <= 64 && D % H == 0 && D <= 2048 && Hh <= 4096 &&
+           rna_lds_bytes(B, D, Hh) <= RNA_LDS_BUDGET;
+}
+
 static int rna_check(const mh_rna_block* b, const char* who) {
     MH_REQUIRE(b, "%s: null descriptor", who);
     MH_REQUIRE(b->B >= 1 && b->B <= 32, "%s: B=%d (needs 1..32 rows)", who, b->B);
@@ -610,6 +631,9 @@ static int rna_check(const mh_rna_block* b, const char* who) {
     MH_REQUIRE(b->H >= 1 && b->H <= 64 && b->D % b->H == 0 && b->D <= 4096, "%s: H=%d does not divide D=%d", who, b->H, b->D);
     MH_REQUIRE(b->Hh <= 4096 && b->D <= 2048, "%s: D=%d, Hh=%d exceed the batched prologues (D <= 2048, Hh <= 4096)", who, b->D, b->Hh);
     MH_REQUIRE(b->p_drop >= 0.f && b->p_drop < 1.f && (b->offset & 3) == 0, "%s: bad dropout arguments", who);
+    // before anything is launched: a backward that failed at its fourth Linear would already have accumulated into dw_* / db_*
+    MH_REQUIRE(rna_lds_bytes(b->B, b->D, b->Hh) <= RNA_LDS_BUDGET, "%s: B=%d, D=%d, Hh=%d needs an operand image of %zu bytes (LDS budget %zu)", who,
+               b->B, b->D, b->Hh, rna_lds_bytes(b->B, b->D, b->Hh), RNA_LDS_BUDGET);
     return MH_OK;
 }
 

@@ -2825,7 +2825,7 @@ class MirrorLossTermsFn(Function):
         local = wa is not None
         t = dict(rna_pred=rp.contiguous(), rna_tgt=rt.contiguous(), rna_mask=rm.contiguous().float(), w_mu=wmu.contiguous(),
                  w_logstd=wls.contiguous(), r_mu=rmu.contiguous(), r_logstd=rls.contiguous(), w_score=wsc.contiguous(),
-                 r_score=rsc.contiguous(), wsi_acc=acc, scratch=zeros((8,), dev), out=torch.empty((8,), device=dev, dtype=f32))
+                 r_score=rsc.contiguous(), wsi_acc=acc, scratch=zeros((K.loss_terms_scratch_floats(wsc.shape[0]),), dev), out=torch.empty((8,), device=dev, dtype=f32))
         if local:
             Bq = wa.shape[0]
             t.update(wsi_emb=wa.contiguous(), rna_emb=ra.contiguous(), logit_scale=scale.detach().reshape(1).contiguous(),

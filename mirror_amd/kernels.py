@@ -6,6 +6,7 @@ node down) and launches on torch's current stream.  There is no CPU / PyTorch fa
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 from typing import Optional
 
@@ -1447,15 +1448,19 @@ def headattn_bwd(qkv, attn, dout, H: int) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------- fused RNA Block (csrc/rna_block.hip)
+@functools.lru_cache(maxsize=None)
+def _rna_block_fits(B: int, D: int, Hh: int, H: int) -> bool:
+    # the library's own rule (csrc/rna_block.hip mh_rna_block_fits: every launch of both directions fits the LDS budget), the
+    # one mh_rna_block_fwd / _bwd check before they launch; cached because it sits on every Block.forward
+    return bool(_lib.load().mh_rna_block_fits(B, D, Hh, H))
+
+
 def rna_block_ok(x: torch.Tensor, D: int, Hh: int, H: int) -> bool:
-    """The fused Block covers [B <= 32, D] f32 rows with D, Hh multiples of 32 and H | D (c2: D = 512, Hh = 2048, H = 8)."""
-    if not (x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous() and 1 <= x.shape[0] <= 32 and x.shape[1] == D
-            and D % 32 == 0 and Hh % 32 == 0 and D % H == 0 and D <= 2048 and Hh <= 4096 and H <= 64):
+    """The fused Block covers [B <= 32, D] f32 rows with D, Hh multiples of 32 and H | D (c2: D = 512, Hh = 2048, H = 8), where
+    the operand image of every Linear fits LDS in both directions (the qkv data gradient stages [B, 3 D])."""
+    if not (x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == D and H >= 1):
         return False
-    # the kernels stage the [B x K] operand of every Linear in LDS (csrc/rna_block.hip fwd_lds / launch_bwd): MT * 16 rows of
-    # K + 8 bf16 plus the cross-wave reduction scratch must fit 158 KiB, K = the longest contraction = max(D, Hh)
-    mt = 1 if x.shape[0] <= 16 else 2
-    return mt * 16 * (max(D, Hh) + 8) * 2 + 4 * mt * 16 * 17 * 4 <= 158 * 1024
+    return _rna_block_fits(int(x.shape[0]), int(D), int(Hh), int(H))
 
 
 def rna_block_workspace_bytes(B: int, D: int, Hh: int) -> int:
@@ -1768,6 +1773,12 @@ def mse_masked_bwd(pred, tgt, mask, acc, g, dpred, dtgt, rows, D, gmul: float = 
 LOSS_TERMS_BMAX = 32          # alignment block of mh_loss_terms: B <= 32 and 2 B (D + 1) + B (B + 1) floats <= 150 KiB of LDS
 
 
+def loss_terms_scratch_floats(Bc: int) -> int:
+    """Floats of mh_loss_terms.scratch for Bc score rows: 8 words (zeroed by the caller), then one slot per block of the terms that
+    several blocks share (Bc cluster rows, 32 + 32 of the RNA MSE; csrc/loss_fused.hip)."""
+    return 8 + Bc + 64
+
+
 def loss_terms_ok(B: int, D: int) -> bool:
     return 1 <= B <= LOSS_TERMS_BMAX and 4 * (2 * B * (D + 1) + B * (B + 1)) <= 150 * 1024
 
@@ -1795,13 +1806,15 @@ def _loss_terms_desc(weights, t: dict) -> "_lib.LossTermsDesc":
     d.Bc, d.P = t["w_score"].shape
     if tuple(t["r_score"].shape) != (d.Bc, d.P):
         raise MirrorHipError("loss_terms: prototype score shapes differ")
+    if t["scratch"].numel() < loss_terms_scratch_floats(d.Bc):
+        raise MirrorHipError(f"loss_terms: scratch holds {t['scratch'].numel()} floats, {loss_terms_scratch_floats(d.Bc)} needed")
     for i, w in enumerate(weights):
         d.weight[i] = float(w)
     return d
 
 
 def loss_terms_fwd(weights, t: dict) -> None:
-    """mh_loss_terms_fwd: t carries the operands plus scratch [8] (zeroed), save [B*B + 2B], out [8], wsi_acc (or None)."""
+    """mh_loss_terms_fwd: t carries the operands plus scratch [loss_terms_scratch_floats(Bc)] (the first 8 zeroed), save [B*B + 2B], out [8], wsi_acc (or None)."""
     _lib.call("mh_loss_terms_fwd", C.byref(_loss_terms_desc(weights, t)), stream=_stream())
 
 

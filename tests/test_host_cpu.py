@@ -282,6 +282,63 @@ def test_rna_block_ok_mirrors_the_kernel_limits():
     assert not K.rna_block_ok(torch.zeros(32, 1024), 1024, 4096, 8)     # 2 x 16 x 4104 x 2 B = 262 KiB operand image
     assert not K.rna_block_ok(torch.zeros(8, 4096), 4096, 4096, 8)      # D > 2048
     assert K.rna_block_ok(torch.zeros(16, 1024), 1024, 4096, 8)         # one row tile: 131 KiB
+    # the backward stages the gradient matrix [MT 16, M + 8] of every Linear, and M = 3 D for qkv: refused before anything runs
+    assert not K.rna_block_ok(torch.zeros(32, 1024), 1024, 2048, 8)     # qkv data gradient: 2 x 16 x 3080 x 2 B + 8704 = 205 824 B
+    assert not K.rna_block_ok(torch.zeros(16, 2048), 2048, 64, 8)       # 16 x 6152 x 2 B + 4352 = 201 216 B
+    assert not K.rna_block_ok(torch.zeros(2, 2048), 2048, 2048, 8)
+    assert K.rna_block_ok(torch.zeros(16, 1632), 1632, 64, 8)           # the largest D of one row tile: 161 280 B of 161 792
+    assert not K.rna_block_ok(torch.zeros(16, 1664), 1664, 64, 8)
+    assert K.rna_block_ok(torch.zeros(32, 768), 768, 1536, 12)          # the largest D of two row tiles: 156 672 B
+    assert K.rna_block_ok(torch.zeros(17, 768), 768, 2304, 12) and not K.rna_block_ok(torch.zeros(17, 800), 800, 64, 8)
+    assert K.rna_block_ok(torch.zeros(16, 1024), 1024, 4096, 8)
+    _rna_admission_sweep()
+
+
+def _rna_launch_lds(B, D, Hh):
+    """LDS bytes of the nine GEMM launches of one Block, restated from csrc/rna_block.hip launch by launch: an operand image of
+    MT 16 rows x (contraction + 8) bf16, the split-K reduction scratch 4 waves x MT x 16 x 17 f32; a backward grid is sized for the
+    larger of its data-gradient image and its weight-gradient tiles (32 x 64 + 32 x 256 f32)."""
+    mt = 1 if B <= 16 else 2
+    image = lambda k: mt * 16 * (k + 8) * 2 + 4 * mt * 16 * 17 * 4  # noqa: E731
+    wtile = (32 * 64 + 32 * 256) * 4
+    fwd = {"qkv": image(D), "proj": image(D), "fc1": image(D), "fc2": image(Hh)}
+    bwd = {"fc2": max(image(D), wtile), "fc1": max(image(Hh), wtile), "proj": max(image(D), wtile), "qkv": max(image(3 * D), wtile)}
+    return list(fwd.values()) + list(bwd.values()) + [wtile]
+
+
+def _rna_admission_sweep():
+    """The whole grid: B = 1..32, D and Hh over the multiples of 32 up to (and one step past) their limits, several head counts.
+    rna_block_ok must be true exactly when the nine launches fit 158 KiB and the documented limits hold (D <= 2048, Hh <= 4096,
+    H | D, H <= 64), and the library's own figure must be the largest launch."""
+    lib = _lib.load()
+    budget = 158 * 1024
+    wrong, admitted = [], 0
+    for B in range(1, 33):
+        x_cache = {}
+        for D in range(32, 2048 + 64, 32):
+            x = x_cache.setdefault(D, torch.zeros(B, D))
+            for Hh in range(32, 4096 + 64, 32):
+                need = max(_rna_launch_lds(B, D, Hh))
+                if B in (1, 16, 17, 32):
+                    assert lib.mh_rna_block_lds_bytes(B, D, Hh) == need, (B, D, Hh)
+                for H in ((1, 8, 12, 17, 64, 96) if Hh in (64, 1536, 4096, 4128) else (8,)):
+                    want = need <= budget and D <= 2048 and Hh <= 4096 and D % H == 0 and H <= 64
+                    admitted += want
+                    if K.rna_block_ok(x, D, Hh, H) != want:
+                        wrong.append((B, D, Hh, H, want))
+    assert not wrong, wrong[:5]
+    assert admitted > 10000
+    assert not K.rna_block_ok(torch.zeros(33, 64), 64, 64, 8) and not K.rna_block_ok(torch.zeros(4, 48), 48, 64, 8)
+    assert not K.rna_block_ok(torch.zeros(4, 64), 64, 48, 8) and not K.rna_block_ok(torch.zeros(4, 64).double(), 64, 64, 8)
+    assert not K.rna_block_ok(torch.zeros(4, 128)[:, ::2], 64, 64, 8)
+    # and both entry points say no themselves, in their argument check (nothing is launched: no device needed)
+    import ctypes
+    for B, D, Hh in ((32, 1024, 2048), (16, 2048, 64)):
+        d = _lib.RnaBlockDesc()
+        d.B, d.D, d.Hh, d.H = B, D, Hh, 8
+        for name in ("mh_rna_block_fwd", "mh_rna_block_bwd"):
+            with pytest.raises(mirror_amd.MirrorHipError, match="LDS budget"):
+                _lib.call(name, ctypes.byref(d))
 
 
 def test_pmc_summary_reports_the_replayed_step_on_its_own(tmp_path):

@@ -303,13 +303,11 @@ def test_validate_appends_the_retrieval_entries_behind_the_six_losses():
 
 
 def test_validate_losses_are_bit_identical_with_and_without_retrieval():
-    """INTERMITTENT on the MI355X, through no launch of the retrieval path: of three runs of this test one failed, with
-    wsi_retention_loss 2.1060487429300943 without and 2.106048901875814 with the metric (7.5e-8 relative, one f32 ulp of one
-    batch's term) and the other five losses equal, and two passed with all six bit-equal.  Eight validate() calls in one process
-    over these batches, four of them plain and back to back, then alternating: the four agreed bit for bit, after that `loss` and
-    `wsi_retention_loss` moved by one ulp between calls, between two PLAIN calls as well.  The cause is mh_mse_masked_fwd
-    (csrc/loss.hip), which adds its per-block partial sums with float atomics across up to 1024 blocks, in whatever order they arrive.
-    validate() adds no launch before the losses of a batch are formed.  The bound is left as stated."""
+    """validate() forms a batch's losses before it touches the metric, and every loss kernel on that path adds its blocks' partial
+    sums in a fixed order: the WSI retention MSE through mh_mse_masked_fwd_ordered, the cluster rows and the RNA MSE of
+    mh_loss_terms_fwd through per-block slots that its last block folds (csrc/loss_fused.hip).  With float atomics in their place
+    this test failed intermittently, by one f32 ulp of one batch's term: wsi_retention_loss first (2.1060487429300943 against
+    2.106048901875814), cluster_loss after that one was fixed (0x1.8070f6aaaaaabp-2 against 0x1.8070f60000000p-2)."""
     from mirror_amd.engine import TrainEngine
     model, eng, batches, noises = _validate_setup()
     plain = eng.validate(batches, noise=noises)
