@@ -478,6 +478,25 @@ int mh_mask_apply_bwd_dbias_ok(const void* dy, const void* dx, const float* dpos
 int mh_mask_apply_bwd(const void* dy, void* dx, const float* mask, float* dtoken, float* dpos, int B, int T, int D,
                       int first, int token_scalar, int dt_dy, int dt_dx, float* dbias, mh_stream s);
 
+/* Compact retention embed: the projection in front of the mask-token select (retention_embed, models/mirror.py:690-693) is only needed
+ * at the `first` unmasked prefix rows and the `keep` kept tokens of every batch.  mh_rank_mask_keep = mh_rank_mask (the same mask, bit
+ * for bit) that also leaves keep_idx [B, len_keep] int32 (the token of rank j < len_keep) and slot [B, N] int32 (the rank of a kept
+ * token, -1 for a masked one).  Compact layout [B, first + keep, .]: row b * (first + keep) + t (t < first) = prefix row t, row
+ * b * (first + keep) + first + j = token keep_idx[b, j]. */
+int mh_rank_mask_keep(const float* noise, float* mask, int* keep_idx, int* slot, int B, int N, int len_keep, mh_stream s);
+/* out [B, first + keep, K] bf16 = the compact rows of x [B, T, K] bf16 (K % 8 == 0, 16-byte aligned) */
+int mh_rows_gather(const void* x, const int* keep_idx, void* out, int B, int T, int K, int first, int keep, mh_stream s);
+/* y [B, T, D] f32 = (slot < 0 ? token : rc[compact row]) + pos[t] for the compact bf16 projection rc [B, first + keep, D]: bit-identical
+ * to mh_mask_apply_fwd on the dense bf16 projection (D % 4 == 0; slot [B, T - first]) */
+int mh_mask_expand_fwd(const void* rc, float* y, const int* slot, const float* token, const float* pos, int B, int T, int D, int first,
+                       int keep, mh_stream s);
+/* mh_mask_apply_bwd's quad form (f32 dy, bf16 dx, per-channel token: the same arithmetic and summation order for dtoken, dpos and
+ * dbias) whose dx is the COMPACT tensor drc [B, first + keep, D] bf16: nothing is stored for a masked row */
+int mh_mask_apply_bwd_keep(const float* dy, void* drc, const int* slot, float* dtoken, float* dpos, int B, int T, int D, int first,
+                           int keep, float* dbias, mh_stream s);
+/* dh [B, T, K] f32 = dhc [B, first + keep, K] f32 at the prefix and kept rows, exact zeros at the masked rows (K % 4 == 0) */
+int mh_rows_expand_zero(const float* dhc, const int* slot, float* dh, int B, int T, int K, int first, int keep, mh_stream s);
+
 /* ---------------------------------------------------------------- RNA encoder pieces (models/mirror.py:77-102)
  * qkv [B, 3D] -> softmax over the HEADS axis -> out[b, d*H + h]; attn [B,H,H] saved for backward */
 /* One pre-norm Block of the RNA transformer (reference: Block.forward models/mirror.py:149-152, Attention.forward :77-102,

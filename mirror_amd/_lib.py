@@ -156,6 +156,11 @@ _SIGS = {
     "mh_rank_mask": [P, P, I, I, I],
     "mh_mask_apply_fwd": [P, P, P, P, P, I, I, I, I, I, I, I],
     "mh_mask_apply_bwd": [P, P, P, P, P, I, I, I, I, I, I, I, P],
+    "mh_rank_mask_keep": [P, P, P, P, I, I, I],
+    "mh_rows_gather": [P, P, P, I, I, I, I, I],
+    "mh_mask_expand_fwd": [P, P, P, P, P, I, I, I, I, I],
+    "mh_mask_apply_bwd_keep": [P, P, P, P, P, I, I, I, I, I, P],
+    "mh_rows_expand_zero": [P, P, P, I, I, I, I, I],
     "mh_headattn_fwd": [P, P, P, I, I, I, I],
     "mh_headattn_bwd": [P, P, P, P, I, I, I, I],
     "mh_add": [P, P, P, L, I, I, I],

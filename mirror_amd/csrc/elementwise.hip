@@ -525,10 +525,7 @@ extern "C" int mh_colsum(const void* x, float* out, int64_t rows, int cols, int6
 // One workgroup per row sorts the row's (order-preserving key, index) pairs in LDS (bitonic network over the next power of two, the
 // tail padded with maximal keys) and scatters mask[index] = position >= len_keep.  The earlier all-pairs count was N^2 compares per
 // row: 16 x 4096 took 256 workgroups for ~150-400 us beside the WSI encoder's first layers; the network is N log^2 N / 2.
-__global__ __launch_bounds__(1024) void rank_mask_kernel(const float* __restrict__ noise, float* __restrict__ mask, int N, int P, int len_keep) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
-    const long b = blockIdx.x;
-    const float* nb = noise + b * N;
+__device__ __forceinline__ void rank_sort(unsigned long long* keys, const float* __restrict__ nb, int N, int P) {
     for (int j = threadIdx.x; j < P; j += 1024) {
         unsigned long long k = ~0ull;
         if (j < N) {
@@ -549,7 +546,46 @@ __global__ __launch_bounds__(1024) void rank_mask_kernel(const float* __restrict
             }
             __syncthreads();
         }
+}
+
+__global__ __launch_bounds__(1024) void rank_mask_kernel(const float* __restrict__ noise, float* __restrict__ mask, int N, int P, int len_keep) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
+    const long b = blockIdx.x;
+    rank_sort(keys, noise + b * N, N, P);
     for (int j = threadIdx.x; j < N; j += 1024) mask[b * N + (unsigned)(keys[j] & 0xffffffffu)] = j >= len_keep ? 1.f : 0.f;
+}
+
+// the same ranking, which also leaves the keep map of the compact retention embed: keep_idx[b, j] = the token of rank j < len_keep,
+// slot[b, token] = its rank when kept, -1 when masked (every row keeps exactly len_keep tokens: the compact shapes are static)
+__global__ __launch_bounds__(1024) void rank_mask_keep_kernel(const float* __restrict__ noise, float* __restrict__ mask,
+                                                              int* __restrict__ keep_idx, int* __restrict__ slot, int N, int P, int len_keep) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
+    const long b = blockIdx.x;
+    rank_sort(keys, noise + b * N, N, P);
+    // the sorted keys move to registers (N <= 16384: 16 per thread) and their LDS becomes rank[token], so that mask and slot leave in
+    // token order (coalesced) instead of as two scattered 4-byte stores per token
+    unsigned tok[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const int j = threadIdx.x + 1024 * i;
+        tok[i] = j < N ? (unsigned)(keys[j] & 0xffffffffu) : 0u;
+    }
+    __syncthreads();
+    int* rank = reinterpret_cast<int*>(keys);
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const int j = threadIdx.x + 1024 * i;
+        if (j < N) {
+            rank[tok[i]] = j;
+            if (j < len_keep) keep_idx[b * len_keep + j] = (int)tok[i];
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < N; t += 1024) {
+        const int r = rank[t];
+        mask[b * N + t] = r < len_keep ? 0.f : 1.f;
+        slot[b * N + t] = r < len_keep ? r : -1;
+    }
 }
 
 extern "C" int mh_rank_mask(const float* noise, float* mask, int B, int N, int len_keep, mh_stream s) {
@@ -563,6 +599,22 @@ extern "C" int mh_rank_mask(const float* noise, float* mask, int B, int N, int l
     MH_REQUIRE(big || P * 8 <= 65536, "mh_rank_mask: %d bytes of LDS refused", P * 8);
     hipLaunchKernelGGL(rank_mask_kernel, dim3(B), dim3(1024), (size_t)P * sizeof(unsigned long long), (hipStream_t)s, noise, mask, N, P, len_keep);
     MH_LAUNCH_CHECK("mh_rank_mask");
+    return MH_OK;
+}
+
+extern "C" int mh_rank_mask_keep(const float* noise, float* mask, int* keep_idx, int* slot, int B, int N, int len_keep, mh_stream s) {
+    MH_REQUIRE(N >= 1 && N <= 16384, "mh_rank_mask_keep: N=%d unsupported (max 16384)", N);
+    MH_REQUIRE(len_keep >= 0 && len_keep <= N && slot && (keep_idx || len_keep == 0), "mh_rank_mask_keep: len_keep=%d of N=%d, or a null map", len_keep, N);
+    if (B == 0) return MH_OK;
+    int P = 2;
+    while (P < N) P <<= 1;
+    static const bool big = [] {
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(rank_mask_keep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8) == hipSuccess;
+    }();
+    MH_REQUIRE(big || P * 8 <= 65536, "mh_rank_mask_keep: %d bytes of LDS refused", P * 8);
+    hipLaunchKernelGGL(rank_mask_keep_kernel, dim3(B), dim3(1024), (size_t)P * sizeof(unsigned long long), (hipStream_t)s, noise, mask, keep_idx, slot, N, P,
+                       len_keep);
+    MH_LAUNCH_CHECK("mh_rank_mask_keep");
     return MH_OK;
 }
 
@@ -638,12 +690,15 @@ __global__ __launch_bounds__(256) void mask_apply_bwd_kernel(const T* dy, TDX* d
 
 // f32 in, D % 4 == 0: lane owns 4 columns (quad accesses), a wave owns one t at a time and has 8 batch rows in flight
 typedef float mb_f4 __attribute__((ext_vector_type(4)));
-template <typename TDX>
+template <typename TDX, bool KEEP = false>
 __global__ __launch_bounds__(256) void mask_apply_bwd_vec_kernel(const float* dy, TDX* dx, const float* __restrict__ mask,
                                                                  float* __restrict__ dtoken, float* __restrict__ dpos, int B, int Tn, int D,
-                                                                 int first, int token_scalar, int band, float* __restrict__ dbias) {
+                                                                 int first, int token_scalar, int band, float* __restrict__ dbias,
+                                                                 const int* __restrict__ slot = nullptr, int keep = 0) {
     // dbias [D] (round 5, may be null): += the column sums of dx AS STORED (rounded to TDX, what mh_colsum over dx would read): the
     // bias gradient of the projection in front, without that pass
+    // KEEP (round 9): the mask is read from slot [B, Tn - first] (< 0 = masked) and dx is the COMPACT tensor [B, first + keep, D]: a
+    // prefix row t goes to row t of its batch, a kept token to row first + slot, a masked row is not stored at all; the sums are the same
     __shared__ mb_f4 red[4][64];
     __shared__ mb_f4 reda[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -656,11 +711,16 @@ __global__ __launch_bounds__(256) void mask_apply_bwd_vec_kernel(const float* dy
             for (int b0 = 0; b0 < B; b0 += 8) {
                 mb_f4 g[8];
                 float mk[8];       // requested with the gradient rows: eight dependent mask loads per step were a latency chain
+                int sl[8];         // KEEP: the row of the batch's compact block, < 0 = masked
 #pragma unroll
                 for (int u = 0; u < 8; u++)
                     if (b0 + u < B) {
                         g[u] = *reinterpret_cast<const mb_f4*>(dy + ((long)(b0 + u) * Tn + t) * D + c);
-                        mk[u] = t >= first ? mask[(long)(b0 + u) * (Tn - first) + (t - first)] : 0.f;
+                        if constexpr (KEEP) {
+                            const int j = t >= first ? slot[(long)(b0 + u) * (Tn - first) + (t - first)] : t - first;
+                            sl[u] = (j < keep && j >= -first) ? first + j : -1;      // (a slot past the compact block is not stored)
+                            mk[u] = (t >= first && j < 0) ? 1.f : 0.f;
+                        } else mk[u] = t >= first ? mask[(long)(b0 + u) * (Tn - first) + (t - first)] : 0.f;
                     }
 #pragma unroll
                 for (int u = 0; u < 8; u++) {
@@ -672,7 +732,9 @@ __global__ __launch_bounds__(256) void mask_apply_bwd_vec_kernel(const float* dy
 #pragma unroll
                         for (int e = 0; e < 4; e++) sa[e] += bf2f(f2bf(g[u][e]));
                     } else sa += g[u];
-                    if (msk || (const void*)dx != (const void*)dy)
+                    if constexpr (KEEP) {
+                        if (!msk && sl[u] >= 0) st4(dx + ((long)(b0 + u) * (first + keep) + sl[u]) * D + c, g[u]);
+                    } else if (msk || (const void*)dx != (const void*)dy)
                         st4(dx + ((long)(b0 + u) * Tn + t) * D + c, msk ? (mb_f4){0.f, 0.f, 0.f, 0.f} : g[u]);
                 }
             }
@@ -775,6 +837,108 @@ extern "C" int mh_mask_apply_bwd(const void* dy, void* dx, const float* mask, fl
     DISPATCH2(dt_dy, dt_dx, MAB_)
 #undef MAB_
     MH_LAUNCH_CHECK("mh_mask_apply_bwd");
+    return MH_OK;
+}
+
+// ------------------------------------------------------------------ compact retention embed (round 9)
+// The projection in front of the mask-token select is only needed at the unmasked prefix and the kept tokens.  Compact layout
+// [B, first + keep, .]: row b * (first + keep) + t (t < first) = prefix row t, row b * (first + keep) + first + j = token keep_idx[b, j];
+// slot [B, T - first] is the inverse map (-1 = masked), both from mh_rank_mask_keep.  One row per wave iteration, 16-byte accesses.
+__global__ __launch_bounds__(256) void rows_gather_kernel(const uint4* __restrict__ x, const int* __restrict__ keep_idx, uint4* __restrict__ out,
+                                                          int B, int Tn, int K8, int first, int keep) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int Tc = first + keep;
+    const long rows = (long)B * Tc;
+    for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += (long)gridDim.x * 4) {
+        const int r = (int)(row % Tc);
+        const long b = row / Tc;
+        const int t = r < first ? r : first + keep_idx[b * keep + (r - first)];
+        if (t < 0 || t >= Tn) continue;        // (an index outside the sequence is never followed)
+        const uint4* src = x + (b * Tn + t) * K8;
+        for (int c = lane; c < K8; c += 64) out[row * K8 + c] = src[c];
+    }
+}
+
+extern "C" int mh_rows_gather(const void* x, const int* keep_idx, void* out, int B, int T, int K, int first, int keep, mh_stream s) {
+    MH_REQUIRE(first >= 0 && keep >= 0 && first + keep <= T && K % 8 == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0 && (keep_idx || keep == 0),
+               "mh_rows_gather: first=%d keep=%d T=%d K=%d (K %% 8 == 0, 16-byte aligned operands)", first, keep, T, K);
+    const long rows = (long)B * (first + keep);
+    if (rows == 0 || K == 0) return MH_OK;
+    hipLaunchKernelGGL(rows_gather_kernel, dim3((unsigned)min((long)mh_cdiv(rows, 4), 16384L)), dim3(256), 0, (hipStream_t)s, (const uint4*)x, keep_idx,
+                       (uint4*)out, B, T, K / 8, first, keep);
+    MH_LAUNCH_CHECK("mh_rows_gather");
+    return MH_OK;
+}
+
+// y[b, t] = (masked ? token : rc[compact row]) + pos[t]: the arithmetic of mask_apply_fwd_vec_kernel<bf16_t> on the dense projection
+__global__ __launch_bounds__(256) void mask_expand_fwd_kernel(const bf16_t* __restrict__ rc, float* __restrict__ y, const int* __restrict__ slot,
+                                                              const float* __restrict__ token, const float* __restrict__ pos, int B, int Tn, int D,
+                                                              int first, int keep) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long rows = (long)B * Tn;
+    for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += (long)gridDim.x * 4) {
+        const int t = (int)(row % Tn);
+        const long b = row / Tn;
+        const int j = t >= first ? slot[b * (Tn - first) + (t - first)] : t - first;
+        const bool masked = (t >= first && j < 0) || j >= keep;
+        const bf16_t* src = rc + (b * (first + keep) + first + j) * D;
+        for (int c = 4 * lane; c < D; c += 256) {
+            const mf_f4 v = masked ? *reinterpret_cast<const mf_f4*>(token + c) : ld4(src + c);
+            *reinterpret_cast<mf_f4*>(y + row * D + c) = v + *reinterpret_cast<const mf_f4*>(pos + (long)t * D + c);
+        }
+    }
+}
+
+extern "C" int mh_mask_expand_fwd(const void* rc, float* y, const int* slot, const float* token, const float* pos, int B, int T, int D, int first,
+                                  int keep, mh_stream s) {
+    MH_REQUIRE(first >= 0 && keep >= 0 && first + keep <= T && D % 4 == 0 && mh_quad_ok(rc, 2) &&
+                   (((uintptr_t)y | (uintptr_t)token | (uintptr_t)pos) & 15) == 0 && (slot || T == first),
+               "mh_mask_expand_fwd: first=%d keep=%d T=%d D=%d (D %% 4 == 0, aligned operands)", first, keep, T, D);
+    const long rows = (long)B * T;
+    if (rows == 0 || D == 0) return MH_OK;
+    hipLaunchKernelGGL(mask_expand_fwd_kernel, dim3((unsigned)min((long)mh_cdiv(rows, 4), 16384L)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)rc, y, slot,
+                       token, pos, B, T, D, first, keep);
+    MH_LAUNCH_CHECK("mh_mask_expand_fwd");
+    return MH_OK;
+}
+
+extern "C" int mh_mask_apply_bwd_keep(const float* dy, void* drc, const int* slot, float* dtoken, float* dpos, int B, int T, int D, int first,
+                                      int keep, float* dbias, mh_stream s) {
+    if (T == 0 || D == 0 || B == 0) return MH_OK;
+    MH_REQUIRE(first >= 0 && keep >= 0 && first + keep <= T && (slot || T == first) && mh_mask_apply_bwd_dbias_ok(dy, drc, dpos, D, MH_F32, MH_BF16),
+               "mh_mask_apply_bwd_keep: first=%d keep=%d T=%d D=%d (the quad form: D %% 4 == 0, D >= 256, 16-byte aligned operands)", first, keep, T, D);
+    const int band = 16;      // as mh_mask_apply_bwd (alone at B = 16, T = 4097, D = 512: 8 rows 105 us, 16: 85, 32: 117, 64: 187; the dense form 87)
+    dim3 gv(mh_cdiv(D, 256), mh_cdiv(T, band));
+    hipLaunchKernelGGL((mask_apply_bwd_vec_kernel<bf16_t, true>), gv, dim3(256), 0, (hipStream_t)s, dy, (bf16_t*)drc, (const float*)nullptr, dtoken, dpos,
+                       B, T, D, first, 0, band, dbias, slot, keep);
+    MH_LAUNCH_CHECK("mh_mask_apply_bwd_keep");
+    return MH_OK;
+}
+
+// dh [B, T, K] f32 = the compact gradient's rows at the prefix and the kept tokens, exact zeros at the masked ones
+__global__ __launch_bounds__(256) void rows_expand_zero_kernel(const float* __restrict__ dhc, const int* __restrict__ slot, float* __restrict__ dh,
+                                                               int B, int Tn, int K, int first, int keep) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long rows = (long)B * Tn;
+    for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += (long)gridDim.x * 4) {
+        const int t = (int)(row % Tn);
+        const long b = row / Tn;
+        const int j = t >= first ? slot[b * (Tn - first) + (t - first)] : t - first;
+        const bool masked = (t >= first && j < 0) || j >= keep;
+        const float* src = dhc + (b * (first + keep) + first + j) * K;
+        for (int c = 4 * lane; c < K; c += 256)
+            *reinterpret_cast<mf_f4*>(dh + row * K + c) = masked ? (mf_f4){0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const mf_f4*>(src + c);
+    }
+}
+
+extern "C" int mh_rows_expand_zero(const float* dhc, const int* slot, float* dh, int B, int T, int K, int first, int keep, mh_stream s) {
+    MH_REQUIRE(first >= 0 && keep >= 0 && first + keep <= T && K % 4 == 0 && (((uintptr_t)dhc | (uintptr_t)dh) & 15) == 0 && (slot || T == first),
+               "mh_rows_expand_zero: first=%d keep=%d T=%d K=%d (K %% 4 == 0, 16-byte aligned operands)", first, keep, T, K);
+    const long rows = (long)B * T;
+    if (rows == 0 || K == 0) return MH_OK;
+    hipLaunchKernelGGL(rows_expand_zero_kernel, dim3((unsigned)min((long)mh_cdiv(rows, 4), 16384L)), dim3(256), 0, (hipStream_t)s, dhc, slot, dh, B, T, K,
+                       first, keep);
+    MH_LAUNCH_CHECK("mh_rows_expand_zero");
     return MH_OK;
 }
 

@@ -1062,19 +1062,33 @@ def _sq_of(pred, tgt, mask):
 class EmbedMaskPosFn(Function):
     """(mask ? mask_token : h @ W^T + b) + pos -> f32 residual stream in ONE launch: retention_embed, random_masking's token select
     and `+ retention_gene_embed` (models/mirror.py:636-643, :691-693) as the projection's epilogue (mh_gemm_epi MASKPOS).
-    h [B, T, K] bf16; mask [B, T - first] (1 = masked); token [D]; pos [T, D]."""
+    h [B, T, K] bf16; mask [B, T - first] (1 = masked); token [D]; pos [T, D].
+    keepmap = (keep_idx, slot, keep) of the mask (K.rank_mask; round 9): the projection is only needed at the prefix and the kept
+    tokens, so their rows are gathered into a compact [B, first + keep, K] operand, multiplied (bias in the product's epilogue, bf16
+    out) and expanded by the select (mh_mask_expand_fwd); the backward multiplies the same compact rows (dr of a masked row is zero)
+    and expands the data gradient with exact zeros.  Same values as the dense launch, which a mask without a map takes."""
 
     @staticmethod
-    def forward(ctx, h32, h, w, b, mask, token, pos, first, prec):
+    def forward(ctx, h32, h, w, b, mask, token, pos, first, prec, keepmap=None):
         """h32: the tensor autograd tracks (its gradient is returned in f32); h: its bf16 copy, the operand."""
         wa = shadow(w, prec)
         Bn, T, Kd = h.shape
         N = wa.shape[0]
         out = torch.empty((Bn, T, N), device=h.device, dtype=f32)
         M = Bn * T
-        tail = K.linear_fused_tail(M)
         bd = None if b is None else b.detach()
         tok, ps = token.detach().reshape(-1).contiguous(), pos.detach().reshape(T, N).contiguous()
+        ctx.geom = (Bn, T, N, first, token.shape, pos.shape, prec)
+        ctx.params = (token, pos)
+        ctx.keep = None if keepmap is None else keepmap[2]
+        if keepmap is not None:
+            keep_idx, slot, keep = keepmap
+            hc = K.rows_gather(h, keep_idx, first, keep)
+            rc = _gemm_rows(hc, wa.t(), bias=bd, mma=prec.mma, out_dtype=bf16)        # what Fn.linear runs: ragged rows, small shapes
+            K.mask_expand_fwd(rc, slot, tok, ps, T, first, keep, out)
+            ctx.save_for_backward(hc, wa, w, b, slot)
+            return out
+        tail = K.linear_fused_tail(M)
         fork = _tail_fork() if tail else None
         K.linear_fused(h, wa, bd, out, K.epi_maskpos(mask, tok, ps, T, first), m_rows=M - tail)
         if tail and T - tail >= first:       # the last rows of the last slide through the composed ops
@@ -1085,42 +1099,75 @@ class EmbedMaskPosFn(Function):
         elif tail:
             raise K.MirrorHipError("EmbedMaskPosFn: the tail rows cross the unmasked prefix")
         ctx.save_for_backward(h, wa, w, b, mask)
-        ctx.geom = (Bn, T, N, first, token.shape, pos.shape, prec)
-        ctx.params = (token, pos)
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        h, wa, w, b, mask = ctx.saved_tensors
+        h, wa, w, b, mask = ctx.saved_tensors         # compact path: h is the gathered operand, mask the slot map
         Bn, T, N, first, tshape, pshape, prec = ctx.geom
+        keep = ctx.keep
+        Tc = T if keep is None else first + keep
         dy = dy.contiguous()
-        dr = torch.empty(dy.shape, device=dy.device, dtype=prec.act)          # gradient of the projection output (zero at masked rows)
+        # gradient of the projection output: zero at masked rows (dense), or only the prefix and kept rows (compact)
+        dr = torch.empty((Bn, Tc, N), device=dy.device, dtype=prec.act)
         token, pos = ctx.params
         dtok, s_tok = _gbuf_n(token, (N,))          # the kernel accumulates into both: straight into the gradient arena
         dpos, s_pos = _gbuf_n(pos, (T * N,))
         # the bias gradient of the projection = column sums of dr: the same pass leaves them (round 5; no mh_colsum launch over dr)
         db_in = None
-        if b is not None and ctx.needs_input_grad[3] and _BIAS_IN_PRODUCER and K.mask_apply_bwd_dbias_ok(dy, dr, dpos, N):
+        quad = K.mask_apply_bwd_dbias_ok(dy, dr, dpos, N)
+        if b is not None and ctx.needs_input_grad[3] and _BIAS_IN_PRODUCER and (quad or keep is not None):
             db_in = _gbuf(b, (N,))
-        K.mask_apply_bwd(dy, mask, dtok, dpos, Bn, T, N, first, False, out=dr, dbias=None if db_in is None else db_in[0])
+        dbias = None if db_in is None else db_in[0]
+        if keep is None:
+            K.mask_apply_bwd(dy, mask, dtok, dpos, Bn, T, N, first, False, out=dr, dbias=dbias)
+        elif quad:
+            K.mask_apply_bwd_keep(dy, mask, dtok, dpos, Bn, T, N, first, keep, out=dr, dbias=dbias)
+        else:       # the position table's slot of the gradient arena is not on a 16-byte boundary: its sums go through a buffer that is
+            dp = zeros((T * N,), dy.device)
+            K.mask_apply_bwd_keep(dy, mask, dtok, dp, Bn, T, N, first, keep, out=dr, dbias=dbias)
+            dpos.add_(dp)
         dtok, dpos = _gret(token, dtok, s_tok), _gret(pos, dpos, s_pos)
         # f32 data gradient: EncFanoutFn sums it with the target / cls gradients in one pass (mh_fanout_bwd reads f32)
         needs = (ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3])
-        dh, dw, db = _linear_rows_bwd(needs, h, wa, w, b, 0, T, prec, dr, dx_dtype=f32, db_have=db_in)
+        dh, dw, db = _linear_rows_bwd(needs, h, wa, w, b, 0, Tc, prec, dr, dx_dtype=f32, db_have=db_in)
+        if keep is not None and dh is not None:
+            dh = K.rows_expand_zero(dh, mask, T, first, keep)        # exact zeros at the masked rows
         return (dh, None, dw, db, None, None if dtok is None else dtok.reshape(tshape), None if dpos is None else dpos.reshape(pshape),
-                None, None)
+                None, None, None)
 
 
 def embed_mask_pos(h, w, b, mask, token, pos, first: int, prec: Precision):
     """MaskApplyFn(linear(h, w, b), mask, token, pos, first): one launch when h has a bf16 copy (layer_norm(bf16_copy=True)) or is
-    bf16 itself and the shapes are on the 256 x 256-tile kernel; the composed ops otherwise."""
+    bf16 itself and the shapes are on the 256 x 256-tile kernel; the composed ops otherwise.  A mask that carries its keep map
+    (K.rank_mask) takes EmbedMaskPosFn's compact path: only the prefix and the kept tokens are multiplied, forward and backward."""
     hb = h if h.dtype == bf16 else getattr(h, "_bf16", None)
     if (hb is not None and prec.act == bf16 and not prec.fp8_fwd and hb.is_contiguous() and tuple(hb.shape) == tuple(h.shape)
             and mask.dtype == f32 and mask.is_contiguous() and hb.shape[1] >= 256 and K.linear_fused_ok(hb, shadow(w, prec))
             and token.numel() == w.shape[0] and pos.numel() == h.shape[1] * w.shape[0]):
-        return EmbedMaskPosFn.apply(h, hb, w, b, mask, token, pos, first, prec)
+        keepmap = _keep_of(mask, hb.shape[0], hb.shape[1] - first)
+        # a dense launch of at most one round of 256 x 256 tiles cannot get shorter with fewer rows, and the compact path is four
+        # launches to its one: those shapes keep the MASKPOS epilogue
+        if keepmap is not None and -(-hb.shape[0] * hb.shape[1] // 256) * (w.shape[0] // 256) <= _EMBED_KEEP_TILES:
+            keepmap = None
+        return EmbedMaskPosFn.apply(h, hb, w, b, mask, token, pos, first, prec, keepmap)
     r = linear(h, w, b, prec=prec)
     return MaskApplyFn.apply(r, mask, token, pos, first, False)
+
+
+_EMBED_KEEP_TILES = _CUS      # (test hook, round 9) 0 = the compact path for every mask that carries its keep map
+
+
+def _keep_of(mask, Bn: int, n_tok: int):
+    """The keep map K.rank_mask left on `mask` (keep_idx [B, keep], slot [B, n_tok], keep), or None: no map, another geometry, or a mask
+    that torch has written since the ranking launch (the map would no longer describe it)."""
+    km = getattr(mask, "_keep", None)
+    if km is None or mask._version != 0 or tuple(mask.shape) != (Bn, n_tok):
+        return None
+    keep_idx, slot, keep = km
+    if tuple(slot.shape) != (Bn, n_tok) or tuple(keep_idx.shape) != (Bn, keep) or slot.device != mask.device:
+        return None
+    return km
 
 
 # ------------------------------------------------------------------ LayerNorm
@@ -2382,6 +2429,7 @@ def probe_point(x: torch.Tensor, name: str) -> torch.Tensor:
 
 # ------------------------------------------------------------------ masking
 def rank_mask(noise: torch.Tensor, len_keep: int) -> torch.Tensor:
+    """The mask carries its keep map (`mask._keep`, K.rank_mask): embed_mask_pos multiplies only the kept rows when it finds one."""
     return K.rank_mask(noise, len_keep)
 
 

@@ -1387,13 +1387,80 @@ def sample_weighted(cdf: torch.Tensor, count: int, seed: int, offset: int, dev_b
 
 
 # ----------------------------------------------------------------------------- masking
-def rank_mask(noise: torch.Tensor, len_keep: int) -> torch.Tensor:
+def rank_mask(noise: torch.Tensor, len_keep: int, keep_map: bool = True) -> torch.Tensor:
+    """mask [B, N] f32 (1 = masked): every row keeps the len_keep tokens of lowest noise.  keep_map: the same launch leaves the keep map
+    on the returned tensor, `mask._keep = (keep_idx [B, len_keep] int32, slot [B, N] int32, len_keep)` (mh_rank_mask_keep): the rows
+    the compact retention embed multiplies (functional.EmbedMaskPosFn)."""
     _chk(noise)
     noise = _contig(noise.float(), "noise")
     B, N = noise.shape
     mask = torch.empty_like(noise)
-    _lib.call("mh_rank_mask", _p(noise), _p(mask), B, N, len_keep, stream=_stream())
+    len_keep = int(len_keep)
+    if not keep_map or not 0 <= len_keep <= N:
+        _lib.call("mh_rank_mask", _p(noise), _p(mask), B, N, len_keep, stream=_stream())
+        return mask
+    keep_idx = torch.empty((B, len_keep), device=noise.device, dtype=torch.int32)
+    slot = torch.empty((B, N), device=noise.device, dtype=torch.int32)
+    _lib.call("mh_rank_mask_keep", _p(noise), _p(mask), _p(keep_idx), _p(slot), B, N, len_keep, stream=_stream())
+    mask._keep = (keep_idx, slot, len_keep)
     return mask
+
+
+def _keep_geom(slot, keep_idx, B, T, first, keep) -> None:
+    for t, shape in ((slot, (B, T - first)), (keep_idx, (B, keep))):
+        if t is not None and not (t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise MirrorHipError(f"keep map: expected a contiguous int32 {shape}, got {t.dtype} {tuple(t.shape)}")
+    if not (0 <= first and 0 <= keep and first + keep <= T):
+        raise MirrorHipError(f"keep map: first={first} keep={keep} of T={T}")
+
+
+def rows_gather(x: torch.Tensor, keep_idx: torch.Tensor, first: int, keep: int) -> torch.Tensor:
+    """[B, first + keep, K] bf16: the prefix rows and the kept tokens of x [B, T, K] bf16 (the compact layout of mh_rank_mask_keep)."""
+    _chk(x, keep_idx)
+    B, T, Kd = x.shape
+    _keep_geom(None, keep_idx, B, T, first, keep)
+    if x.dtype != torch.bfloat16 or not x.is_contiguous():
+        raise MirrorHipError("rows_gather: x must be a contiguous bf16 [B, T, K] tensor")
+    out = torch.empty((B, first + keep, Kd), device=x.device, dtype=torch.bfloat16)
+    _lib.call("mh_rows_gather", _p(x), _p(keep_idx), _p(out), B, T, Kd, first, keep, stream=_stream())
+    return out
+
+
+def mask_expand_fwd(rc: torch.Tensor, slot: torch.Tensor, token: torch.Tensor, pos: torch.Tensor, T: int, first: int, keep: int,
+                    out: torch.Tensor) -> torch.Tensor:
+    """out [B, T, D] f32 = (slot < 0 ? token : rc[compact row]) + pos[t] for the compact bf16 projection rc [B, first + keep, D]."""
+    _chk(rc, slot, token, pos, out)
+    B, Tc, D = rc.shape
+    _keep_geom(slot, None, B, T, first, keep)
+    if not (rc.dtype == torch.bfloat16 and rc.is_contiguous() and Tc == first + keep and out.dtype == torch.float32 and out.is_contiguous()
+            and tuple(out.shape) == (B, T, D) and token.dtype == pos.dtype == torch.float32 and token.is_contiguous() and pos.is_contiguous()
+            and token.numel() == D and pos.numel() == T * D):
+        raise MirrorHipError("mask_expand_fwd: bad operands")
+    _lib.call("mh_mask_expand_fwd", _p(rc), _p(out), _p(slot), _p(token), _p(pos), B, T, D, first, keep, stream=_stream())
+    return out
+
+
+def mask_apply_bwd_keep(dy, slot, dtoken, dpos, B, T, D, first, keep, out, dbias=None) -> None:
+    """mask_apply_bwd (f32 dy, the quad form) whose dx is the compact bf16 tensor out [B, first + keep, D]: masked rows are not stored."""
+    _chk(dy, slot, dtoken, dpos, out, dbias)
+    _keep_geom(slot, None, B, T, first, keep)
+    if not (dy.dtype == torch.float32 and dy.is_contiguous() and dy.numel() == B * T * D and out.dtype == torch.bfloat16 and out.is_contiguous()
+            and out.numel() == B * (first + keep) * D and dpos.dtype == dtoken.dtype == torch.float32 and dpos.numel() == T * D
+            and dtoken.numel() == D and (dbias is None or (dbias.dtype == torch.float32 and dbias.numel() == D and dbias.is_contiguous()))):
+        raise MirrorHipError("mask_apply_bwd_keep: bad operands")
+    _lib.call("mh_mask_apply_bwd_keep", _p(dy), _p(out), _p(slot), _p(dtoken), _p(dpos), B, T, D, first, keep, _p(dbias), stream=_stream())
+
+
+def rows_expand_zero(dhc: torch.Tensor, slot: torch.Tensor, T: int, first: int, keep: int) -> torch.Tensor:
+    """[B, T, K] f32: the compact gradient dhc [B, first + keep, K] f32 at the prefix and kept rows, exact zeros at the masked ones."""
+    _chk(dhc, slot)
+    B, Tc, Kd = dhc.shape
+    _keep_geom(slot, None, B, T, first, keep)
+    if not (dhc.dtype == torch.float32 and dhc.is_contiguous() and Tc == first + keep):
+        raise MirrorHipError("rows_expand_zero: dhc must be a contiguous f32 [B, first + keep, K] tensor")
+    dh = torch.empty((B, T, Kd), device=dhc.device, dtype=torch.float32)
+    _lib.call("mh_rows_expand_zero", _p(dhc), _p(slot), _p(dh), B, T, Kd, first, keep, stream=_stream())
+    return dh
 
 
 def mask_apply_fwd(x, mask, token, pos, B, T, D, first, token_scalar, out=None) -> None:

@@ -665,6 +665,8 @@ class MIRROR(nn.Module):
                 prefetch_alignment_gather(wsi_alignment_emb, rna_alignment_emb, ag[0])
         main.wait_event(mask_ready)
         wsi_mask.record_stream(main)
+        for t in getattr(wsi_mask, "_keep", ())[:2]:      # the keep map ranked with it (the compact retention embed reads it)
+            t.record_stream(main)
         Fn.probe("decoder_start")
         wsi_retention_emb, wsi_mask = self.wsi_encoder.forward_retention_head(
             wsi_full, mask_ratio=wsi_mask_ratio, mask=wsi_mask, key_padding_mask=wsi_key_padding_mask,
