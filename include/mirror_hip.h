@@ -892,6 +892,48 @@ int mh_surv_risk(const float* logits, int64_t ld, int N, int M, float* risk, mh_
 int mh_cindex_counts(const uint8_t* event, const double* time, const float* estimate, int64_t n, float tied_tol, int64_t* counts,
                      mh_stream s);
 
+/* ---------------------------------------------------------------- continuous-time survival: Cox loss and log-rank test (added in v122)
+ * The Cox proportional-hazards partial likelihood of a one-logit head (MCAT / PORPOISE `CoxSurvLoss`, DeepSurv, pycox) on the
+ * follow-up time itself, no bins.  scores r [N] f32 read through the row stride ld (a [N] vector, or one column of a matrix);
+ * time [N] f64, 8-byte aligned; e_i = (censoring_i == 1) read through dt_c (MH_SV_*), anything else is censored.
+ *   m = max_j r_j,  w_j = exp(r_j - m) in f64
+ *   S_i = sum_j [t_j >= t_i] w_j     D_i = sum_j [t_j == t_i][e_j] w_j     d_i = sum_j [t_j == t_i][e_j]
+ *   l_i = sum_{j < i} [t_j == t_i][e_j]
+ *   f_i = 0 (MH_COX_BRESLOW);  l_i / d_i on event rows, else 0 (MH_COX_EFRON);   den_i = S_i - f_i D_i  (> 0 whenever w_i > 0)
+ *   loss_i = e_i (log den_i + m - r_i)
+ * which, summed over a tie group in index order, is the textbook Breslow / Efron partial likelihood.  Reductions: none (rows only),
+ * sum, mean = sum / max(n_events, 1) (DeepSurv / pycox), batch = sum / N (MCAT); no events: loss 0, gradient 0.  n_events and the
+ * divisor stay on the device.  A NaN time gives NaN in that row's loss and gradient and the row is in no other row's risk set; a NaN
+ * logit makes m, and with it every row, NaN.  Domain: max r - min r <= 700 (beyond it w underflows in f64); 1 <= N <= 65536.
+ * Every sum is f64 in a fixed order (per row four partial sums over ascending j, added in order; rows folded by one block): bitwise
+ * reproducible, no atomics, nothing allocated, no host wait, graph capturable.  Only the stores to loss_rows / out / dlogits round to
+ * f32. */
+#define MH_COX_BRESLOW 0
+#define MH_COX_EFRON 1
+#define MH_COX_RED_NONE 0
+#define MH_COX_RED_SUM 1
+#define MH_COX_RED_MEAN 2
+#define MH_COX_RED_BATCH 3
+/* bytes of the workspace the forward fills and the backward reads (m, n_events, w, den, f and the f64 rows: 8 (4 N + 2)); -1 for a
+ * bad N */
+int64_t mh_cox_workspace_bytes(int N);
+/* loss_rows [N] f32 (nullable) = loss_i; out[0] (nullable, needs a reduction other than none; STORED, not accumulated) = the reduced
+ * loss.  Three launches: m / w / n_events, the pair pass (64 rows per block, one per lane; the block's four waves split each LDS
+ * tile of 256 j), the fold. */
+int mh_cox_loss_fwd(const float* logits, int64_t ld, const double* time, const void* censoring, int dt_c, int N, int ties,
+                    int reduction, float* loss_rows, float* out, void* workspace, mh_stream s);
+/* dlogits[k * ld_d] = d(sum_i g_i loss_i) / d r_k = w_k sum_i q_i ([t_k > t_i] + [t_k == t_i](1 - e_k f_i)) - g_k e_k with
+ * q_i = g_i e_i / den_i, where g_i = g[i] (g_per_row, reduction none only) or the reduction's coefficient times g[0].  workspace: as
+ * the forward with the same inputs, ties and N left it (ties is already folded into f there; the scores enter through w). */
+int mh_cox_loss_bwd(const float* logits, int64_t ld, const double* time, const void* censoring, int dt_c, int N, int ties,
+                    int reduction, const float* g, int g_per_row, const void* workspace, float* dlogits, int64_t ld_d, mh_stream s);
+/* Two-group log-rank statistics: event [n] (nonzero = event), time [n] f64, group [n] (nonzero = group 1), 1 <= n <= 65536.
+ * For every distinct event time tau: n(tau) = #{t_j >= tau}, n1(tau) the same within group 1, d(tau) = #{t_j == tau, event_j},
+ * d1(tau); stats f64 [4] = {O1 = sum d1, E1 = sum d n1 / n, V = sum n1 (n - n1) d (n - d) / (n^2 (n - 1)) over n > 1, n_events}.
+ * The first event row (smallest index) at a time owns its term; counts are integers, the terms f64, added in index order by one
+ * block.  Rows with a NaN time are ignored.  chi2 = (O1 - E1)^2 / V and p = erfc(sqrt(chi2 / 2)) are the caller's. */
+int mh_logrank_stats(const uint8_t* event, const double* time, const uint8_t* group, int64_t n, double* stats, mh_stream s);
+
 /* ---------------------------------------------------------------- downstream subtyping step (train_subtyping.py, v120)
  * logits / scores [N x C] f32, row stride ld (the f32 output of mirror_classifier, models/mirror.py:667-707); labels [N] int32 /
  * int64 read through dt_l (MH_SV_I32 / MH_SV_I64 of the survival block).  Every entry point is deterministic (no float atomics:

@@ -1,7 +1,8 @@
 """mirror_amd — MI355X-native (gfx950) implementation of the MIRROR pre-training hot path.
 
 Host side mirrors the reference's Python surface (`models.mirror`, `losses.MIRRORLoss`,
-`losses.InfoNCE`; the survival losses and metric of train_survival.py in `losses` and `survival`; the subtyping losses
+`losses.InfoNCE`; the survival losses and metric of train_survival.py in `losses` and `survival`, with the Cox
+partial-likelihood loss and the log-rank test beside them; the subtyping losses
 and metrics of train_subtyping.py in `losses` and `metrics`; the zero-shot retrieval metrics and top-k
 neighbours of the alignment heads in `retrieval`; the kNN probe of frozen embeddings in `knn`);
 all arithmetic runs in hand-written HIP kernels behind the C ABI of `include/mirror_hip.h` (`mirror_amd/lib/libmirror_hip.so`).  There is no CPU fallback.
@@ -15,7 +16,8 @@ def install_aliases() -> None:
     """Make the reference trainers' own imports resolve to this build: `import models`
     (train_mirror.py:43), `from losses import MIRRORLoss` (:889-891), `from losses import InfoNCE`
     (train_pretrain.py:43), `from losses import CrossEntropySurvLoss, NLLSurvLoss` (train_survival.py:47) and the sub-module paths
-    `models.mirror`, `losses.mirror_loss`, `losses.info_nce`, `losses.nll_surv`, `losses.cross_entropy_surv`.
+    `models.mirror`, `losses.mirror_loss`, `losses.info_nce`, `losses.nll_surv`, `losses.cross_entropy_surv`;
+    `from losses import CoxSurvLoss` and `losses.cox_surv` resolve too.
     Call it before the trainer's imports run (sitecustomize.py or the first lines of the script)."""
     import importlib
     import sys
@@ -26,6 +28,7 @@ def install_aliases() -> None:
     info_nce = importlib.import_module(__name__ + ".losses.info_nce")
     nll_surv = importlib.import_module(__name__ + ".losses.nll_surv")
     ce_surv = importlib.import_module(__name__ + ".losses.cross_entropy_surv")
+    cox_surv = importlib.import_module(__name__ + ".losses.cox_surv")
     sys.modules["models"] = models
     sys.modules["models.mirror"] = mirror_mod
     sys.modules["losses"] = losses
@@ -33,3 +36,4 @@ def install_aliases() -> None:
     sys.modules["losses.info_nce"] = info_nce
     sys.modules["losses.nll_surv"] = nll_surv
     sys.modules["losses.cross_entropy_surv"] = ce_surv
+    sys.modules["losses.cox_surv"] = cox_surv

@@ -221,6 +221,9 @@ _SIGS = {
     "mh_surv_loss_bwd": [P, L, P, I, P, I, I, I, I, F, F, F, F, P, I, F, P],
     "mh_surv_risk": [P, L, I, I, P],
     "mh_cindex_counts": [P, P, P, L, F, P],
+    "mh_cox_loss_fwd": [P, L, P, P, I, I, I, I, P, P, P],
+    "mh_cox_loss_bwd": [P, L, P, P, I, I, I, I, P, I, P, P, L],
+    "mh_logrank_stats": [P, P, P, L, P],
     "mh_cls_ce_fwd": [P, L, P, I, I, I, F, L, P, P, I],
     "mh_cls_ce_bwd": [P, L, P, I, I, I, F, L, P, I, P],
     "mh_cls_confusion": [P, L, I, P, I, I, I, P, P],
@@ -239,7 +242,7 @@ EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "
                                  "mh_rna_block_lds_bytes", "mh_rna_block_fits",
                                  "mh_gemm_workspace_bytes", "mh_layernorm_bwd_workspace_bytes", "mh_nys_attn3_workspace_bytes",
                                  "mh_pinv_chain_workspace_bytes", "mh_resconv_bwd_workspace_bytes", "mh_mask_apply_bwd_dbias_ok",
-                                 "mh_retrieval_workspace_bytes", "mh_retrieval_topk_workspace_bytes"])
+                                 "mh_retrieval_workspace_bytes", "mh_retrieval_topk_workspace_bytes", "mh_cox_workspace_bytes"])
 
 _lib = None
 
@@ -305,6 +308,11 @@ def load() -> C.CDLL:
                              "__graft_entry__.build())")
     lib.mh_retrieval_topk_workspace_bytes.restype = C.c_int64
     lib.mh_retrieval_topk_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int]
+    if not hasattr(lib, "mh_cox_workspace_bytes"):
+        raise MirrorHipError(f"{LIB_PATH} lacks mh_cox_workspace_bytes: rebuild the library (`make -C mirror_amd/csrc`, or "
+                             "__graft_entry__.build())")
+    lib.mh_cox_workspace_bytes.restype = C.c_int64
+    lib.mh_cox_workspace_bytes.argtypes = [C.c_int]
     for name, sig in _SIGS.items():
         fn = getattr(lib, name, None)
         if fn is None:      # entry points added within a generation (no argument list changed): an older build lacks them

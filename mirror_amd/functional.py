@@ -2985,6 +2985,36 @@ class SurvLossFn(Function):
         return dx, None, None, None, None, None, None
 
 
+class CoxLossFn(Function):
+    """Cox partial-likelihood loss of f32 scores [N] or [N, 1] against follow-up times and the event flag `censoring == 1`
+    (csrc/cox.hip; the definition is in include/mirror_hip.h).  ties: "breslow" / "efron"; reduction: "none" ([N]), "sum", "mean"
+    (sum / max(n_events, 1)), "batch" (sum / N).  Times of any real dtype are converted to f64 on the device.  Saved: the inputs and
+    the forward's f64 workspace (m, n_events, w, den, f), which the one-launch backward reads.  Gradients flow to the logits only."""
+
+    @staticmethod
+    def forward(ctx, logits, event_times, censoring, ties, reduction):
+        K._chk(logits, event_times, censoring)
+        N = logits.shape[0]
+        t64 = event_times.reshape(-1).to(torch.float64)
+        ties_c, red_c = K.COX_TIES[ties], K.COX_RED[reduction]
+        ws = K.cox_workspace(N, logits.device)
+        if reduction == "none":
+            res = torch.empty((N,), device=logits.device, dtype=f32)
+            K.cox_loss_fwd(logits, t64, censoring, ties_c, red_c, res, None, ws)
+        else:
+            out = torch.empty((1,), device=logits.device, dtype=f32)
+            K.cox_loss_fwd(logits, t64, censoring, ties_c, red_c, None, out, ws)
+            res = out.reshape(())
+        ctx.save_for_backward(logits, t64, censoring, ws)
+        ctx.cfg = (ties_c, red_c)
+        return res
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, t64, censoring, ws = ctx.saved_tensors
+        return K.cox_loss_bwd(logits, t64, censoring, *ctx.cfg, g, ws), None, None, None, None
+
+
 class ClsCELossFn(Function):
     """Cross-entropy with label smoothing of f32 logits [N, C] against integer labels [N] (timm's LabelSmoothingCrossEntropy,
     nn.CrossEntropyLoss(ignore_index, reduction, label_smoothing)), one HIP launch per direction.  Returns a 0-d tensor for

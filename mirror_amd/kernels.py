@@ -2194,6 +2194,83 @@ def cindex_counts(event_u8: torch.Tensor, time_f64: torch.Tensor, est_f32: torch
     return counts
 
 
+# ----------------------------------------------------------------------------- Cox loss and log-rank test (csrc/cox.hip)
+COX_TIES = {"breslow": 0, "efron": 1}
+COX_RED = {"none": 0, "sum": 1, "mean": 2, "batch": 3}
+COX_MAX_N = 65536
+
+
+def _cox_inputs(logits: torch.Tensor, time_f64: torch.Tensor, censoring: torch.Tensor):
+    """(logits, row stride, time, censoring, dt_c, N) checked for mh_cox_loss_*: logits [N] or [N, 1] f32 read in place through
+    their stride, time contiguous f64 [N], censoring [N] of a supported dtype."""
+    _chk(logits, time_f64, censoring)
+    if logits.dtype != torch.float32 or not (logits.dim() == 1 or (logits.dim() == 2 and logits.shape[1] == 1)):
+        raise MirrorHipError(f"Cox logits must be f32 [N] or [N, 1], got {logits.dtype} {tuple(logits.shape)}")
+    N = logits.shape[0]
+    if N < 1 or N > COX_MAX_N:
+        raise MirrorHipError(f"Cox loss needs 1 <= N <= {COX_MAX_N} rows, got {N}")
+    ld = logits.stride(0) if N > 1 else 1
+    if ld < 1:
+        logits, ld = logits.contiguous(), 1
+    if time_f64.numel() != N or censoring.numel() != N:
+        raise MirrorHipError(f"event_times / censoring need {N} elements, got {time_f64.numel()} / {censoring.numel()}")
+    if time_f64.dtype != torch.float64:
+        raise MirrorHipError(f"Cox times must be f64 here (CoxLossFn converts them), got {time_f64.dtype}")
+    if censoring.dtype not in _SV_C:
+        raise MirrorHipError(f"censoring must be bool, uint8, int32, int64 or f32, got {censoring.dtype}")
+    t, c = time_f64.reshape(-1).contiguous(), censoring.reshape(-1).contiguous()
+    return logits, ld, t, c, _SV_C[c.dtype], N
+
+
+def cox_workspace(N: int, device) -> torch.Tensor:
+    """The f64 workspace the forward fills and the backward reads (mh_cox_workspace_bytes)."""
+    nbytes = int(_lib.load().mh_cox_workspace_bytes(int(N)))
+    if nbytes < 0:
+        raise MirrorHipError(f"Cox loss needs 1 <= N <= {COX_MAX_N} rows, got {N}")
+    return torch.empty((nbytes // 8,), device=device, dtype=torch.float64)
+
+
+def cox_loss_fwd(logits, time_f64, censoring, ties: int, reduction: int, rows: Optional[torch.Tensor], out: Optional[torch.Tensor],
+                 ws: torch.Tensor) -> None:
+    """rows [N] f32 (optional) = the per-row Cox losses; out [1] (optional) = their reduction (stored); ws = cox_workspace(N)."""
+    logits, ld, t, c, dt_c, N = _cox_inputs(logits, time_f64, censoring)
+    _chk(rows, out, ws)
+    assert ws.dtype == torch.float64 and ws.is_contiguous() and ws.numel() >= 4 * N + 2
+    assert out is None or (out.dtype == torch.float32 and out.numel() >= 1)
+    assert rows is None or (rows.dtype == torch.float32 and rows.is_contiguous() and rows.numel() == N)
+    _lib.call("mh_cox_loss_fwd", _p(logits), ld, _p(t), _p(c), dt_c, N, ties, reduction, _p(rows), _p(out), _p(ws), stream=_stream())
+
+
+def cox_loss_bwd(logits, time_f64, censoring, ties: int, reduction: int, g: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """dlogits (f32, the logits' shape) for the upstream g: one element, or one per row when reduction is none."""
+    logits, ld, t, c, dt_c, N = _cox_inputs(logits, time_f64, censoring)
+    _chk(g, ws)
+    assert ws.dtype == torch.float64 and ws.is_contiguous() and ws.numel() >= 4 * N + 2
+    g = g.reshape(-1).contiguous().float()
+    per_row = reduction == COX_RED["none"]
+    if g.numel() != (N if per_row else 1):
+        raise MirrorHipError(f"Cox loss upstream gradient must have {N if per_row else 1} elements, got {g.numel()}")
+    dx = torch.empty(logits.shape, device=logits.device, dtype=torch.float32)
+    _lib.call("mh_cox_loss_bwd", _p(logits), ld, _p(t), _p(c), dt_c, N, ties, reduction, _p(g), int(per_row and N > 1), _p(ws),
+              _p(dx), 1, stream=_stream())
+    return dx
+
+
+def logrank_stats(event_u8: torch.Tensor, time_f64: torch.Tensor, group_u8: torch.Tensor) -> torch.Tensor:
+    """f64 [4] {O1, E1, V, n_events} of the two-group log-rank test, on the device (no sync)."""
+    _chk(event_u8, time_f64, group_u8)
+    n = event_u8.numel()
+    assert event_u8.dtype == torch.uint8 and time_f64.dtype == torch.float64 and group_u8.dtype == torch.uint8
+    assert event_u8.is_contiguous() and time_f64.is_contiguous() and group_u8.is_contiguous()
+    if time_f64.numel() != n or group_u8.numel() != n:
+        raise MirrorHipError(f"log-rank inputs differ in length: {n}, {time_f64.numel()}, {group_u8.numel()}")
+    if n < 1 or n > COX_MAX_N:
+        raise MirrorHipError(f"log-rank test needs 1 <= n <= {COX_MAX_N} samples, got {n}")
+    stats = torch.empty((4,), device=event_u8.device, dtype=torch.float64)
+    _lib.call("mh_logrank_stats", _p(event_u8), _p(time_f64), _p(group_u8), n, _p(stats), stream=_stream())
+    return stats
+
+
 # ----------------------------------------------------------------------------- subtyping step (train_subtyping.py)
 CLS_RED = {"none": 0, "mean": 1, "sum": 2}
 NO_IGNORE = -(1 << 63)          # ignore_index that no int32 label can equal (timm's loss has none)

@@ -1,14 +1,17 @@
 """Survival validation metrics of train_survival.py on HIP kernels: the risk score of :1431-1433 and the censored concordance
 index of :1460-1465 (`sksurv.metrics.concordance_index_censored`, restated from its documented definition; sksurv is not a
-dependency).  Both take device tensors."""
+dependency), and the two-group log-rank test of a high / low risk split that sits beside it in a results table.  All take
+device tensors."""
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
 
 from . import kernels as K
 
-__all__ = ["concordance_index_censored", "risk_scores"]
+__all__ = ["concordance_index_censored", "logrank_by_median", "logrank_test", "risk_scores"]
 
 
 def risk_scores(logits: torch.Tensor) -> torch.Tensor:
@@ -44,3 +47,39 @@ def concordance_index_censored(event_indicator: torch.Tensor, event_time: torch.
         raise ValueError("Data has no comparable pairs, cannot estimate concordance index.")
     cindex = np.float64((con + 0.5 * tie) / comp)
     return cindex, con, dis, tie, ttime
+
+
+def logrank_test(event_indicator: torch.Tensor, event_time: torch.Tensor, group: torch.Tensor):
+    """Two-group log-rank test: (chi2, p, observed1, expected1, variance) as Python floats.
+
+    For every distinct event time tau: n = #{t_j >= tau}, n1 the same within group 1 (`group != 0`), d = #{t_j == tau, event_j},
+    d1.  observed1 = sum d1, expected1 = sum d n1 / n, variance = sum n1 (n - n1) d (n - d) / (n^2 (n - 1)) over n > 1,
+    chi2 = (observed1 - expected1)^2 / variance and p = erfc(sqrt(chi2 / 2)), the survival function of chi-square with one degree
+    of freedom.  The sums are one launch on the device (integer counts, f64 terms in a fixed order), read back with one sync;
+    `event_time` is converted to f64 on the device and samples with a NaN time are ignored.  Raises ValueError when the variance
+    is 0: no events, or one group empty at every event time.  At most 65536 samples."""
+    n = event_indicator.numel()
+    if event_time.numel() != n or group.numel() != n:
+        raise ValueError(f"event_indicator, event_time and group differ in length: {n}, {event_time.numel()}, {group.numel()}")
+    if n == 0:
+        raise ValueError("logrank_test: empty input")
+    K._chk(event_indicator, event_time, group)
+
+    def as_u8(x):
+        x = x.reshape(-1)
+        return (x if x.dtype == torch.bool else x != 0).contiguous().view(torch.uint8)
+
+    stats = K.logrank_stats(as_u8(event_indicator), event_time.reshape(-1).to(torch.float64).contiguous(), as_u8(group))
+    o1, e1, var, n_events = (float(v) for v in stats.cpu().numpy())
+    if n_events == 0:
+        raise ValueError("All samples are censored")
+    if not var > 0.0:
+        raise ValueError("log-rank variance is 0: one group is empty at every event time")
+    chi2 = (o1 - e1) ** 2 / var
+    return chi2, math.erfc(math.sqrt(chi2 / 2.0)), o1, e1, var
+
+
+def logrank_by_median(event_indicator: torch.Tensor, event_time: torch.Tensor, risk: torch.Tensor):
+    """logrank_test of the split `risk > median(risk)` (torch.median: the lower of the two middle values for an even count)."""
+    risk = risk.reshape(-1)
+    return logrank_test(event_indicator, event_time, risk > risk.median())
