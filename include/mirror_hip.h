@@ -33,7 +33,7 @@ extern "C" {
 typedef void* mh_stream; /* hipStream_t */
 
 const char* mh_last_error(void);
-int mh_version(void);       /* 122 */
+int mh_version(void);       /* 123 */
 int mh_exp_build(void);      /* 1: built with -DMH_EXP (timing-experiment switches compiled in); the shipped build returns 0 */
 /* number of visible HIP devices whose arch is gfx950; <=0 means the library cannot run here */
 int mh_device_ok(void);
@@ -188,20 +188,72 @@ int mh_layernorm_fwd_dual(const float* x, const float* gamma, const float* beta,
 int mh_layernorm_fwd_q8(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                         int batches, int rows_per_batch, int D, int64_t x_bs, int64_t y_bs, float eps, void* q8, unsigned* ring,
                         const float* tick, float margin, float* scale, mh_stream s);
-/* dx = d/dx, dgamma/dbeta accumulated (+=, f32; caller zeroes them). dy uses y's addressing.
- * workspace (optional, f32, ws_floats >= 2*D): per-block dgamma/dbeta partials are written there and folded by a second
- * small launch instead of thousands of same-address atomics; size it 2*D*min(rows/16, 1024) floats for full speed. */
-int64_t mh_layernorm_bwd_workspace_bytes(int64_t rows, int D);      /* full-speed size of `workspace` below */
-int mh_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                     void* dx, float* dgamma, float* dbeta,
-                     int batches, int rows_per_batch, int D, int64_t x_bs, int64_t y_bs,
-                     int dt_x, int dt_dy, int dt_dx, int accumulate_dx, float* workspace, int64_t ws_floats, mh_stream s);
+/* LayerNorm backward: ONE entry point, described by a zero-initialised mh_ln_bwd.  dx = d loss / d x; dgamma / dbeta are accumulated
+ * (+=, f32; the caller zeroes them); dy uses y's addressing.  Beside the base block the descriptor holds four optional riders, work
+ * of a neighbouring op done while this launch holds the operands.  A rider is present exactly when its lead pointer is non-NULL; an
+ * all-zero rider block means absent (l == 0 beside gadd == NULL is l = 1).  Accepted combinations: none; landmark; landmark + ReLU;
+ * fan; drop; drop + fan.  Anything else, or a rider whose conditions below do not hold, is refused with MH_EINVAL before the first
+ * launch: a refused call has touched nothing.
+ * Every rider needs the WORKSPACE FORM: D % 4 == 0, x_bs % 4 == y_bs % 4 == 0, dy / x / dx / gamma 16-byte aligned, >= 64 rows and
+ * a workspace of >= 2 D floats (3 D where said).  A call without a rider that is off that form runs on the same-address-atomics forms. */
+int64_t mh_layernorm_bwd_workspace_bytes(int64_t rows, int D);      /* full-speed size of mh_ln_bwd.workspace */
+typedef struct {
+    /* ---- base */
+    const void* dy;               /* dt_dy */
+    const void* x;                /* dt_x */
+    const float *gamma, *mean, *rstd;
+    void* dx;                     /* dt_dx == dt_x */
+    float *dgamma, *dbeta;        /* [D] f32, += */
+    int32_t batches, rows_per_batch, D;
+    int64_t x_bs, y_bs;           /* elements per batch of x / dx and of dy */
+    int32_t dt_x, dt_dy, dt_dx;   /* MH_F32 / MH_BF16 */
+    int32_t accumulate_dx;        /* dx += instead of dx = */
+    float* workspace;             /* optional, f32: per-block dgamma / dbeta partials are written there and folded by a second small */
+    int64_t ws_floats;            /* launch instead of thousands of same-address atomics; 2 D min(rows / 16, 1024) floats for full speed */
+    /* ---- landmark rider: the backward of mh_layernorm_fwd_lm.  dy row i of batch b also receives gadd[b, (i + pad) / l] / l, where
+     * gadd [batches, (pad + rows_per_batch) / l, D] in dy's dtype, 16-byte aligned, = d loss / d xpm; l >= 1, pad >= 0,
+     * (pad + rows_per_batch) % l == 0.  row_mask / lm_scale (nullable, need gadd): the forward's mask and scale (see there) */
+    const void* gadd;
+    int32_t pad, l;
+    const float* row_mask;        /* f32 [batches, pad + rows_per_batch]: a masked row's total dy is zero */
+    const float* lm_scale;        /* f32 [batches, (pad + rows_per_batch) / l]: multiplies the group's gadd */
+    /* ---- ReLU rider (needs gadd; f32 x, bf16 dy, D % 4 == 0): x rows [relu_first, relu_first + relu_rows) of every batch, a range
+     * inside the batch, are the output of a ReLU (`_fc1 = Linear + ReLU`, models/mirror.py:346, :652-654, feeds layer 1's norm):
+     * their total gradient is written to relu_out (bf16 [batches, relu_rows, D], 8-byte aligned) as x > 0 ? dx : 0, the operand of
+     * _fc1's weight gradient, and NOT as f32 dx (no separate ReLU-backward pass); the other rows (cls) keep their f32 dx */
+    void* relu_out;
+    int32_t relu_first, relu_rows;
+    float* relu_db;               /* nullable, f32 [D], needs relu_out and a 16-byte aligned workspace of >= 3 D floats: += the column
+                                     sums of relu_out as stored, _fc1's bias gradient, a third partial row (no mh_colsum pass) */
+    /* ---- fan rider (excludes gadd; f32 x / dx, dy f32 or bf16, rows_per_batch >= 2, D % 4 == 0): the LayerNorm output fans out (the
+     * WSI encoder's final norm: decoder input, retention target = rows 1.., cls row; models/mirror.py:684-700, :833).  dy row i >= 1
+     * of batch b also receives fan_alpha * fan_bf16[b, i - 1] (bf16 [batches, rows_per_batch - 1, D], 8-byte aligned: the masked MSE
+     * hands its target gradient over as -dpred) and row 0 fan_cls[b] — the three-way sum mh_fanout_bwd writes is formed while this
+     * launch reads its operands */
+    const void* fan_bf16;
+    float fan_alpha;
+    const float* fan_cls;         /* nullable, f32 [batches, D], 16-byte aligned */
+    /* ---- drop rider (excludes gadd, may carry the fan rider; f32 x / dx, dy f32 or bf16, D % 8 == 0, D <= 1024, a 16-byte aligned
+     * workspace of >= 3 D floats): x is the output of `resid + Dropout_p(Linear(core))` ([3P] to_out = Sequential(Linear, Dropout)
+     * and TransLayer's residual add, models/mirror.py:312), so this launch's dx is that Dropout's upstream gradient: drop_out
+     * (bf16 [batches, drop_rows_per_batch, D], 8-byte aligned) receives mask * dx / (1 - p) on the lite Philox stream (the masks
+     * mh_gemm_epi DROPADD drew for (seed, offset + *dev_base, element)), the operand of to_out's two gradient products, and drop_db
+     * its column sums: mh_dropout_lite_colsum's pass over dx is not launched */
+    void* drop_out;
+    float drop_p;                 /* in [0, 1) */
+    uint64_t drop_seed, drop_offset;        /* drop_offset % 8 == 0 */
+    const uint64_t* drop_base;    /* nullable device-side base added to drop_offset */
+    float* drop_db;               /* required, f32 [D]: += to_out's bias gradient */
+    int32_t drop_rows_per_batch;  /* >= rows_per_batch: rows per batch of the Dropout's tensor; a norm over the first rows of a
+                                     square-padded sequence leaves the rows behind them to the caller (zeros) */
+} mh_ln_bwd;
+int mh_layernorm_bwd(const mh_ln_bwd* d, mh_stream s);
 
 /* LayerNorm of a Nystrom layer that also leaves the landmark means of its output (models/mirror.py:298 + [3P] NystromAttention's
  * front padding and `q_landmarks = reduce(q, '... (n l) d -> ... n d', 'sum') / l`): x f32 [batches, >= rows, D] (x_bs elements per
  * batch) -> y bf16 [batches, pad + rows, D] (pad zero rows first, written here) and xpm f32 [batches, (pad + rows) / l, D] =
  * the mean of each group of l consecutive rows of y.  to_qkv is linear and bias-free, so the landmarks are to_qkv(xpm)[:, :2D].
- * mh_layernorm_bwd_lm: mh_layernorm_bwd whose dy rows also receive gadd[b, (i + pad) / l] / l (gadd, in dy's dtype, = d loss / d xpm).
+ * Its backward is mh_layernorm_bwd with the landmark rider (gadd = d loss / d xpm).
  * xpm (f32) may be NULL when only the bf16 means are wanted (they are the landmark rows behind the sequence in to_qkv's operand). */
 int mh_layernorm_fwd_lm(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, void* xpm,
                         void* xpm_bf16, int batches, int rows, int D, int64_t x_bs, int pad, int l, float eps, const float* row_mask,
@@ -210,42 +262,8 @@ int mh_layernorm_fwd_lm(const float* x, const float* gamma, const float* beta, v
                            sequence — rows with a zero entry leave as zero rows ([3P] `q, k, v = t * mask[..., None]` through the bias-free
                            to_qkv) and stay out of their group's sum: the landmark rows are masked sums / l (the caller scales them by
                            l / valid count — or passes those factors as lm_scale, f32 [batches, (pad + rows) / l], nullable: the landmark rows then leave as
-                           the masked MEANS); mh_layernorm_bwd_lm takes the same mask and scale */
+                           the masked MEANS); mh_layernorm_bwd's landmark rider takes the same mask and scale */
                         /* xpm_bf16 (optional): the bf16 rounding of xpm, the B operand of the landmark projection's weight gradient */
-/* mh_layernorm_bwd for a LayerNorm output that fans out (the WSI encoder's final norm: decoder input, retention target = rows 1..,
- * cls row; models/mirror.py:684-700, :833): f32 x / dx, dy f32 or bf16 (dt_dy; round 5: the decoder's data gradient arrives in
- * bf16, as under autocast); dy row i >= 1 of batch b also receives fan_alpha * fan_bf16[b, i - 1]
- * (fan_bf16 [batches, rows_per_batch - 1, D]: the masked MSE hands its target gradient over as -dpred) and row 0 fan_cls[b]
- * (f32 [batches, D], may be NULL) — the three-way sum mh_fanout_bwd writes is formed while this launch reads its operands.
- * Needs the workspace form (D % 4 == 0, 16-byte aligned buffers, >= 64 rows, mh_layernorm_bwd_workspace_bytes). */
-int mh_layernorm_bwd_fan(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                         void* dx, float* dgamma, float* dbeta, int batches, int rows_per_batch, int D, int64_t x_bs, int64_t y_bs,
-                         int dt_dy, int accumulate_dx, float* workspace, int64_t ws_floats, const void* fan_bf16, float fan_alpha,
-                         const float* fan_cls, mh_stream s);
-/* mh_layernorm_bwd (optionally with mh_layernorm_bwd_fan's two extra gradients: fan_bf16 may be NULL) for a LayerNorm whose input x is the
- * output of `resid + Dropout_p(Linear(core))` ([3P] to_out = Sequential(Linear, Dropout) and TransLayer's residual add,
- * models/mirror.py:312): this launch's dx is that Dropout's upstream gradient, so drop_out [batches * rows, D] bf16 receives
- * mask * dx / (1 - p) on the lite Philox stream (the masks mh_gemm_epi DROPADD drew for (seed, offset + *dev_base, element)) — the operand of
- * to_out's two gradient products — and drop_db [D] += its column sums (to_out's bias gradient): mh_dropout_lite_colsum's pass over dx is
- * not launched.  f32 x / dx; dy f32 or bf16; the workspace form with >= 3 D floats per block; D % 8 == 0, D <= 1024. */
-int mh_layernorm_bwd_drop(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                          void* dx, float* dgamma, float* dbeta, int batches, int rows_per_batch, int D, int64_t x_bs, int64_t y_bs,
-                          int dt_dy, int accumulate_dx, float* workspace, int64_t ws_floats, const void* fan_bf16, float fan_alpha,
-                          const float* fan_cls, void* drop_out, float drop_p, uint64_t drop_seed, uint64_t drop_offset,
-                          const uint64_t* drop_base, float* drop_db, int drop_rows_per_batch, mh_stream s);
-                          /* drop_rows_per_batch >= rows_per_batch: rows per batch of the Dropout's tensor [batches, ., D] (drop_out has its
-                             shape); a norm over the first rows of a square-padded sequence leaves the rows behind them to the caller (zeros) */
-int mh_layernorm_bwd_lm(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                        void* dx, float* dgamma, float* dbeta, int batches, int rows_per_batch, int D, int64_t x_bs, int64_t y_bs,
-                        int dt_x, int dt_dy, int dt_dx, int accumulate_dx, float* workspace, int64_t ws_floats,
-                        const void* gadd, int pad, int l, void* relu_out, int relu_first, int relu_rows, float* relu_db,
-                        const float* row_mask, const float* lm_scale, mh_stream s);
-                        /* relu_out (nullable, bf16 [batches, relu_rows, D]; f32 x): x rows [relu_first, relu_first + relu_rows) of every batch
-                           are the output of a ReLU (`_fc1 = Linear + ReLU`, models/mirror.py:346, :652-654, feeds layer 1's norm): their
-                           total gradient is written HERE as bf16 (x > 0 ? dx : 0), the operand of _fc1's weight gradient, and NOT as f32 dx
-                           (no separate ReLU-backward pass); the other rows (cls) keep their f32 dx.
-                           relu_db (nullable, f32 [D], needs relu_out and a workspace of >= 3 D floats): += the column sums of relu_out as
-                           stored, i.e. _fc1's bias gradient, as a third partial row beside dgamma / dbeta (no mh_colsum pass over relu_out) */
 
 /* ---------------------------------------------------------------- fp8 forward projections (BASELINE config 5)
  * mh_quant_fp8: q[i] = e4m3(x[i] * 448 / max|x|) for a whole tensor (x f32 / bf16, n % 4 == 0), scale[0] = max|x| / 448

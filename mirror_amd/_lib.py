@@ -106,6 +106,22 @@ class RnaBlockDesc(C.Structure):
             "scratch")])
 
 
+class LnBwdDesc(C.Structure):
+    """mh_ln_bwd of include/mirror_hip.h (field order = the header's)."""
+    _fields_ = [
+        ("dy", C.c_void_p), ("x", C.c_void_p), ("gamma", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p),
+        ("dx", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p),
+        ("batches", C.c_int32), ("rows_per_batch", C.c_int32), ("D", C.c_int32), ("x_bs", C.c_int64), ("y_bs", C.c_int64),
+        ("dt_x", C.c_int32), ("dt_dy", C.c_int32), ("dt_dx", C.c_int32), ("accumulate_dx", C.c_int32),
+        ("workspace", C.c_void_p), ("ws_floats", C.c_int64),
+        ("gadd", C.c_void_p), ("pad", C.c_int32), ("l", C.c_int32), ("row_mask", C.c_void_p), ("lm_scale", C.c_void_p),
+        ("relu_out", C.c_void_p), ("relu_first", C.c_int32), ("relu_rows", C.c_int32), ("relu_db", C.c_void_p),
+        ("fan_bf16", C.c_void_p), ("fan_alpha", C.c_float), ("fan_cls", C.c_void_p),
+        ("drop_out", C.c_void_p), ("drop_p", C.c_float), ("drop_seed", C.c_uint64), ("drop_offset", C.c_uint64),
+        ("drop_base", C.c_void_p), ("drop_db", C.c_void_p), ("drop_rows_per_batch", C.c_int32),
+    ]
+
+
 # name -> argtypes (the trailing stream argument is appended automatically)
 _SIGS = {
     "mh_gemm": [C.POINTER(GemmDesc)],
@@ -117,10 +133,7 @@ _SIGS = {
     "mh_layernorm_fwd": [P, P, P, P, P, P, I, I, I, L, L, F, I, I],
     "mh_layernorm_fwd_dual": [P, P, P, P, P, P, P, I, I, I, L, L, F],
     "mh_layernorm_fwd_q8": [P, P, P, P, P, P, I, I, I, L, L, F, P, P, P, F, P],
-    "mh_layernorm_bwd": [P, P, P, P, P, P, P, P, I, I, I, L, L, I, I, I, I, P, L],
-    "mh_layernorm_bwd_fan": [P, P, P, P, P, P, P, P, I, I, I, L, L, I, I, P, L, P, F, P],
-    "mh_layernorm_bwd_drop": [P, P, P, P, P, P, P, P, I, I, I, L, L, I, I, P, L, P, F, P, P, F, U64, U64, P, P, I],
-    "mh_layernorm_bwd_lm": [P, P, P, P, P, P, P, P, I, I, I, L, L, I, I, I, I, P, L, P, I, I, P, I, I, P, P, P],
+    "mh_layernorm_bwd": [C.POINTER(LnBwdDesc)],
     "mh_layernorm_fwd_lm": [P, P, P, P, P, P, P, P, I, I, I, L, I, I, F, P, P],
     "mh_softmax_fwd": [P, P, L, I, L, L, I, I],
     "mh_softmax_bwd": [P, P, P, L, I, L, L, L, I, I, I],
@@ -249,7 +262,7 @@ _lib = None
 # The ABI generation this binding was written against (mh_version() of csrc/errors.cpp).  _SIGS above restates the argument lists of
 # include/mirror_hip.h by hand: a library built from another generation would be called with shifted arguments (a stream where a
 # counter belongs) and corrupt device memory silently, so load() refuses anything but this exact number.
-ABI_VERSION = 122
+ABI_VERSION = 123
 
 
 class MirrorHipError(RuntimeError):

@@ -791,146 +791,93 @@ extern "C" int64_t mh_layernorm_bwd_workspace_bytes(int64_t rows, int D) {
                                          // instance ran 631 blocks instead of 911 (62 % of the chip's slots: 119 us instead of ~100)
 }
 
-static int ln_bwd_impl(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                       void* dx, float* dgamma, float* dbeta, int batches, int rpb, int D, int64_t x_bs,
-                       int64_t y_bs, int dt_x, int dt_dy, int dt_dx, int acc_dx, float* workspace, int64_t ws_floats,
-                       const void* gadd, int ga_pad, int ga_l, mh_stream s, void* relu_out = nullptr, int relu_first = 0, int relu_rows = 0,
-                       float* relu_db = nullptr, const void* fan = nullptr, float fan_alpha = 0.f, const float* fan_cls = nullptr,
-                       void* drop_out = nullptr, float drop_p = 0.f, uint64_t drop_seed = 0, uint64_t drop_offset = 0,
-                       const uint64_t* drop_base = nullptr, float* drop_db = nullptr, int drop_rpb = 0, const float* rmask = nullptr, const float* lm_scale = nullptr);
-
-extern "C" int mh_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                                void* dx, float* dgamma, float* dbeta, int batches, int rpb, int D, int64_t x_bs,
-                                int64_t y_bs, int dt_x, int dt_dy, int dt_dx, int acc_dx, float* workspace, int64_t ws_floats,
-                                mh_stream s) {
-    return ln_bwd_impl(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, batches, rpb, D, x_bs, y_bs, dt_x, dt_dy, dt_dx, acc_dx, workspace,
-                       ws_floats, nullptr, 0, 1, s);
-}
-
-// the backward of mh_layernorm_fwd_lm: dy of row i of batch b is dy[b, i] + gadd[b, (i + pad) / l] / l, gadd [batches, (pad + rpb) / l, D]
-// in dy's dtype = the gradient of the landmark means (needs the workspace form: D % 4 == 0, aligned buffers, a workspace)
-extern "C" int mh_layernorm_bwd_lm(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                                   void* dx, float* dgamma, float* dbeta, int batches, int rpb, int D, int64_t x_bs,
-                                   int64_t y_bs, int dt_x, int dt_dy, int dt_dx, int acc_dx, float* workspace, int64_t ws_floats,
-                                   const void* gadd, int pad, int l, void* relu_out, int relu_first, int relu_rows, float* relu_db,
-                                   const float* row_mask, const float* lm_scale, mh_stream s) {
-    MH_REQUIRE(gadd && l >= 1 && pad >= 0 && (pad + rpb) % l == 0 && ((uintptr_t)gadd & 15) == 0, "mh_layernorm_bwd_lm: gadd, l >= 1, (pad + rows) %% l == 0");
-    MH_REQUIRE(!relu_out || (dt_x == MH_F32 && relu_first >= 0 && relu_rows >= 0 && relu_first + relu_rows <= rpb && ((uintptr_t)relu_out & 7) == 0 && D % 4 == 0),
-               "mh_layernorm_bwd_lm: relu_out needs f32 x and a row range inside the batch");
-    MH_REQUIRE(!relu_db || (relu_out && ((uintptr_t)workspace & 15) == 0 && ws_floats >= 3L * D), "mh_layernorm_bwd_lm: relu_db rides on relu_out (workspace of >= 3 D floats)");
-    return ln_bwd_impl(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, batches, rpb, D, x_bs, y_bs, dt_x, dt_dy, dt_dx, acc_dx, workspace,
-                       ws_floats, gadd, pad, l, s, relu_out, relu_first, relu_rows, relu_db, nullptr, 0.f, nullptr, nullptr, 0.f, 0, 0, nullptr, nullptr, 0,
-                       row_mask, lm_scale);
-}
-
-// mh_layernorm_bwd whose dy rows also receive the other two gradients of a fanned-out LayerNorm output (see FAN above): needs the
-// workspace form with f32 x and f32 dy
-extern "C" int mh_layernorm_bwd_fan(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                                    void* dx, float* dgamma, float* dbeta, int batches, int rpb, int D, int64_t x_bs,
-                                    int64_t y_bs, int dt_dy, int accumulate_dx, float* workspace, int64_t ws_floats,
-                                    const void* fan_bf16, float fan_alpha, const float* fan_cls, mh_stream s) {
-    MH_REQUIRE(fan_bf16 && rpb >= 2 && ((uintptr_t)fan_bf16 & 7) == 0 && (!fan_cls || ((uintptr_t)fan_cls & 15) == 0) && D % 4 == 0,
-               "mh_layernorm_bwd_fan: fan [batches, rows - 1, D] bf16 on quads, rows >= 2");
-    return ln_bwd_impl(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, batches, rpb, D, x_bs, y_bs, MH_F32, dt_dy, MH_F32, accumulate_dx, workspace,
-                       ws_floats, nullptr, 0, 1, s, nullptr, 0, 0, nullptr, fan_bf16, fan_alpha, fan_cls);
-}
-
-// mh_layernorm_bwd (optionally with mh_layernorm_bwd_fan's two extra gradients) for a LayerNorm whose input x is the output of
-// `resid + Dropout_p(Linear(core))`: drop_out [batches * rows, D] bf16 = dropout backward of this launch's dx on the lite stream,
-// drop_db [D] += its column sums.  f32 x / dx, dy f32 or bf16 (f32 with fan), the workspace form
-extern "C" int mh_layernorm_bwd_drop(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                                     void* dx, float* dgamma, float* dbeta, int batches, int rpb, int D, int64_t x_bs,
-                                     int64_t y_bs, int dt_dy, int accumulate_dx, float* workspace, int64_t ws_floats,
-                                     const void* fan_bf16, float fan_alpha, const float* fan_cls,
-                                     void* drop_out, float drop_p, uint64_t drop_seed, uint64_t drop_offset, const uint64_t* drop_base,
-                                     float* drop_db, int drop_rows_per_batch, mh_stream s) {
-    MH_REQUIRE(drop_rows_per_batch >= rpb, "mh_layernorm_bwd_drop: the Dropout's tensor has %d rows per batch, the norm reads %d", drop_rows_per_batch, rpb);
-    MH_REQUIRE(drop_out && drop_db && drop_p >= 0.f && drop_p < 1.f && (drop_offset & 7) == 0 && ((uintptr_t)drop_out & 7) == 0 && D % 8 == 0 &&
-                   ((uintptr_t)workspace & 15) == 0 && ws_floats >= 3L * D,
-               "mh_layernorm_bwd_drop: drop_out / drop_db, p in [0, 1), offset %% 8 == 0, D %% 8 == 0, a workspace of >= 3 D floats");
-    MH_REQUIRE(!fan_bf16 || (rpb >= 2 && ((uintptr_t)fan_bf16 & 7) == 0 && (!fan_cls || ((uintptr_t)fan_cls & 15) == 0)),
-               "mh_layernorm_bwd_drop: fan [batches, rows - 1, D] bf16 on quads");
-    return ln_bwd_impl(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, batches, rpb, D, x_bs, y_bs, MH_F32, dt_dy, MH_F32, accumulate_dx, workspace,
-                       ws_floats, nullptr, 0, 1, s, nullptr, 0, 0, nullptr, fan_bf16, fan_alpha, fan_cls, drop_out, drop_p, drop_seed, drop_offset,
-                       drop_base, drop_db, drop_rows_per_batch);
-}
-
-static int ln_bwd_impl(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                       void* dx, float* dgamma, float* dbeta, int batches, int rpb, int D, int64_t x_bs,
-                       int64_t y_bs, int dt_x, int dt_dy, int dt_dx, int acc_dx, float* workspace, int64_t ws_floats,
-                       const void* gadd, int ga_pad, int ga_l, mh_stream s, void* relu_out, int relu_first, int relu_rows, float* relu_db,
-                       const void* fan, float fan_alpha, const float* fan_cls, void* drop_out, float drop_p, uint64_t drop_seed,
-                       uint64_t drop_offset, const uint64_t* drop_base, float* drop_db, int drop_rpb, const float* rmask, const float* lm_scale) {
+// One implementation behind mh_layernorm_bwd: the descriptor's base block plus the riders whose lead pointer is set (mirror_hip.h)
+static int ln_bwd_impl(const mh_ln_bwd& d, mh_stream s) {
+    const int D = d.D, rpb = d.rows_per_batch, dt_x = d.dt_x, dt_dy = d.dt_dy;
+    const int l = d.gadd ? d.l : 1;                 // an all-zero landmark block is absent, and the launches divide by l
+    const long rows = (long)d.batches * rpb;
+    const bool vecok = D % 4 == 0 && d.x_bs % 4 == 0 && d.y_bs % 4 == 0 && ((uintptr_t)d.x & 15) == 0 && ((uintptr_t)d.dy & 15) == 0 &&
+                       ((uintptr_t)d.dx & 15) == 0 && ((uintptr_t)d.gamma & 15) == 0;
+    // workspace form: per-block partial rows in the workspace, folded by a second launch (the only form that carries riders)
+    const bool ws_form = vecok && d.workspace && d.ws_floats >= 2L * D && rows >= 64;
+    const bool f32_x = dt_x == MH_F32 && d.dt_dx == MH_F32;
+    const bool ws3 = ((uintptr_t)d.workspace & 15) == 0 && d.ws_floats >= 3L * D;
+    const bool fan_ok = rpb >= 2 && ((uintptr_t)d.fan_bf16 & 7) == 0 && (!d.fan_cls || ((uintptr_t)d.fan_cls & 15) == 0) && D % 4 == 0;
+    // every check runs before the first launch: a refused call has touched nothing
     MH_REQUIRE(D >= 1 && D <= 64 * LN_MAXPL, "mh_layernorm_bwd: D=%d unsupported", D);
-    MH_REQUIRE(dt_dx == dt_x, "mh_layernorm_bwd: dx dtype must equal x dtype");
-    const long rows = (long)batches * rpb;
-    if (rows == 0) return MH_OK;
+    MH_REQUIRE(d.dt_dx == dt_x, "mh_layernorm_bwd: dx dtype must equal x dtype");
     MH_REQUIRE(rows < (1L << 31), "mh_layernorm_bwd: too many rows");
+    MH_REQUIRE(!d.gadd || (l >= 1 && d.pad >= 0 && (d.pad + rpb) % l == 0 && ((uintptr_t)d.gadd & 15) == 0),
+               "mh_layernorm_bwd: landmark rider: l >= 1, pad >= 0, (pad + rows) %% l == 0, gadd on 16 bytes");
+    MH_REQUIRE(d.gadd || (!d.relu_out && !d.row_mask && !d.lm_scale), "mh_layernorm_bwd: landmark rider: relu_out, row_mask and lm_scale need gadd");
+    MH_REQUIRE(!d.gadd || (!d.fan_bf16 && !d.drop_out), "mh_layernorm_bwd: landmark rider: gadd excludes fan_bf16 and drop_out");
+    MH_REQUIRE(!d.relu_out || (dt_x == MH_F32 && dt_dy == MH_BF16 && d.relu_first >= 0 && d.relu_rows >= 0 && d.relu_first + d.relu_rows <= rpb &&
+                               ((uintptr_t)d.relu_out & 7) == 0 && D % 4 == 0),
+               "mh_layernorm_bwd: ReLU rider: relu_out needs f32 x, bf16 dy and a row range inside the batch");
+    MH_REQUIRE(!d.relu_db || (d.relu_out && ws3), "mh_layernorm_bwd: ReLU rider: relu_db rides on relu_out (workspace of >= 3 D floats)");
+    MH_REQUIRE(!d.fan_bf16 || (f32_x && fan_ok), "mh_layernorm_bwd: fan rider: f32 x / dx, fan [batches, rows - 1, D] bf16 on quads, rows >= 2");
+    MH_REQUIRE(!d.drop_out || d.drop_rows_per_batch >= rpb, "mh_layernorm_bwd: drop rider: the Dropout's tensor has %d rows per batch, the norm reads %d",
+               d.drop_rows_per_batch, rpb);
+    MH_REQUIRE(!d.drop_out || (f32_x && d.drop_db && d.drop_p >= 0.f && d.drop_p < 1.f && (d.drop_offset & 7) == 0 && ((uintptr_t)d.drop_out & 7) == 0 &&
+                               D % 8 == 0 && D <= 1024 && ws3),
+               "mh_layernorm_bwd: drop rider: f32 x / dx, drop_out / drop_db, p in [0, 1), offset %% 8 == 0, D %% 8 == 0, D <= 1024, a workspace of >= 3 D floats");
+    MH_REQUIRE(rows == 0 || ws_form || !(d.gadd || d.fan_bf16 || d.drop_out),
+               "mh_layernorm_bwd: the %s rider needs the workspace form (D %% 4 == 0, 16-byte aligned buffers, a workspace of >= %d D floats, >= 64 rows)",
+               d.gadd ? "landmark" : (d.drop_out ? "drop" : "fan"), d.drop_out ? 3 : 2);
+    if (rows == 0) return MH_OK;
     dim3 grid((unsigned)min((long)mh_cdiv(rows, 4), (long)ln_bwd_blocks()));
-    const bool vecok = D % 4 == 0 && x_bs % 4 == 0 && y_bs % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0 &&
-                       ((uintptr_t)dx & 15) == 0 && ((uintptr_t)gamma & 15) == 0;
-#define LN_BV1(TX, TDY, NC) hipLaunchKernelGGL((layernorm_bwd_vec_kernel<TX, TDY, NC>), grid, dim3(256), 0, (hipStream_t)s, (const TDY*)dy, (const TX*)x, gamma, mean, rstd, (TX*)dx, dgamma, dbeta, rows, rpb, D, (long)x_bs, (long)y_bs, acc_dx)
-#define LN_BV(TX, TDY) do { if (D <= 512) LN_BV1(TX, TDY, 2); else if (D <= 1024) LN_BV1(TX, TDY, 4); else LN_BV1(TX, TDY, 8); } while (0)
-    // workspace form: rows_per_block rows per block (a multiple of 8: two rows per wave per iteration), nb <= ws capacity
-    if (vecok && workspace && ws_floats >= 2L * D && rows >= 64) {
-        const int segs = (relu_db || drop_out) ? 3 : 2;       // partial rows per block: dgamma, dbeta (, a bias gradient's column sums)
-        if (drop_out) relu_db = drop_db;                      // the fold's third destination
-        const int relu_cs = relu_db ? 1 : 0;
-        const long cap = ws_floats / ((long)segs * D);
+    if (ws_form) {          // rows_per_block rows per block (a multiple of 8: two rows per wave per iteration), nb <= ws capacity
+        float* third = d.drop_out ? d.drop_db : d.relu_db;      // the fold's third destination: a bias gradient's column sums
+        const int segs = third ? 3 : 2;                         // partial rows per block: dgamma, dbeta (, third)
+        const long cap = d.ws_floats / ((long)segs * D);
         long nb = min(cap, min((long)mh_cdiv(rows, 16), 1024L));
         const int rows_per_block = (int)(mh_cdiv(mh_cdiv(rows, nb), 8) * 8);
         nb = mh_cdiv(rows, rows_per_block);
         dim3 g2((unsigned)nb);
-#define LN_BW1(TX, TDY, NC, RL) hipLaunchKernelGGL((layernorm_bwd_ws_kernel<TX, TDY, NC, RL>), g2, dim3(256), 0, (hipStream_t)s, (const TDY*)dy, (const TX*)x, gamma, mean, rstd, (TX*)dx, workspace, (int)rows, rpb, D, (long)x_bs, (long)y_bs, acc_dx, rows_per_block, (const TDY*)gadd, ga_pad, ga_l, (ga_pad + rpb) / ga_l, 1.f / (float)ga_l, (bf16_t*)relu_out, relu_first, relu_rows, relu_cs, (const bf16_t*)nullptr, 0.f, (const float*)nullptr, (bf16_t*)nullptr, 0.f, (uint64_t)0, (uint64_t)0, (const uint64_t*)nullptr, 0, rmask, lm_scale)
-#define LN_BW(TX, TDY) do { if (D <= 512) LN_BW1(TX, TDY, 2, false); else if (D <= 1024) LN_BW1(TX, TDY, 4, false); else LN_BW1(TX, TDY, 8, false); } while (0)
-#define LN_BWF_(TDY, NC) hipLaunchKernelGGL((layernorm_bwd_ws_kernel<float, TDY, NC, false, true>), g2, dim3(256), 0, (hipStream_t)s, (const TDY*)dy, (const float*)x, gamma, mean, rstd, (float*)dx, workspace, (int)rows, rpb, D, (long)x_bs, (long)y_bs, acc_dx, rows_per_block, (const TDY*)nullptr, 0, 1, 0, 0.f, (bf16_t*)nullptr, 0, 0, 0, (const bf16_t*)fan, fan_alpha, fan_cls)
-#define LN_BWF(NC) do { if (dt_dy == MH_F32) LN_BWF_(float, NC); else LN_BWF_(bf16_t, NC); } while (0)
-#define LN_BWD_(TDY, NC, FN) hipLaunchKernelGGL((layernorm_bwd_ws_kernel<float, TDY, NC, false, FN, true>), g2, dim3(256), 0, (hipStream_t)s, (const TDY*)dy, (const float*)x, gamma, mean, rstd, (float*)dx, workspace, (int)rows, rpb, D, (long)x_bs, (long)y_bs, acc_dx, rows_per_block, (const TDY*)nullptr, 0, 1, 0, 0.f, (bf16_t*)nullptr, 0, 0, 0, (const bf16_t*)fan, fan_alpha, fan_cls, (bf16_t*)drop_out, drop_p, drop_seed, drop_offset, drop_base, drop_rpb)
-        if (drop_out) {         // to_out's Dropout backward + bias gradient inside this launch: instances of their own (f32 x)
-            MH_REQUIRE(dt_x == MH_F32 && D <= 1024, "mh_layernorm_bwd_drop: f32 x, D <= 1024");
-            if (fan && dt_dy == MH_F32) { if (D <= 512) LN_BWD_(float, 2, true); else LN_BWD_(float, 4, true); }
-            else if (fan) { if (D <= 512) LN_BWD_(bf16_t, 2, true); else LN_BWD_(bf16_t, 4, true); }
-            else if (dt_dy == MH_F32) { if (D <= 512) LN_BWD_(float, 2, false); else LN_BWD_(float, 4, false); }
-            else { if (D <= 512) LN_BWD_(bf16_t, 2, false); else LN_BWD_(bf16_t, 4, false); }
-        } else
-        if (fan) {              // the fanned-out form (f32 x, f32 dy) is an instance of its own too
+        // every instance takes the whole argument list; what an absent rider leaves behind is NULL / 0 and its code is compiled out or skipped.
+        // The instances are named in a fixed order below: the code object lays them out in the order of first use
+#define LN_WS(TX, TDY, NC, RL, FN, DR) hipLaunchKernelGGL((layernorm_bwd_ws_kernel<TX, TDY, NC, RL, FN, DR>), g2, dim3(256), 0, (hipStream_t)s, (const TDY*)d.dy, (const TX*)d.x, d.gamma, d.mean, d.rstd, (TX*)d.dx, d.workspace, (int)rows, rpb, D, (long)d.x_bs, (long)d.y_bs, d.accumulate_dx, rows_per_block, (const TDY*)d.gadd, d.pad, l, (d.pad + rpb) / l, 1.f / (float)l, (bf16_t*)d.relu_out, d.relu_first, d.relu_rows, d.relu_db ? 1 : 0, (const bf16_t*)d.fan_bf16, d.fan_alpha, d.fan_cls, (bf16_t*)d.drop_out, d.drop_p, d.drop_seed, d.drop_offset, d.drop_base, d.drop_rows_per_batch, d.row_mask, d.lm_scale)
+#define LN_BW(TX, TDY, RL) do { if (D <= 512) LN_WS(TX, TDY, 2, RL, false, false); else if (D <= 1024) LN_WS(TX, TDY, 4, RL, false, false); else LN_WS(TX, TDY, 8, RL, false, false); } while (0)
+#define LN_BWF(NC) do { if (dt_dy == MH_F32) LN_WS(float, float, NC, false, true, false); else LN_WS(float, bf16_t, NC, false, true, false); } while (0)
+#define LN_BWD(TDY, FN) do { if (D <= 512) LN_WS(float, TDY, 2, false, FN, true); else LN_WS(float, TDY, 4, false, FN, true); } while (0)
+        if (d.drop_out) {           // to_out's Dropout backward + bias gradient inside this launch: instances of their own (f32 x)
+            if (d.fan_bf16 && dt_dy == MH_F32) LN_BWD(float, true);
+            else if (d.fan_bf16) LN_BWD(bf16_t, true);
+            else if (dt_dy == MH_F32) LN_BWD(float, false);
+            else LN_BWD(bf16_t, false);
+        } else if (d.fan_bf16) {    // the fanned-out form (f32 x) is an instance of its own too
             if (D <= 512) LN_BWF(2); else if (D <= 1024) LN_BWF(4); else LN_BWF(8);
-        } else
-        if (relu_out) {         // the ReLU-fused form (f32 x, bf16 dy: layer 1 of the bf16 policy) is an instance of its own
-            MH_REQUIRE(dt_x == MH_F32 && dt_dy == MH_BF16, "mh_layernorm_bwd_lm: relu_out needs f32 x and bf16 dy");
-            if (D <= 512) LN_BW1(float, bf16_t, 2, true); else if (D <= 1024) LN_BW1(float, bf16_t, 4, true); else LN_BW1(float, bf16_t, 8, true);
-        } else if (dt_x == MH_F32 && dt_dy == MH_F32) LN_BW(float, float);
-        else if (dt_x == MH_F32 && dt_dy == MH_BF16) LN_BW(float, bf16_t);
-        else if (dt_x == MH_BF16 && dt_dy == MH_BF16) LN_BW(bf16_t, bf16_t);
-        else LN_BW(bf16_t, float);
-#undef LN_BWD_
+        } else if (d.relu_out) LN_BW(float, bf16_t, true);       // the ReLU-fused form (f32 x, bf16 dy: layer 1 of the bf16 policy)
+        else if (dt_x == MH_F32 && dt_dy == MH_F32) LN_BW(float, float, false);
+        else if (dt_x == MH_F32 && dt_dy == MH_BF16) LN_BW(float, bf16_t, false);
+        else if (dt_x == MH_BF16 && dt_dy == MH_BF16) LN_BW(bf16_t, bf16_t, false);
+        else LN_BW(bf16_t, float, false);
+#undef LN_BWD
 #undef LN_BWF
-#undef LN_BWF_
 #undef LN_BW
-#undef LN_BW1
-        if (D % 4 == 0 && ((uintptr_t)workspace & 15) == 0)
+#undef LN_WS
+        if (D % 4 == 0 && ((uintptr_t)d.workspace & 15) == 0)
             hipLaunchKernelGGL(layernorm_bwd_fold4_kernel, dim3(mh_cdiv(segs * D / 4, 64), (unsigned)min(mh_cdiv(nb, 32), 16)), dim3(256), 0,
-                               (hipStream_t)s, (const float*)workspace, (int)nb, D, dgamma, dbeta, segs, relu_db);
+                               (hipStream_t)s, (const float*)d.workspace, (int)nb, D, d.dgamma, d.dbeta, segs, third);
         else
             hipLaunchKernelGGL(layernorm_bwd_fold_kernel, dim3(mh_cdiv(2 * D, 256), (unsigned)min(nb, 32L)), dim3(256), 0, (hipStream_t)s,
-                               (const float*)workspace, (int)nb, D, dgamma, dbeta);
+                               (const float*)d.workspace, (int)nb, D, d.dgamma, d.dbeta);
         MH_LAUNCH_CHECK("mh_layernorm_bwd");
         return MH_OK;
     }
-    MH_REQUIRE(!drop_out, "mh_layernorm_bwd_drop: needs the workspace form (D %% 4 == 0, 16-byte aligned buffers, a workspace of >= 3 D floats, >= 64 rows)");
-    MH_REQUIRE(!fan, "mh_layernorm_bwd_fan: needs the workspace form (D %% 4 == 0, 16-byte aligned buffers, a workspace of >= 2 D floats, >= 64 rows)");
-    MH_REQUIRE(!gadd && !relu_out, "mh_layernorm_bwd_lm: needs the workspace form (D %% 4 == 0, 16-byte aligned buffers, a workspace of >= 2 D floats, >= 64 rows)");
     if (vecok) {
+#define LN_BV1(TX, TDY, NC) hipLaunchKernelGGL((layernorm_bwd_vec_kernel<TX, TDY, NC>), grid, dim3(256), 0, (hipStream_t)s, (const TDY*)d.dy, (const TX*)d.x, d.gamma, d.mean, d.rstd, (TX*)d.dx, d.dgamma, d.dbeta, rows, rpb, D, (long)d.x_bs, (long)d.y_bs, d.accumulate_dx)
+#define LN_BV(TX, TDY) do { if (D <= 512) LN_BV1(TX, TDY, 2); else if (D <= 1024) LN_BV1(TX, TDY, 4); else LN_BV1(TX, TDY, 8); } while (0)
         if (dt_x == MH_F32 && dt_dy == MH_F32) LN_BV(float, float);
         else if (dt_x == MH_F32 && dt_dy == MH_BF16) LN_BV(float, bf16_t);
         else if (dt_x == MH_BF16 && dt_dy == MH_BF16) LN_BV(bf16_t, bf16_t);
         else LN_BV(bf16_t, float);
+#undef LN_BV
+#undef LN_BV1
         MH_LAUNCH_CHECK("mh_layernorm_bwd");
         return MH_OK;
     }
-#undef LN_BV
-#undef LN_BV1
-#define LN_B(TX, TDY) hipLaunchKernelGGL((layernorm_bwd_kernel<TX, TDY, TX>), grid, dim3(256), 0, (hipStream_t)s, (const TDY*)dy, (const TX*)x, gamma, mean, rstd, (TX*)dx, dgamma, dbeta, rows, rpb, D, (long)x_bs, (long)y_bs, acc_dx)
+#define LN_B(TX, TDY) hipLaunchKernelGGL((layernorm_bwd_kernel<TX, TDY, TX>), grid, dim3(256), 0, (hipStream_t)s, (const TDY*)d.dy, (const TX*)d.x, d.gamma, d.mean, d.rstd, (TX*)d.dx, d.dgamma, d.dbeta, rows, rpb, D, (long)d.x_bs, (long)d.y_bs, d.accumulate_dx)
     if (dt_x == MH_F32 && dt_dy == MH_F32) LN_B(float, float);
     else if (dt_x == MH_F32 && dt_dy == MH_BF16) LN_B(float, bf16_t);
     else if (dt_x == MH_BF16 && dt_dy == MH_BF16) LN_B(bf16_t, bf16_t);
@@ -938,6 +885,11 @@ static int ln_bwd_impl(const void* dy, const void* x, const float* gamma, const 
 #undef LN_B
     MH_LAUNCH_CHECK("mh_layernorm_bwd");
     return MH_OK;
+}
+
+extern "C" int mh_layernorm_bwd(const mh_ln_bwd* d, mh_stream s) {
+    MH_REQUIRE(d, "mh_layernorm_bwd: NULL descriptor");
+    return ln_bwd_impl(*d, s);
 }
 
 // ------------------------------------------------------------------------------ softmax

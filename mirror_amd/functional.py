@@ -934,7 +934,7 @@ class ToOutDropAddFn(Function):
         # None when dy is not the LayerNorm's dx alone (another consumer's gradient was summed in, a hook touched it): the plain pass below
         handed = None if ctx.site is None else ctx.site.claim(dy)
         if handed is not None:
-            # the LayerNorm backward that produced dy already wrote the masked bf16 gradient and its column sums (mh_layernorm_bwd_drop)
+            # the LayerNorm backward that produced dy already wrote the masked bf16 gradient and its column sums (mh_layernorm_bwd's drop rider)
             gb, cs = handed
             if want_db:
                 dbuf, sunk = _gbuf(b, (dy.shape[-1],))
@@ -1229,7 +1229,7 @@ class LayerNormFn(Function):
         db, sunk_b = _gbuf(beta, (D,))
         # this norm's output fans out (EncFanoutFn): the retention target's and the cls row's gradients were left in the slot instead of
         # being summed into a [B, T, D] tensor — they are additive to whatever arrives here as dy, and the launch below adds them as it
-        # reads dy (mh_layernorm_bwd_fan), or mh_fanout_bwd materialises the sum when the shapes are off that form
+        # reads dy (mh_layernorm_bwd's fan rider), or mh_fanout_bwd materialises the sum when the shapes are off that form
         fan = None
         if ctx.fan_slot is not None and ctx.fan_slot.extra is not None:
             fan, ctx.fan_slot.extra = ctx.fan_slot.extra, None
@@ -1278,7 +1278,7 @@ class NormQkvLmFn(Function):
     sequence, so the operand of to_qkv is one [B n_p + B m, D] buffer and the landmarks come out as the last B m rows of its
     [B n_p + B m, 3D] result — no projection launch of their own, no pass over the q | k columns.  The backward is symmetric:
     NystromCoreFn returns d qkv and d lm as the two row ranges of ONE gradient buffer ([dq_l | dk_l | 0] rows), so the data gradient
-    (whose last rows are d xpm, added to the rows' gradient by mh_layernorm_bwd_lm) and the weight gradient (one contraction over
+    (whose last rows are d xpm, added to the rows' gradient by mh_layernorm_bwd's landmark rider) and the weight gradient (one contraction over
     all B n_p + B m rows) need no landmark launches either.  Returns (qkv [B, n_p, 3D], lm [B, m, 2D] with row stride 3D).
     The v columns of the sequence rows are a deferred launch (link.v_cols, under the pinv chain); the pad rows are skipped
     by the flat row-window kernels (K.gemm_rows_ext) when the geometry allows, else every physical row is multiplied."""

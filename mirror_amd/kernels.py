@@ -605,64 +605,61 @@ def layernorm_fwd_q8(x, gamma, beta, y, mean, rstd, batches, rpb, D, x_bs, y_bs,
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, batches, rpb, D, x_bs, y_bs, accumulate_dx=False, gadd=None,
                   pad: int = 0, l: int = 1, relu_out=None, relu_first: int = 0, relu_db=None, fan=None, drop=None, row_mask=None, lm_scale=None):
-    """gadd ([batches, (pad + rpb) / l, D], dy's dtype): the gradient of the landmark means layernorm_fwd_lm produced; every dy row also
-    receives gadd[b, (i + pad) / l] / l (mh_layernorm_bwd_lm).  relu_out (bf16 [batches, R, D], with gadd only): rows [relu_first,
+    """mh_layernorm_bwd: one descriptor (mh_ln_bwd) carrying every rider given here; the library refuses the combinations it has no
+    kernel for (the landmark riders beside fan or drop) before it launches anything.
+    gadd ([batches, (pad + rpb) / l, D], dy's dtype): the gradient of the landmark means layernorm_fwd_lm produced; every dy row also
+    receives gadd[b, (i + pad) / l] / l.  relu_out (bf16 [batches, R, D], with gadd only): rows [relu_first,
     relu_first + R) of x are a ReLU's output — their gradient leaves as bf16 (x > 0 ? dx : 0) in relu_out instead of f32 dx;
     relu_db (f32 [D], with relu_out): += the column sums of relu_out (the bias gradient of the Linear in front of the ReLU).
     fan = (src bf16 [batches, rpb - 1, D], alpha, cls f32 [batches, D] or None), without gadd: dy rows 1.. also receive alpha * src, row 0
-    cls (mh_layernorm_bwd_fan; layernorm_bwd_fan_ok says whether the shapes are on that form).
+    cls (layernorm_bwd_fan_ok says whether the shapes are on that form).
     drop = (out bf16 [batches, >= rpb, D] (the Dropout's tensor; rows past rpb are the caller's), p, seed, offset, dev_base, db f32 [D]), without gadd: x is the output of resid + Dropout_p(Linear),
-    so out receives the lite-stream dropout backward of this launch's dx and db its column sums (mh_layernorm_bwd_drop)."""
-    _chk(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, relu_out, relu_db)
-    if relu_db is not None and (relu_out is None or relu_db.dtype != torch.float32 or relu_db.numel() != D or not relu_db.is_contiguous()):
-        raise MirrorHipError("layernorm_bwd: relu_db is a contiguous f32 [D] and rides on relu_out")
-    if relu_out is not None and (gadd is None or relu_out.dtype != torch.bfloat16 or not relu_out.is_contiguous() or relu_out.dim() != 3
-                                 or relu_out.shape[0] != batches or relu_out.shape[2] != D or relu_first + relu_out.shape[1] > rpb):
-        raise MirrorHipError("layernorm_bwd: relu_out must be contiguous bf16 [batches, R, D] with relu_first + R <= rows (landmark form only)")
-    rows = batches * rpb
+    so out receives the lite-stream dropout backward of this launch's dx and db its column sums (fan may ride along)."""
+    _chk(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, gadd, relu_out, relu_db, row_mask, lm_scale)
+    d = _lib.LnBwdDesc()
+    d.dy, d.x, d.gamma, d.mean, d.rstd, d.dx, d.dgamma, d.dbeta = _p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta)
+    d.batches, d.rows_per_batch, d.D, d.x_bs, d.y_bs = batches, rpb, D, x_bs, y_bs
+    d.dt_x, d.dt_dy, d.dt_dx, d.accumulate_dx = dt(x), dt(dy), dt(dx), int(accumulate_dx)
     ws = None
-    nbytes = int(_lib.load().mh_layernorm_bwd_workspace_bytes(rows, D))
+    nbytes = int(_lib.load().mh_layernorm_bwd_workspace_bytes(batches * rpb, D))
     if nbytes:          # per-block dgamma / dbeta partials (folded by a second launch) instead of same-address atomics
         ws = torch.empty((nbytes // 4,), device=x.device, dtype=torch.float32)
-    if lm_scale is not None:
-        _chk(lm_scale)
-        if gadd is None or lm_scale.dtype != torch.float32 or not lm_scale.is_contiguous() or lm_scale.numel() != batches * ((pad + rpb) // l):
-            raise MirrorHipError("layernorm_bwd: lm_scale is a contiguous f32 [batches, (pad + rows) / l] and rides on the landmark form (gadd)")
-    if row_mask is not None:
-        _chk(row_mask)
-        if gadd is None or row_mask.dtype != torch.float32 or not row_mask.is_contiguous() or row_mask.numel() != batches * (pad + rpb):
-            raise MirrorHipError("layernorm_bwd: row_mask is a contiguous f32 [batches, pad + rows] and rides on the landmark form (gadd)")
+        d.workspace, d.ws_floats = ws.data_ptr(), ws.numel()
     if gadd is not None:
-        _chk(gadd)
         if gadd.dtype != dy.dtype or not gadd.is_contiguous() or gadd.numel() != batches * ((pad + rpb) // l) * D:
             raise MirrorHipError("layernorm_bwd: gadd must be contiguous [batches, (pad + rows) / l, D] in dy's dtype")
-        _lib.call("mh_layernorm_bwd_lm", _p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta),
-                  batches, rpb, D, x_bs, y_bs, dt(x), dt(dy), dt(dx), int(accumulate_dx), _p(ws) if ws is not None else 0,
-                  ws.numel() if ws is not None else 0, _p(gadd), int(pad), int(l), _p(relu_out), int(relu_first),
-                  0 if relu_out is None else int(relu_out.shape[1]), _p(relu_db), _p(row_mask), _p(lm_scale), stream=_stream())
-        return
-    if drop is not None:
-        dout, p_, seed_, off_, base_, ddb = drop
-        src, alpha, cls = fan if fan is not None else (None, 0.0, None)
-        _chk(dout, base_, ddb, src, cls)
-        if (gadd is not None or ws is None or not layernorm_bwd_drop_ok(dy, x, dx, dout, ddb, batches, rpb, D, off_)
-                or (fan is not None and not layernorm_bwd_fan_ok(dy, x, dx, src, cls, batches, rpb, D))):
-            raise MirrorHipError("layernorm_bwd: drop needs f32 x / dx, a contiguous bf16 [batches, rows, D] output, D % 8 == 0, D <= 1024, offset % 8 == 0, >= 64 rows")
-        _lib.call("mh_layernorm_bwd_drop", _p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta),
-                  batches, rpb, D, x_bs, y_bs, dt(dy), int(accumulate_dx), _p(ws), ws.numel(), _p(src), float(alpha), _p(cls),
-                  _p(dout), float(p_), int(seed_), int(off_), _p(base_), _p(ddb), int(dout.shape[1]), stream=_stream())
-        return
+        d.gadd, d.pad, d.l = _p(gadd), int(pad), int(l)
+    if lm_scale is not None:
+        if lm_scale.dtype != torch.float32 or not lm_scale.is_contiguous() or lm_scale.numel() != batches * ((pad + rpb) // l):
+            raise MirrorHipError("layernorm_bwd: lm_scale is a contiguous f32 [batches, (pad + rows) / l]")
+        d.lm_scale = _p(lm_scale)
+    if row_mask is not None:
+        if row_mask.dtype != torch.float32 or not row_mask.is_contiguous() or row_mask.numel() != batches * (pad + rpb):
+            raise MirrorHipError("layernorm_bwd: row_mask is a contiguous f32 [batches, pad + rows]")
+        d.row_mask = _p(row_mask)
+    if relu_out is not None:
+        if (relu_out.dtype != torch.bfloat16 or not relu_out.is_contiguous() or relu_out.dim() != 3
+                or relu_out.shape[0] != batches or relu_out.shape[2] != D or relu_first + relu_out.shape[1] > rpb):
+            raise MirrorHipError("layernorm_bwd: relu_out must be contiguous bf16 [batches, R, D] with relu_first + R <= rows")
+        d.relu_out, d.relu_first, d.relu_rows = _p(relu_out), int(relu_first), int(relu_out.shape[1])
+    if relu_db is not None:
+        if relu_db.dtype != torch.float32 or relu_db.numel() != D or not relu_db.is_contiguous():
+            raise MirrorHipError("layernorm_bwd: relu_db is a contiguous f32 [D]")
+        d.relu_db = _p(relu_db)
     if fan is not None:
         src, alpha, cls = fan
         _chk(src, cls)
         if not layernorm_bwd_fan_ok(dy, x, dx, src, cls, batches, rpb, D) or ws is None:
             raise MirrorHipError("layernorm_bwd: fan needs f32 x / dx, a contiguous bf16 [batches, rows - 1, D] source and >= 64 rows")
-        _lib.call("mh_layernorm_bwd_fan", _p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta),
-                  batches, rpb, D, x_bs, y_bs, dt(dy), int(accumulate_dx), _p(ws), ws.numel(), _p(src), float(alpha), _p(cls), stream=_stream())
-        return
-    _lib.call("mh_layernorm_bwd", _p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta),
-              batches, rpb, D, x_bs, y_bs, dt(x), dt(dy), dt(dx), int(accumulate_dx), _p(ws) if ws is not None else 0,
-              ws.numel() if ws is not None else 0, stream=_stream())
+        d.fan_bf16, d.fan_alpha, d.fan_cls = _p(src), float(alpha), _p(cls)
+    if drop is not None:
+        dout, p_, seed_, off_, base_, ddb = drop
+        _chk(dout, base_, ddb)
+        if ws is None or not layernorm_bwd_drop_ok(dy, x, dx, dout, ddb, batches, rpb, D, off_):
+            raise MirrorHipError("layernorm_bwd: drop needs f32 x / dx, a contiguous bf16 [batches, rows, D] output, D % 8 == 0, D <= 1024, offset % 8 == 0, >= 64 rows")
+        d.drop_out, d.drop_p, d.drop_seed, d.drop_offset, d.drop_base, d.drop_db = _p(dout), float(p_), int(seed_), int(off_), _p(base_), _p(ddb)
+        d.drop_rows_per_batch = int(dout.shape[1])
+    _lib.call("mh_layernorm_bwd", C.byref(d), stream=_stream())
 
 
 def layernorm_bwd_drop_ok(dy, x, dx, dout, ddb, batches: int, rpb: int, D: int, offset: int) -> bool:

@@ -43,7 +43,7 @@ def test_new_entry_points_in_header_bindings_and_exports():
 
 
 def test_the_abi_generation_is_unchanged():
-    assert _lib.load().mh_version() == 122 == _lib.ABI_VERSION
+    assert _lib.load().mh_version() == 123 == _lib.ABI_VERSION
 
 
 def test_create_optimizer_v2_groups_as_timm_and_skips_frozen_parameters():

@@ -259,6 +259,6 @@ def test_metric_arguments_are_validated():
 def test_classify_entry_points_are_exported():
     from mirror_amd import _lib
     lib = _lib.load()
-    assert lib.mh_version() == _lib.ABI_VERSION == 122
+    assert lib.mh_version() == _lib.ABI_VERSION == 123
     for name in ("mh_cls_ce_fwd", "mh_cls_ce_bwd", "mh_cls_confusion", "mh_auroc_counts"):
         assert name in _lib.EXPORTS and hasattr(lib, name), name

@@ -151,7 +151,7 @@ def test_the_new_surface_refuses_cpu_tensors():
 def test_the_binding_declares_the_new_entry_points():
     from mirror_amd import _lib
     lib = _lib.load()
-    assert {"mh_sample_rows", "mh_sample_weighted"} <= set(_lib._SIGS) and _lib.ABI_VERSION == 122
+    assert {"mh_sample_rows", "mh_sample_weighted"} <= set(_lib._SIGS) and _lib.ABI_VERSION == 123
     assert hasattr(lib, "mh_sample_rows") and hasattr(lib, "mh_sample_weighted")
 
 

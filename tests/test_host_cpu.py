@@ -71,25 +71,80 @@ def test_load_refuses_a_library_of_another_abi_generation(monkeypatch):
     assert _lib.load().mh_version() == lib.mh_version()
 
 
+_SCALARS = {"int": "int32", "int32_t": "int32", "int64_t": "int64", "uint64_t": "uint64", "float": "float", "double": "double"}
+
+
 def _struct_fields(header: str, name: str):
-    """Field names of `typedef struct { ... } name;` in declaration order."""
+    """(field name, type class) of `typedef struct { ... } name;` in declaration order.  Type classes: "pointer", "int32", "int64",
+    "uint64", "float", "double", and (class, n) for a fixed-size array of n."""
     end = header.index("} %s;" % name)
     body = header[header.rindex("typedef struct {", 0, end):end]
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
+    fields = []
     for decl in body.split(";"):
-        decl = decl.replace("typedef struct {", "").strip()
+        decl = " ".join(decl.replace("typedef struct {", "").split())
         if not decl:
             continue
-        decl = re.sub(r"^(const\s+)?[A-Za-z_][A-Za-z0-9_]*\s*\*?\s*", "", decl)          # the declaration's type
-        names += [n.strip().lstrip("*").strip() for n in decl.split(",")]
-    return names
+        base, rest = re.match(r"(?:const )?([A-Za-z_][A-Za-z0-9_]*)\s*(.*)$", decl).groups()        # the declaration's type, its declarators
+        for item in rest.split(","):
+            item = item.strip()
+            cls = "pointer" if item.startswith("*") else _SCALARS[base]
+            arr = re.match(r"([A-Za-z_][A-Za-z0-9_]*)\[(\d+)\]$", item)
+            fields.append((arr.group(1), (cls, int(arr.group(2)))) if arr else (item.lstrip("* "), cls))
+    return fields
 
 
-def test_gemm_desc_matches_header_field_order():
+def _ctypes_fields(struct):
+    import ctypes as C
+    scalars = {C.c_int32: "int32", C.c_int64: "int64", C.c_uint64: "uint64", C.c_float: "float", C.c_double: "double"}
+
+    def cls(t):
+        if t is C.c_void_p or issubclass(t, C._Pointer):
+            return "pointer"
+        if issubclass(t, C.Array):
+            return (cls(t._type_), t._length_)
+        return scalars[t]
+
+    return [(n, cls(t)) for n, t in struct._fields_]
+
+
+def test_descriptor_structs_match_the_header_field_by_field():
+    """Every descriptor of include/mirror_hip.h against its ctypes restatement: name AND type class of each field, in order.  Equal
+    type sequences give equal layouts under the natural alignment both sides use; a field that is int32 on one side and int64 on the
+    other would shift everything behind it."""
     header = open(os.path.join(ROOT, "include", "mirror_hip.h")).read()
-    assert _struct_fields(header, "mh_gemm_desc") == [f[0] for f in _lib.GemmDesc._fields_]
-    assert _struct_fields(header, "mh_gemm_epi") == [f[0] for f in _lib.GemmEpi._fields_]
+    for c_name, binding in [("mh_gemm_desc", "GemmDesc"), ("mh_gemm_epi", "GemmEpi"), ("mh_skinny_wgrad_item", "SkinnyWgradItem"),
+                            ("mh_rna_block", "RnaBlockDesc"), ("mh_loss_terms", "LossTermsDesc"), ("mh_ema_cfg", "EmaCfg"),
+                            ("mh_optim_cfg", "OptimCfg"), ("mh_ln_bwd", "LnBwdDesc")]:
+        want, got = _struct_fields(header, c_name), _ctypes_fields(getattr(_lib, binding))
+        assert len(want) >= 6, c_name
+        assert got == want, (c_name, [(g, w) for g, w in zip(got, want) if g != w][:3])
+
+
+@pytest.mark.parametrize("fields, message", [
+    (dict(gadd=1, l=4, fan_bf16=1), "gadd excludes"),
+    (dict(gadd=1, l=4, drop_out=1, drop_db=1, drop_rows_per_batch=64), "gadd excludes"),
+    (dict(relu_out=1, relu_rows=3, dt_dy=_lib.MH_BF16), "need gadd"),
+    (dict(row_mask=1), "need gadd"),
+    (dict(lm_scale=1), "need gadd"),
+    (dict(gadd=1, l=4, relu_db=1), "relu_db rides on relu_out"),
+    (dict(gadd=1), "landmark rider: l >= 1"),
+    (dict(fan_bf16=1, dt_x=_lib.MH_BF16, dt_dx=_lib.MH_BF16), "fan rider: f32 x / dx"),
+    (dict(drop_out=1, drop_db=1, drop_rows_per_batch=64, dt_x=_lib.MH_BF16, dt_dx=_lib.MH_BF16), "drop rider: f32 x / dx"),
+])
+def test_layernorm_bwd_descriptor_refuses_rider_combinations_before_any_launch(fields, message):
+    """The combination rules of mh_ln_bwd (include/mirror_hip.h) are checked on the host in front of the first launch, so they show
+    without a GPU.  batches = 0: a rule that went missing would return MH_OK (no rows, nothing to launch) rather than run a kernel on
+    the placeholder pointers, which are aligned and never dereferenced."""
+    import ctypes as C
+    d = _lib.LnBwdDesc()
+    for n in ("dy", "x", "gamma", "mean", "rstd", "dx", "dgamma", "dbeta", "workspace"):
+        setattr(d, n, 1 << 16)
+    d.batches, d.rows_per_batch, d.D, d.x_bs, d.y_bs, d.ws_floats = 0, 64, 64, 64 * 64, 64 * 64, 3 * 64 * 8
+    for n, v in fields.items():
+        setattr(d, n, v << 16 if n in ("gadd", "relu_out", "relu_db", "row_mask", "lm_scale", "fan_bf16", "drop_out", "drop_db") else v)
+    lib = _lib.load()
+    assert lib.mh_layernorm_bwd(C.byref(d), None) == -1 and message in lib.mh_last_error().decode(), lib.mh_last_error().decode()
 
 
 def test_state_dict_contract_matches_reference_keys():

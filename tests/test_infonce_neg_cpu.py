@@ -51,7 +51,7 @@ def test_entry_points_declared_bound_and_exported():
         assert name in declared, name
         assert name in _lib.EXPORTS and name in _lib._SIGS, name
         assert hasattr(lib, name), name
-    assert lib.mh_version() == 122 and _lib.ABI_VERSION == 122
+    assert lib.mh_version() == 123 and _lib.ABI_VERSION == 123
     assert "losses/info_nce.py:126-143" in header
 
 

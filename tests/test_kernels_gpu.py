@@ -451,11 +451,13 @@ def test_gemm_f32_accuracy_vs_fp64():
 
 
 # --------------------------------------------------------------------------------------- row kernels
-@pytest.mark.parametrize("D", [32, 96, 512, 1536])
+# 3 x 7 = 21 rows run on the same-address-atomics forms, 3 x 23 = 69 rows (>= 64) on the workspace form
+@pytest.mark.parametrize("D,rpb", [(32, 7), (96, 7), (512, 7), (1536, 7), (96, 23), (512, 23)],
+                         ids=["32", "96", "512", "1536", "96-69rows", "512-69rows"])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-def test_layernorm_fwd_bwd(D, dtype):
+def test_layernorm_fwd_bwd(D, rpb, dtype):
     gen = g(D)
-    B, rpb, pad = 3, 7, 2
+    B, pad = 3, 2
     x = torch.randn(B, rpb, D, generator=gen) * 2 + 0.5
     gam, bet = torch.randn(D, generator=gen), torch.randn(D, generator=gen)
     xd = x.to(DEV)  # residual stream is f32 in both modes
@@ -604,6 +606,57 @@ def test_layernorm_bwd_lm_relu_rows_and_their_column_sums():
     ref = 2.0 + h1.double().sum((0, 1))
     close(rdb, ref.float().cpu(), 1e-5, 1e-4, "relu_db = colsum(relu_out)")
     assert float((h1.float() * (x[:, 1:] <= 0)).abs().max()) == 0.0
+
+
+def test_layernorm_bwd_landmark_rider_against_f64_autograd():
+    """The landmark rider of mh_layernorm_bwd (gadd = d loss / d xpm) against float64 autograd of what mh_layernorm_fwd_lm computes:
+    y = LayerNorm(x) behind `pad` zero rows, xpm = the means of groups of l rows, loss = sum(dy y) + sum(gadd xpm).  f32 dy and gadd:
+    per element the arithmetic of test_layernorm_fwd_bwd plus one multiply-add, hence its f32 tolerances."""
+    gen = g(65)
+    B, T, D, l = 2, 65, 64, 2
+    pad = (l - T % l) % l
+    m = (pad + T) // l
+    assert (pad, m) == (1, 33)
+    x = torch.randn(B, T, D, generator=gen) * 2 + 0.5
+    gam, bet = torch.randn(D, generator=gen), torch.randn(D, generator=gen)
+    dy = torch.randn(B, pad + T, D, generator=gen)
+    gadd = torch.randn(B, m, D, generator=gen)
+    xr, gr, br = (t.double().requires_grad_(True) for t in (x, gam, bet))
+    yr = F.layer_norm(xr, (D,), gr, br, 1e-5)
+    xpm = torch.cat([torch.zeros(B, pad, D, dtype=torch.float64), yr], 1).view(B, m, l, D).mean(2)
+    ((dy[:, pad:].double() * yr).sum() + (gadd.double() * xpm).sum()).backward()
+    xd, gd, dyd = x.to(DEV), gam.to(DEV), dy.to(DEV)
+    y = torch.empty((B, T, D), device=DEV)
+    mean, rstd = torch.empty(B * T, device=DEV), torch.empty(B * T, device=DEV)
+    K.layernorm_fwd(xd, gd, bet.to(DEV), y, mean, rstd, B, T, D, T * D, T * D, 1e-5)
+    dx = torch.empty_like(xd)
+    dg, db = torch.zeros(D, device=DEV), torch.zeros(D, device=DEV)
+    K.layernorm_bwd(dyd[:, pad:], xd, gd, mean, rstd, dx, dg, db, B, T, D, T * D, (pad + T) * D, gadd=gadd.to(DEV), pad=pad, l=l)
+    tol = 1e-5
+    close(dx, xr.grad, 10 * tol, 10 * tol, "ln dx")
+    close(dg, gr.grad, 10 * tol, 20 * tol, "ln dgamma")
+    close(db, br.grad, 10 * tol, 20 * tol, "ln dbeta")
+
+
+@pytest.mark.parametrize("other", ["fan", "drop"])
+def test_layernorm_bwd_refuses_the_landmark_rider_beside_fan_or_drop(other):
+    """mh_layernorm_bwd has no kernel for gadd beside fan_bf16 or drop_out: the call is refused (not run with one rider dropped) before
+    anything is launched, so the outputs keep what they held.  Every tensor is real and of the right shape."""
+    gen = g(64)
+    B, T, D, l = 2, 64, 64, 4
+    x = torch.randn(B, T, D, generator=gen).to(DEV)
+    gam = torch.randn(D, generator=gen).to(DEV)
+    mean, rstd = x.mean(-1).reshape(-1).contiguous(), (x.var(-1, unbiased=False) + 1e-5).rsqrt().reshape(-1).contiguous()
+    dy = torch.randn(B, T, D, generator=gen).to(DEV)
+    gadd = torch.randn(B, T // l, D, generator=gen).to(DEV)
+    dx, dg, db = torch.full((B, T, D), 7.0, device=DEV), torch.full((D,), 7.0, device=DEV), torch.full((D,), 7.0, device=DEV)
+    dout, ddb = torch.full((B, T, D), 7.0, device=DEV, dtype=torch.bfloat16), torch.full((D,), 7.0, device=DEV)
+    rider = ({"fan": (torch.randn(B, T - 1, D, generator=gen).to(DEV, torch.bfloat16), -1.0, torch.randn(B, D, generator=gen).to(DEV))}
+             if other == "fan" else {"drop": (dout, 0.1, 4242, 4096, None, ddb)})
+    with pytest.raises(K.MirrorHipError):
+        K.layernorm_bwd(dy, x, gam, mean, rstd, dx, dg, db, B, T, D, T * D, T * D, gadd=gadd, pad=0, l=l, **rider)
+    for t in (dx, dg, db, dout, ddb):
+        assert bool((t == 7.0).all())
 
 
 @pytest.mark.parametrize("cols", [16, 256, 1000, 4352])

@@ -187,4 +187,4 @@ def test_header_declares_the_entry_point_and_the_ctypes_row_matches():
     assert "mh_retrieval_ranks_grouped" in _lib.EXPORTS and "mh_retrieval_workspace_bytes" in _lib.EXPORTS
     assert re.search(r"\bint64_t\s+mh_retrieval_workspace_bytes\s*\(", header)
     assert _lib._SIGS["mh_retrieval_ranks"] == [P, P, L, L, I, P, P, P]      # the ungrouped call is as it was
-    assert _lib.ABI_VERSION == 122
+    assert _lib.ABI_VERSION == 123

@@ -144,7 +144,7 @@ def test_public_argument_checks():
 
 # ------------------------------------------------------------------ the declarations
 def test_the_three_entry_points_are_bound_within_the_same_abi_generation():
-    assert _lib.ABI_VERSION == 122
+    assert _lib.ABI_VERSION == 123
     assert _lib._SIGS["mh_retrieval_topk"] == [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     assert _lib._SIGS["mh_knn_scores"] == [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_void_p]
@@ -152,7 +152,7 @@ def test_the_three_entry_points_are_bound_within_the_same_abi_generation():
         assert name in _lib.EXPORTS
     assert "mh_retrieval_topk_workspace_bytes" not in _lib._SIGS      # no stream argument: bound by hand, with its int64 result
     lib = _lib.load()
-    assert lib.mh_version() == 122
+    assert lib.mh_version() == 123
     ws = lib.mh_retrieval_topk_workspace_bytes
     assert ws.restype is C.c_int64
     # 8 bytes per (query, strip, slot); parts above the number of key tiles (ceil(nk / 128)) is cut to it
