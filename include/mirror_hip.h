@@ -1067,6 +1067,56 @@ int64_t mh_retrieval_topk_workspace_bytes(int64_t nq, int64_t nk, int D, int kk,
 int mh_knn_scores(const int32_t* idx, const float* val, const int64_t* labels, int64_t nq, int64_t nk, int kk, int C,
                   float inv_temperature, float* scores, mh_stream s);
 
+/* ---------------------------------------------------------------- few-shot prototype probe of frozen embeddings (csrc/fewshot.hip;
+ * the reference has the protocol only: tools/gen_few_shot_files.py draws `shots` training slides per class with random.choices,
+ * tools/downstream_tasks_evaluator.py evaluates on the fold's validation slides).  The classifier is SimpleShot's nearest centroid
+ * (Wang et al. 2019): centre, L2-normalise, average the support, take the nearest prototype, over E support draws ("episodes") at once.
+ * Every entry point is deterministic (fixed summation order, no float atomics), allocates nothing and never waits on the host.
+ *
+ * mu [D] f32 = the column means of x [n x D] f32 contiguous: up to 128 strips of rows, each summed in row order in f64, the strips
+ * added in strip order, divided by n and rounded to f32 once (an error of half an ulp of mu[d], whatever n).  Two launches.
+ * 1 <= n <= 2^20, 1 <= D <= 4096.  workspace: mh_colmean_workspace_bytes(n, D) bytes (the strips' sums, 8 D per strip), 8-byte aligned,
+ * nothing to zero.  (mh_colsum adds with float atomics and in no fixed order.) */
+int mh_colmean(const float* x, int64_t n, int D, float* mu, void* workspace, mh_stream s);
+int64_t mh_colmean_workspace_bytes(int64_t n, int D);
+/* y[r] = (x[r] - mu) / max(||x[r] - mu||, eps), x, y [n x D] f32 contiguous (y may be x), mu [D]: mh_l2norm_fwd behind a centring.
+ * One wave per row: a lane adds the squares of its columns d = lane, lane + 64, .. in that order, the lanes are added by a fixed
+ * butterfly.  Same limits; eps > 0.  2 n D 4 bytes read (the second pass from cache at D <= 4096), n D 4 written. */
+int mh_center_l2norm(const float* x, const float* mu, float* y, int64_t n, int D, float eps, mh_stream s);
+#define MH_FEWSHOT_EUCLIDEAN 0   /* SimpleShot: nearest prototype by distance, as the argmax of q.p - |p|^2 / 2 */
+#define MH_FEWSHOT_COSINE 1      /* the prototype is normalised again; no bias */
+/* Prototypes of E episodes x C classes from K support rows each: rows int64 [E x C x K] indexes the prepared pool y [n x D] f32,
+ * through perm int64 [n] when that is not NULL (row = perm[rows[..]]: the class-sorted order mh_sample_rows drew in).
+ *   p[e, c] = (sum_k y[row(e, c, k)]) * (1 / K)       summed in k order in f32 from 0, one multiply by the f32 reciprocal of K
+ *   euclidean: bias[e, c] = -0.5 |p|^2 (f32; argmax_c of q.p + bias = argmin_c |q - p|);  cosine: p / max(|p|, 1e-12), bias must be NULL.
+ * protos f32 [E x Cp x D], bias f32 [E x Cp], Cp = the next power of two >= C: slots c >= C are pads, 0 with bias -inf, so that an
+ * episode's keys never straddle a 128-key tile of mh_fewshot_predict.  An index outside [0, n) (in rows, or in perm where rows points)
+ * reads nothing and makes that one prototype and its bias NaN.  |p|^2: per thread in column order, a fixed butterfly, the four waves in
+ * order.  2 <= C <= 64, 1 <= K <= 1024, 1 <= D <= 4096, 1 <= n <= 2^20, E Cp <= 2^20.  One workgroup per (e, slot);
+ * E C K D 4 bytes read, E Cp D 4 written. */
+int mh_fewshot_protos(const float* y, int64_t n, const int64_t* rows, const int64_t* perm, int E, int C, int Cp, int K, int D, int metric,
+                      float* protos, float* bias, mh_stream s);
+/* pred int32 [E x nq]: the class of the largest score[e, i, c] = dot(q_i, p[e, c]) + bias[e, c], where the dot product is the k-ordered
+ * f32 fmaf chain from 0 of the retrieval kernels (v_mfma_f32_32x32x2_f32 over the E Cp prototypes as keys, no split-K) and the bias is
+ * ONE f32 add (bias NULL, the cosine metric: no add).  A NaN score is not eligible, equal scores go to the SMALLER class, pad slots are
+ * never looked at; pred = -1 when no class is eligible (a NaN query row).  q [nq x D] f32 contiguous (prepared like the pool).
+ * Grid ceil(nq / 128) x ceil(E Cp / 128); the 128 x 128 tile goes through LDS in two halves behind the product and one thread scans
+ * each (row, episode) in ascending class order: no [nq x E Cp] matrix is written, no atomics.  Limits as above, 1 <= nq <= 2^20.
+ * (nq + E Cp) D 4 bytes read per tile row / column, E nq 4 written. */
+int mh_fewshot_predict(const float* q, const float* protos, const float* bias, int64_t nq, int E, int C, int Cp, int D, int32_t* pred,
+                       mh_stream s);
+/* Per-episode confusion counts and summary of pred [E x nq] against labels int64 [nq] (8-byte aligned):
+ *   conf int32 [E x C x C], indexed [label, prediction], STORED (nothing to zero).  A row whose label lies outside [0, C) or whose
+ *   prediction is -1 enters no cell and adds 1 to bad[e] (int32 [E], stored).
+ *   summary f64 [E x 3], with tp_c = conf[c, c], n_c = the rows of label c (a prediction of -1 included), m_c = sum_y conf[y, c]:
+ *     [0] accuracy, percent            100 sum_c tp_c / sum_c n_c
+ *     [1] balanced accuracy, percent   100 mean of tp_c / n_c over the classes with n_c > 0
+ *     [2] macro F1 in [0, 1]           mean of 2 tp_c / (n_c + m_c) over the classes with n_c + m_c > 0 (sklearn's f1_score "macro")
+ *   each formed in f64 from the integer counts in class order; NaN when no class qualifies.
+ * One workgroup per episode, integer LDS atomics only.  2 <= C <= 64, 1 <= E, nq <= 2^20. */
+int mh_fewshot_tally(const int32_t* pred, const int64_t* labels, int64_t nq, int E, int C, int32_t* conf, int32_t* bad, double* summary,
+                     mh_stream s);
+
 #ifdef __cplusplus
 }
 #endif

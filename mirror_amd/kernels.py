@@ -2634,3 +2634,117 @@ def knn_scores(idx: torch.Tensor, val: torch.Tensor, labels: torch.Tensor, num_c
     scores = torch.empty((nq, C), device=idx.device, dtype=torch.float32)
     _lib.call("mh_knn_scores", _p(idx), _p(val), _p(labels), nq, nk, kk, C, inv_t, _p(scores), stream=_stream())
     return scores
+
+
+# ----------------------------------------------------------------------------- few-shot prototype probe (csrc/fewshot.hip)
+FEWSHOT_METRIC = {"euclidean": 0, "cosine": 1}
+
+
+def _fs_f32(t: torch.Tensor, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+        got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{what} must be f32 [n, D], got {got}")
+    _chk(t)
+    n, D = t.shape
+    if not (1 <= n <= (1 << 20)) or not (1 <= D <= 4096):
+        raise MirrorHipError(f"{what}: n = {n} (1..2^20), D = {D} (1..4096)")
+    return t.detach().contiguous()
+
+
+def fewshot_cp(C: int) -> int:
+    """Key slots per episode: the next power of two >= C (pads hold 0 / -inf)."""
+    return 1 << (int(C) - 1).bit_length()
+
+
+def colmean(x: torch.Tensor) -> torch.Tensor:
+    """f32 [D] on the device (no sync): the column means of x f32 [n, D], summed in a fixed order in f64 (mh_colmean)."""
+    x = _fs_f32(x, "colmean: x")
+    n, D = x.shape
+    mu = torch.empty((D,), device=x.device, dtype=torch.float32)
+    ws = torch.empty((int(_lib.load().mh_colmean_workspace_bytes(n, D)) // 8,), device=x.device, dtype=torch.float64)
+    _lib.call("mh_colmean", _p(x), n, D, _p(mu), _p(ws), stream=_stream())
+    return mu
+
+
+def center_l2norm(x: torch.Tensor, mu: torch.Tensor, eps: float = 1e-12) -> torch.Tensor:
+    """f32 [n, D]: rows (x - mu) / max(|x - mu|, eps) (mh_center_l2norm)."""
+    x = _fs_f32(x, "center_l2norm: x")
+    n, D = x.shape
+    if not isinstance(mu, torch.Tensor) or mu.dtype != torch.float32 or tuple(mu.shape) != (D,):
+        raise ValueError(f"center_l2norm: mu must be f32 [{D}]")
+    _chk(mu)
+    y = torch.empty_like(x)
+    _lib.call("mh_center_l2norm", _p(x), _p(mu.contiguous()), _p(y), n, D, float(eps), stream=_stream())
+    return y
+
+
+def fewshot_protos(y: torch.Tensor, rows: torch.Tensor, perm: Optional[torch.Tensor], metric: str):
+    """(protos f32 [E, Cp, D], bias f32 [E, Cp] or None for "cosine") on the device (no sync): the means of the K support rows
+    rows [E, C, K] (int64) of the prepared pool y f32 [n, D], through perm int64 [n] when given (mh_fewshot_protos: k-ordered f32 sums,
+    pads 0 / -inf, an index outside the pool makes that prototype NaN)."""
+    y = _fs_f32(y, "fewshot_protos: y")
+    n, D = y.shape
+    if metric not in FEWSHOT_METRIC:
+        raise ValueError(f'fewshot_protos: metric must be "euclidean" or "cosine", got {metric!r}')
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 3 or rows.dtype != torch.int64:
+        got = f"{rows.dtype} {tuple(rows.shape)}" if isinstance(rows, torch.Tensor) else type(rows).__name__
+        raise ValueError(f"fewshot_protos: rows must be int64 [E, C, K], got {got}")
+    E, C, Kk = rows.shape
+    if perm is not None and (not isinstance(perm, torch.Tensor) or perm.dtype != torch.int64 or tuple(perm.shape) != (n,)):
+        raise ValueError(f"fewshot_protos: perm must be int64 [{n}]")
+    _chk(rows, perm)
+    Cp = fewshot_cp(C) if C >= 1 else 1
+    if not (2 <= C <= 64) or not (1 <= Kk <= 1024) or not (1 <= E and E * Cp <= (1 << 20)):
+        raise MirrorHipError(f"fewshot_protos: C = {C} (2..64), K = {Kk} (1..1024), E = {E} (E * {Cp} <= 2^20)")
+    rows = rows.contiguous()
+    perm = None if perm is None else perm.contiguous()
+    protos = torch.empty((E, Cp, D), device=y.device, dtype=torch.float32)
+    bias = torch.empty((E, Cp), device=y.device, dtype=torch.float32) if metric == "euclidean" else None
+    _lib.call("mh_fewshot_protos", _p(y), n, _p(rows), _p(perm), E, C, Cp, Kk, D, FEWSHOT_METRIC[metric], _p(protos), _p(bias), stream=_stream())
+    return protos, bias
+
+
+def fewshot_predict(q: torch.Tensor, protos: torch.Tensor, bias: Optional[torch.Tensor], C: int) -> torch.Tensor:
+    """int32 [E, nq] on the device (no sync): per episode the class with the largest q[i] . protos[e, c] (+ bias[e, c]), NaN scores not
+    eligible, ties to the smaller class, -1 when none is eligible (mh_fewshot_predict: the retrieval kernels' exact-f32 tile product;
+    the [nq, E Cp] scores are never stored)."""
+    q = _fs_f32(q, "fewshot_predict: q")
+    nq, D = q.shape
+    if isinstance(C, bool) or not isinstance(C, int) or not (2 <= C <= 64):
+        raise ValueError(f"fewshot_predict: C must be an int in [2, 64], got {C!r}")
+    Cp = fewshot_cp(C)
+    if not isinstance(protos, torch.Tensor) or protos.dtype != torch.float32 or protos.dim() != 3 or tuple(protos.shape[1:]) != (Cp, D):
+        raise ValueError(f"fewshot_predict: protos must be f32 [E, {Cp}, {D}]")
+    E = protos.shape[0]
+    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (E, Cp)):
+        raise ValueError(f"fewshot_predict: bias must be f32 [{E}, {Cp}]")
+    _chk(protos, bias)
+    if not (1 <= E and E * Cp <= (1 << 20)):
+        raise MirrorHipError(f"fewshot_predict: E = {E} episodes of {Cp} keys outside [1, 2^20] keys")
+    protos = protos.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    pred = torch.empty((E, nq), device=q.device, dtype=torch.int32)
+    _lib.call("mh_fewshot_predict", _p(q), _p(protos), _p(bias), nq, E, C, Cp, D, _p(pred), stream=_stream())
+    return pred
+
+
+def fewshot_tally(pred: torch.Tensor, labels: torch.Tensor, C: int):
+    """(conf int32 [E, C, C], bad int32 [E], summary f64 [E, 3]) on the device (no sync): per episode the confusion counts
+    [label, prediction] of pred int32 [E, nq] against labels int64 [nq], the rows left out (label outside [0, C) or prediction -1), and
+    {accuracy %, balanced accuracy %, macro F1} from the integer counts (mh_fewshot_tally)."""
+    if not isinstance(pred, torch.Tensor) or pred.dim() != 2 or pred.dtype != torch.int32:
+        raise ValueError("fewshot_tally: pred must be int32 [E, nq]")
+    E, nq = pred.shape
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or tuple(labels.shape) != (nq,):
+        raise ValueError(f"fewshot_tally: labels must be int64 [{nq}]")
+    if isinstance(C, bool) or not isinstance(C, int) or not (2 <= C <= 64):
+        raise ValueError(f"fewshot_tally: C must be an int in [2, 64], got {C!r}")
+    _chk(pred, labels)
+    if not (1 <= E <= (1 << 20)) or not (1 <= nq <= (1 << 20)):
+        raise MirrorHipError(f"fewshot_tally: E = {E}, nq = {nq} (1..2^20)")
+    pred, labels = pred.contiguous(), labels.contiguous()
+    conf = torch.empty((E, C, C), device=pred.device, dtype=torch.int32)
+    bad = torch.empty((E,), device=pred.device, dtype=torch.int32)
+    summary = torch.empty((E, 3), device=pred.device, dtype=torch.float64)
+    _lib.call("mh_fewshot_tally", _p(pred), _p(labels), nq, E, C, _p(conf), _p(bad), _p(summary), stream=_stream())
+    return conf, bad, summary
