@@ -608,7 +608,9 @@ def _blk_ok(t: torch.Tensor) -> bool:
 
 
 def _wgrad(dy: torch.Tensor, x: torch.Tensor, N: int, Kd: int, prec: Precision, dw: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """dW[N, K] += sum over every row of dy^T x (f32, split-K atomics). dy contiguous; x may be a row window."""
+    """dW[N, K] += sum over every row of dy^T x, f32.  Split-K under the bf16 policy: bf16 partial tiles + a fold pass that also
+    adds the rows % 64 remainder (kernels.SPLITK_PARTIALS; f32 atomics where mh_gemm_workspace_bytes is 0: few parts, f32
+    operands, M or N no multiple of 256).  dy contiguous; x may be a row window."""
     if dw is None:
         dw = torch.zeros((N, Kd), device=dy.device, dtype=f32)
     if dy.dim() > 2 and x.is_contiguous():
