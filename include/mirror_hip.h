@@ -1117,6 +1117,66 @@ int mh_fewshot_predict(const float* q, const float* protos, const float* bias, i
 int mh_fewshot_tally(const int32_t* pred, const int64_t* labels, int64_t nq, int E, int C, int32_t* conf, int32_t* bad, double* summary,
                      mh_stream s);
 
+/* ---------------------------------------------------------------- k-means of frozen embeddings, scored against labels (csrc/kmeans.hip;
+ * mirror_amd/cluster.py).  The label-free question of a self-supervised encoder: do the slide embeddings fall into the cohort's
+ * subtypes on their own?  Lloyd's iteration over R restarts at once (the restarts in the role of the few-shot episodes), then NMI, ARI
+ * and purity of the clusters against the labels.  Every entry point is deterministic (fixed summation order, no float atomics),
+ * allocates nothing and never waits on the host.  Shared limits: 1 <= K <= 1024 clusters, 1 <= D <= 4096, 1 <= n <= 2^20 rows,
+ * 1 <= R <= 65535 restarts (one grid row each) with R K <= 2^20.  x [n x D] f32 contiguous is the prepared pool (mh_colmean,
+ * mh_center_l2norm), cent [R x K x D] f32 the centroids, assign int32 [R x n].
+ *
+ * assign[r, i] = the k with the largest score dot(x_i, cent[r, k]) + bias[r, k]: the dot product is the k-ordered f32 fmaf chain from 0
+ * of the retrieval kernels (v_mfma_f32_32x32x2_f32, no split-K), the bias (f32 [R x K], or NULL: no add) is ONE f32 add.  A NaN score is
+ * not eligible, equal scores go to the SMALLER k, assign = -1 when nothing is eligible (a NaN row).  score f32 [R x n] or NULL: the
+ * winning value (NaN beside -1).  prev int32 [R x n] or NULL, and it may be assign itself: with it, changed[r] (int32 [R], ZEROED BY THE
+ * CALLER, NULL exactly when prev is) grows by the number of rows of restart r whose assignment differs from prev: one integer atomic per
+ * workgroup.  Grid ceil(n / 128) x R: a workgroup walks the ceil(K / 128) key tiles of its restart in ascending order and carries every
+ * row's best across them; no [n x R K] matrix is written, columns >= K are never looked at, cent needs no padding.
+ * A workgroup loads its 128 rows again for every key tile and all K centroids of its restart once: R (n ceil(K / 128) + ceil(n / 128) K) D 4
+ * bytes read, 2 n R K D flop. */
+int mh_kmeans_assign(const float* x, const float* cent, const float* bias, int64_t n, int R, int K, int D, const int32_t* prev,
+                     int32_t* assign, float* score, int32_t* changed, mh_stream s);
+#define MH_KMEANS_EUCLIDEAN 0    /* nearest centroid by distance, as the argmax of x.c - |c|^2 / 2 */
+#define MH_KMEANS_COSINE 1       /* spherical k-means: the centroid is normalised; no bias */
+/* The centroid update.  For every (r, k) with at least one row i of assign[r, i] = k:
+ *   cent[r, k, d] = (sum of x[i, d] over those rows IN ASCENDING ROW ORDER IN F64) / their number, in f64, rounded to f32 ONCE
+ *   euclidean: bias[r, k] = -0.5 |c|^2 of the ROUNDED centroid, |c|^2 in f64, rounded to f32 once
+ *   cosine: c / max(|c|, 1e-12) afterwards, the quotient in f64 from the rounded mean and rounded once more; bias must be NULL.
+ * |c|^2: per thread in column order, a fixed butterfly, the four waves in order.  count int32 [R x K]: the members, stored.  An empty
+ * cluster KEEPS its centroid and its bias and reports 0; rows with assign outside [0, K) belong to no cluster.  The same assign gives
+ * the same centroids bit for bit, so a converged restart is a fixed point of assign + update.  One workgroup per (r, k) scans
+ * assign[r, :] 256 rows at a time and compacts the members in row order: R K n 4 bytes of assign (from cache) and R n D 4 bytes of x
+ * read.  workspace: mh_kmeans_update_workspace_bytes(n, R, K, D) bytes, which is 0 for this form (NULL is fine). */
+int mh_kmeans_update(const float* x, const int32_t* assign, int64_t n, int R, int K, int D, int metric, float* cent, float* bias,
+                     int32_t* count, void* workspace, mh_stream s);
+int64_t mh_kmeans_update_workspace_bytes(int64_t n, int R, int K, int D);
+/* bias[r, k] = -0.5 |cent[r, k]|^2 for centroids that did not come out of the update (the rows a restart starts from, a caller's own
+ * centroids): |c|^2 in f64 in the update's order of additions, rounded to f32 once, so on an updated centroid it repeats the update's
+ * bias bit for bit.  One workgroup per (r, k). */
+int mh_kmeans_bias(const float* cent, int R, int K, int D, float* bias, mh_stream s);
+/* inertia f64 [R]: the sum over the rows with assign in [0, K) of |x_i - cent[r, assign[r, i]]|^2, each row's term in f64 over ascending
+ * d (one fma per column), the rows of a strip added in row order, the strips (mh_colmean's: up to 128 of at least 64 rows) in strip
+ * order.  Two launches.  workspace: mh_kmeans_inertia_workspace_bytes(n, R) bytes (8 per strip and restart), 8-byte aligned, nothing to
+ * zero.  2 R n D 4 bytes read. */
+int mh_kmeans_inertia(const float* x, const float* cent, const int32_t* assign, int64_t n, int R, int K, int D, double* inertia,
+                      void* workspace, mh_stream s);
+int64_t mh_kmeans_inertia_workspace_bytes(int64_t n, int R);
+/* Per-restart contingency counts and agreement scores of assign [R x n] against labels int64 [n] (8-byte aligned):
+ *   cont int32 [R x K x C], indexed [cluster, label], STORED (nothing to zero).  A row whose label lies outside [0, C) or whose
+ *   assignment lies outside [0, K) enters no cell and adds 1 to bad[r] (int32 [R], stored); N below is the number of the other rows.
+ *   summary f64 [R x 3], with a_k and b_c the row and column sums of cont:
+ *     [0] NMI      I / ((H(a) + H(b)) / 2), natural log, I = sum over the cells n_kc > 0 of (n_kc / N) (log n_kc - log a_k - log b_c + log N)
+ *                  (a term below 2^-52 counts as 0, a negative sum as 0), H(a) = -sum_k (a_k / N) (log a_k - log N)
+ *     [1] ARI      2 (tp tn - fn fp) / ((tp + fn) (fn + tn) + (tp + fp) (fp + tn)) from the exact integer pair counts
+ *     [2] purity   sum_k max_c n_kc / N
+ *   each formed in f64 from the integer counts: a cluster's cells in label order, the clusters in cluster order.  The degenerate cases
+ *   are sklearn's (normalized_mutual_info_score, adjusted_rand_score): NMI = 1 when neither side splits the rows, 0 when exactly one
+ *   does not or I = 0; ARI = 1 when fn = fp = 0; N = 0 gives NMI = ARI = 1 and purity NaN.
+ * One workgroup per restart; integer atomics only, on the workgroup's own slice of cont and in LDS.  1 <= K, C <= 1024, K C <= 65536,
+ * 1 <= R, n <= 2^20. */
+int mh_kmeans_tally(const int32_t* assign, const int64_t* labels, int64_t n, int R, int K, int C, int32_t* cont, int32_t* bad,
+                    double* summary, mh_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,15 +4,15 @@ Host side mirrors the reference's Python surface (`models.mirror`, `losses.MIRRO
 `losses.InfoNCE`; the survival losses and metric of train_survival.py in `losses` and `survival`, with the Cox
 partial-likelihood loss and the log-rank test beside them; the subtyping losses
 and metrics of train_subtyping.py in `losses` and `metrics`; the zero-shot retrieval metrics and top-k
-neighbours of the alignment heads in `retrieval`; the kNN probe of frozen embeddings in `knn` and the few-shot prototype probe in
-`fewshot`);
+neighbours of the alignment heads in `retrieval`; the kNN probe of frozen embeddings in `knn`, the few-shot prototype probe in
+`fewshot` and the label-free cluster probe (k-means scored with NMI, ARI and purity) in `cluster`);
 all arithmetic runs in hand-written HIP kernels behind the C ABI of `include/mirror_hip.h` (`mirror_amd/lib/libmirror_hip.so`).  There is no CPU fallback.
 """
 from ._lib import MirrorHipError, LIB_PATH  # noqa: F401
 
 __version__ = "0.1.0"
 
-__all__ = ["MirrorHipError", "LIB_PATH", "FewShotProbe", "install_aliases"]
+__all__ = ["MirrorHipError", "LIB_PATH", "FewShotProbe", "ClusterProbe", "install_aliases"]
 
 
 def __getattr__(name: str):
@@ -20,6 +20,9 @@ def __getattr__(name: str):
     if name == "FewShotProbe":
         from .fewshot import FewShotProbe
         return FewShotProbe
+    if name == "ClusterProbe":
+        from .cluster import ClusterProbe
+        return ClusterProbe
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -2640,11 +2640,13 @@ def knn_scores(idx: torch.Tensor, val: torch.Tensor, labels: torch.Tensor, num_c
 FEWSHOT_METRIC = {"euclidean": 0, "cosine": 1}
 
 
-def _fs_f32(t: torch.Tensor, what: str) -> torch.Tensor:
+def _fs_f32(t: torch.Tensor, what: str, device: bool = True) -> torch.Tensor:
+    """device=False leaves the device check to the caller, who looks at every argument's type and shape first."""
     if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
         got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
         raise ValueError(f"{what} must be f32 [n, D], got {got}")
-    _chk(t)
+    if device:
+        _chk(t)
     n, D = t.shape
     if not (1 <= n <= (1 << 20)) or not (1 <= D <= 4096):
         raise MirrorHipError(f"{what}: n = {n} (1..2^20), D = {D} (1..4096)")
@@ -2748,3 +2750,137 @@ def fewshot_tally(pred: torch.Tensor, labels: torch.Tensor, C: int):
     summary = torch.empty((E, 3), device=pred.device, dtype=torch.float64)
     _lib.call("mh_fewshot_tally", _p(pred), _p(labels), nq, E, C, _p(conf), _p(bad), _p(summary), stream=_stream())
     return conf, bad, summary
+
+
+# ----------------------------------------------------------------------------- k-means and its agreement with labels (csrc/kmeans.hip)
+KMEANS_METRIC = {"euclidean": 0, "cosine": 1}
+
+
+def _km_cent(cent, D: int, who: str):
+    """(R, K) of centroids f32 [R, K, D] inside the limits the k-means entry points share."""
+    if not isinstance(cent, torch.Tensor) or cent.dim() != 3 or cent.dtype != torch.float32 or cent.shape[2] != D:
+        got = f"{cent.dtype} {tuple(cent.shape)}" if isinstance(cent, torch.Tensor) else type(cent).__name__
+        raise ValueError(f"{who}: cent must be f32 [R, K, {D}], got {got}")
+    R, Kk = int(cent.shape[0]), int(cent.shape[1])
+    if not (1 <= Kk <= 1024) or not (1 <= R <= 65535) or R * Kk > (1 << 20):
+        raise MirrorHipError(f"{who}: K = {Kk} (1..1024), R = {R} (1..65535, R * K <= 2^20)")
+    return R, Kk
+
+
+def _km_assign(assign, R: Optional[int], n: int, who: str, what: str = "assign") -> None:
+    if (not isinstance(assign, torch.Tensor) or assign.dim() != 2 or assign.dtype != torch.int32 or assign.shape[1] != n
+            or (R is not None and assign.shape[0] != R)):
+        got = f"{assign.dtype} {tuple(assign.shape)}" if isinstance(assign, torch.Tensor) else type(assign).__name__
+        raise ValueError(f"{who}: {what} must be int32 [{'R' if R is None else R}, {n}], got {got}")
+
+
+def kmeans_assign(x: torch.Tensor, cent: torch.Tensor, bias: Optional[torch.Tensor] = None, prev: Optional[torch.Tensor] = None,
+                  changed: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, want_score: bool = False):
+    """(assign int32 [R, n], score f32 [R, n] or None) on the device (no sync): per restart the centroid with the largest
+    x[i] . cent[r, k] (+ bias[r, k]), NaN scores not eligible, ties to the smaller k, -1 when none is eligible (mh_kmeans_assign: the
+    retrieval kernels' exact-f32 tile product over ceil(K / 128) key tiles; the [n, R K] scores are never stored).  With prev (int32
+    [R, n]; it may be `out`) the int32 [R] row `changed`, zeroed by the caller, grows by the rows that differ from it."""
+    x = _fs_f32(x, "kmeans_assign: x", device=False)
+    n, D = x.shape
+    R, Kk = _km_cent(cent, D, "kmeans_assign")
+    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (R, Kk)):
+        raise ValueError(f"kmeans_assign: bias must be f32 [{R}, {Kk}]")
+    if (prev is None) != (changed is None):
+        raise ValueError("kmeans_assign: prev and changed go together")
+    if prev is not None:
+        _km_assign(prev, R, n, "kmeans_assign", "prev")
+        if not isinstance(changed, torch.Tensor) or changed.dtype != torch.int32 or tuple(changed.shape) != (R,) or not changed.is_contiguous():
+            raise ValueError(f"kmeans_assign: changed must be a contiguous int32 [{R}] tensor")
+        if not prev.is_contiguous():
+            raise ValueError("kmeans_assign: prev must be contiguous")
+    if out is not None:
+        _km_assign(out, R, n, "kmeans_assign", "out")
+        if not out.is_contiguous():
+            raise ValueError("kmeans_assign: out must be contiguous")
+    _chk(x, cent, bias, prev, changed, out)
+    cent = cent.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    if out is None:
+        out = torch.empty((R, n), device=x.device, dtype=torch.int32)
+    score = torch.empty((R, n), device=x.device, dtype=torch.float32) if want_score else None
+    _lib.call("mh_kmeans_assign", _p(x), _p(cent), _p(bias), n, R, Kk, D, _p(prev), _p(out), _p(score), _p(changed), stream=_stream())
+    return out, score
+
+
+def kmeans_update(x: torch.Tensor, assign: torch.Tensor, cent: torch.Tensor, bias: Optional[torch.Tensor], metric: str,
+                  count: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """count int32 [R, K] on the device (no sync); cent f32 [R, K, D] (and bias f32 [R, K], "euclidean") are updated IN PLACE: every
+    cluster with a member becomes the mean of its rows, summed in ascending row order in f64 and rounded to f32 once ("cosine":
+    normalised afterwards; "euclidean": bias = -|c|^2 / 2); an empty cluster keeps its centroid and bias (mh_kmeans_update)."""
+    x = _fs_f32(x, "kmeans_update: x", device=False)
+    n, D = x.shape
+    if metric not in KMEANS_METRIC:
+        raise ValueError(f'kmeans_update: metric must be "euclidean" or "cosine", got {metric!r}')
+    R, Kk = _km_cent(cent, D, "kmeans_update")
+    _km_assign(assign, R, n, "kmeans_update")
+    if (bias is not None) != (metric == "euclidean"):
+        raise ValueError("kmeans_update: the bias goes with the euclidean metric only")
+    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (R, Kk)):
+        raise ValueError(f"kmeans_update: bias must be f32 [{R}, {Kk}]")
+    if count is not None and (not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or tuple(count.shape) != (R, Kk)):
+        raise ValueError(f"kmeans_update: count must be int32 [{R}, {Kk}]")
+    _chk(x, assign, cent, bias, count)
+    if not cent.is_contiguous() or (bias is not None and not bias.is_contiguous()) or (count is not None and not count.is_contiguous()):
+        raise ValueError("kmeans_update: cent, bias and count are written in place and must be contiguous")
+    if count is None:
+        count = torch.empty((R, Kk), device=x.device, dtype=torch.int32)
+    _lib.call("mh_kmeans_update", _p(x), _p(assign.contiguous()), n, R, Kk, D, KMEANS_METRIC[metric], _p(cent), _p(bias), _p(count), None,
+              stream=_stream())
+    return count
+
+
+def kmeans_bias(cent: torch.Tensor) -> torch.Tensor:
+    """f32 [R, K] on the device (no sync): -|c|^2 / 2 of centroids f32 [R, K, D] that the update did not produce, in the update's own
+    order of additions (mh_kmeans_bias)."""
+    if not isinstance(cent, torch.Tensor) or cent.dim() != 3 or not (1 <= cent.shape[2] <= 4096):
+        raise ValueError("kmeans_bias: cent must be f32 [R, K, D] with 1 <= D <= 4096")
+    R, Kk = _km_cent(cent, int(cent.shape[2]), "kmeans_bias")
+    _chk(cent)
+    bias = torch.empty((R, Kk), device=cent.device, dtype=torch.float32)
+    _lib.call("mh_kmeans_bias", _p(cent.detach().contiguous()), R, Kk, int(cent.shape[2]), _p(bias), stream=_stream())
+    return bias
+
+
+def kmeans_inertia(x: torch.Tensor, cent: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
+    """f64 [R] on the device (no sync): the sum over the assigned rows of |x[i] - cent[r, assign[r, i]]|^2, every term and the sum in
+    f64 in a fixed order (mh_kmeans_inertia)."""
+    x = _fs_f32(x, "kmeans_inertia: x", device=False)
+    n, D = x.shape
+    R, Kk = _km_cent(cent, D, "kmeans_inertia")
+    _km_assign(assign, R, n, "kmeans_inertia")
+    _chk(x, cent, assign)
+    inertia = torch.empty((R,), device=x.device, dtype=torch.float64)
+    ws = torch.empty((int(_lib.load().mh_kmeans_inertia_workspace_bytes(n, R)) // 8,), device=x.device, dtype=torch.float64)
+    _lib.call("mh_kmeans_inertia", _p(x), _p(cent.detach().contiguous()), _p(assign.contiguous()), n, R, Kk, D, _p(inertia), _p(ws),
+              stream=_stream())
+    return inertia
+
+
+def kmeans_tally(assign: torch.Tensor, labels: torch.Tensor, K: int, C: int):
+    """(cont int32 [R, K, C], bad int32 [R], summary f64 [R, 3]) on the device (no sync): per restart the contingency counts
+    [cluster, label] of assign int32 [R, n] against labels int64 [n], the rows left out (label outside [0, C) or assign outside
+    [0, K)), and {NMI (arithmetic mean, natural log), ARI, purity} from the integer counts (mh_kmeans_tally)."""
+    if not isinstance(assign, torch.Tensor) or assign.dim() != 2 or assign.dtype != torch.int32:
+        raise ValueError("kmeans_tally: assign must be int32 [R, n]")
+    R, n = assign.shape
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or tuple(labels.shape) != (n,):
+        raise ValueError(f"kmeans_tally: labels must be int64 [{n}]")
+    for v, name in ((K, "K"), (C, "C")):
+        if isinstance(v, bool) or not isinstance(v, int) or not (1 <= v <= 1024):
+            raise ValueError(f"kmeans_tally: {name} must be an int in [1, 1024], got {v!r}")
+    if K * C > 65536:
+        raise MirrorHipError(f"kmeans_tally: K * C = {K * C} cells, 65536 at the most")
+    _chk(assign, labels)
+    if not (1 <= R <= (1 << 20)) or not (1 <= n <= (1 << 20)):
+        raise MirrorHipError(f"kmeans_tally: R = {R}, n = {n} (1..2^20)")
+    assign, labels = assign.contiguous(), labels.contiguous()
+    cont = torch.empty((R, K, C), device=assign.device, dtype=torch.int32)
+    bad = torch.empty((R,), device=assign.device, dtype=torch.int32)
+    summary = torch.empty((R, 3), device=assign.device, dtype=torch.float64)
+    _lib.call("mh_kmeans_tally", _p(assign), _p(labels), n, R, K, C, _p(cont), _p(bad), _p(summary), stream=_stream())
+    return cont, bad, summary
