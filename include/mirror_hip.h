@@ -1177,6 +1177,69 @@ int64_t mh_kmeans_inertia_workspace_bytes(int64_t n, int R);
 int mh_kmeans_tally(const int32_t* assign, const int64_t* labels, int64_t n, int R, int K, int C, int32_t* cont, int32_t* bad,
                     double* summary, mh_stream s);
 
+/* ---------------------------------------------------------------- cluster probe: seeding, silhouette, matched accuracy
+ * (csrc/cluster_ext.hip; mirror_amd/cluster.py).  As the k-means section: deterministic (fixed orders of addition, no float atomics),
+ * nothing allocated, no host wait, every launch on the caller's stream (graph-capturable).  Limits: 1 <= n <= 2^20, 1 <= D <= 4096,
+ * 1 <= K <= 1024, 1 <= R <= 65535.
+ *
+ * Silhouette of R label rows lab int32 [R x n] over the prepared rows y [n x D] f32 contiguous.  Per label row, with
+ *   s_ij  = dot(y_i, y_j): the k-ordered f32 fmaf chain from 0 of the retrieval kernels (v_mfma_f32_32x32x2_f32, no split-K)
+ *   q_i   = the SAME chain of row i with itself, so that identical rows are at distance exactly 0
+ *   d_ij  = sqrt(max(fma(-2, s_ij, q_i + q_j), 0)) in f64 from the f32 values   (MH_KMEANS_EUCLIDEAN)
+ *           1 - s_ij in f64   (MH_KMEANS_COSINE: on unit rows, which the probe prepares, sklearn's metric="cosine")
+ *   S_i[k] = sum of d_ij over j != i with lab_j = k; the pair i = j is left out BY INDEX, not by value
+ *   a_i = S_i[l_i] / (n_l_i - 1),  b_i = min over the non-empty k != l_i of S_i[k] / n_k,  s_i = (b_i - a_i) / max(a_i, b_i)
+ *   s_i = 0 when the row's cluster is a singleton or max(a_i, b_i) = 0 (sklearn's silhouette_samples); NaN when fewer than two clusters
+ *   are non-empty.
+ * A row with lab outside [0, K) takes no part, as sample or as neighbour: it adds 1 to bad[r] (int32 [R], stored) and its sil is NaN.
+ * sil f64 [R x n] or NULL; mean f64 [R]: the mean of s_i over the rows that take part, each of mh_colmean's strips (up to 128 of at
+ * least 64 rows) added in row order, the strips in strip order, divided by their number; NaN when fewer than two clusters are non-empty
+ * or no row takes part.  A NaN anywhere in y may make every sample, and the mean, NaN.
+ * Order of additions of S_i[k]: the rows are sorted by cluster id (stable: row order inside a cluster, the rows outside last) and
+ * the sorted sequence is cut into key tiles of 128 and those into quarters of 32; the T = ceil(n' / 128) key tiles (n' the rows that
+ * take part) form P contiguous groups, group p the tiles [p T / P, (p + 1) T / P), with P = min(16, ceil(n / 128), ceil(1024 /
+ * ceil(n / 128)), 1 + floor(2^26 / (8 n K))): a workgroup per (row tile, group), so that a few thousand rows fill the chip, while the
+ * slices of S beyond the first stay within 64 MiB; P = 1 from n = 2^17 on and wherever n K >= 2^23.  A (tile,
+ * quarter)'s distances to cluster k are added in ascending sorted order from 0; of one tile, the quarters' sums for the same k that
+ * reach an end of their quarter are added to each other in ascending order first; the results are added to the group's sum in
+ * ascending order, and the P groups' sums in group order.  Every sample therefore carries a relative error of a few 2^-53 on top of
+ * the f32 products'.
+ * Five launches per label row; the n x n products are formed once per label row and never stored: no [n x n] matrix, the only state
+ * that grows with K is S f64 [P x n x K] in the workspace: [n x K] and at most 64 MiB more (one form for every K).  Rows are loaded again for
+ * every key tile: 2 n ceil(n / 128) D 4 bytes read, 2 n^2 D flop per label row.
+ * workspace: mh_silhouette_workspace_bytes(n, K, D) bytes (the sorted copy of y, S, the samples in row order, q, the order, the sorted
+ * ids, the cluster sizes: about n (4 D + 8 P K + 20)), 16-byte aligned, nothing to zero, shared by the label rows. */
+int mh_silhouette(const float* y, const int32_t* lab, int64_t n, int R, int K, int D, int metric, double* sil, double* mean, int32_t* bad,
+                  void* workspace, mh_stream s);
+int64_t mh_silhouette_workspace_bytes(int64_t n, int K, int D);
+/* k-means++ seeding (Arthur and Vassilvitskii 2007: D^2 sampling, ONE draw per centre; NOT sklearn's greedy variant with local
+ * trials) of R restarts at once from the prepared rows y [n x D]: rows int64 [R x K] (8-byte aligned) the chosen rows, cent f32
+ * [R x K x D] bit copies of them.  R K <= 2^20.  Restart r uses draw id offset + r of the data feed's Philox stream under kind = 2
+ * (counter = (lo32(blk), 2, lo32(draw), 0x80000000 | hi32(draw)), key = seed; draw ids stay below 2^63); u_j comes from elements 2 j and
+ * 2 j + 1 by mh_sample_weighted's rule, (((w >> 5) << 26) | (w' >> 6)) 2^-53.
+ *   centre 0    row floor(u_0 n), one f64 product
+ *   centre j    m_i = min over the chosen centres c of |y_i - c|^2: f64, ascending d, one fma per column (mh_kmeans_inertia's term);
+ *               a NaN distance counts as 0.  P_p = the sum of m_i over strip p of mh_colmean's partition in row order from 0,
+ *               T = the sum of P_p in strip order from 0, t = u_j T.  The pick is the first strip p with (P_0 + .. + P_p) > t, and in it
+ *               the first row i with (P_0 + .. + P_(p-1)) + (the strip's own running sum up to and including i) > t: such a row has
+ *               m_i > 0.  If rounding leaves no strip (t = T), the pick is the last row with m_i > 0.  If T = 0 (fewer distinct rows
+ *               than centres) or T is NaN, the pick is row floor(u_j n).
+ * The distance is Euclidean in the prepared space for both metrics (on unit rows it is monotone in the cosine).  Two launches per
+ * centre (one for centre 0): m is updated against the newest centre only.  workspace: mh_kmeanspp_workspace_bytes(n, R) bytes
+ * (m f64 [R x n] and 8 per strip and restart), 8-byte aligned, nothing to zero.  R K n D 4 bytes read. */
+int mh_kmeanspp_init(const float* y, int64_t n, int R, int K, int D, uint64_t seed, uint64_t offset, int64_t* rows, float* cent,
+                     void* workspace, mh_stream s);
+int64_t mh_kmeanspp_workspace_bytes(int64_t n, int R);
+/* Matched accuracy from the contingency counts cont int32 [R x K x C] of mh_kmeans_tally ([cluster, label], non-negative): per
+ * restart a one-to-one assignment of clusters to classes with min(K, C) pairs and the largest sum of cont[k, match[k]].
+ *   match int32 [R x K]: the class of cluster k, or -1 (K > C: K - C clusters stay without);  hits int64 [R] (8-byte aligned): that sum.
+ * All arithmetic is integer (int64 potentials), so hits is the exact optimum; among assignments of equal sum the choice is
+ * deterministic (the smaller column of equal minima) but otherwise free.  One workgroup per restart: shortest augmenting paths
+ * (Jonker-Volgenant), the smaller side as rows, a serial outer loop with the minimum over the columns workgroup-parallel; the cells
+ * are read from LDS when K C <= 4096 and from cont in place otherwise: no workspace.  The tally's limits: 1 <= K, C <= 1024,
+ * K C <= 65536, 1 <= R <= 2^20. */
+int mh_cluster_match(const int32_t* cont, int R, int K, int C, int32_t* match, int64_t* hits, mh_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -260,13 +260,17 @@ _SIGS = {
     "mh_kmeans_bias": [P, I, I, I, P],
     "mh_kmeans_inertia": [P, P, P, L, I, I, I, P, P],
     "mh_kmeans_tally": [P, P, L, I, I, I, P, P, P],
+    "mh_silhouette": [P, P, L, I, I, I, I, P, P, P, P],
+    "mh_kmeanspp_init": [P, L, I, I, I, U64, U64, P, P, P],
+    "mh_cluster_match": [P, I, I, I, P, P],
 }
 EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "mh_gemm_variant_name", "mh_device_ok", "mh_nys_attn3_ws_floats", "mh_rna_block_workspace_bytes",
                                  "mh_rna_block_lds_bytes", "mh_rna_block_fits",
                                  "mh_gemm_workspace_bytes", "mh_layernorm_bwd_workspace_bytes", "mh_nys_attn3_workspace_bytes",
                                  "mh_pinv_chain_workspace_bytes", "mh_resconv_bwd_workspace_bytes", "mh_mask_apply_bwd_dbias_ok",
                                  "mh_retrieval_workspace_bytes", "mh_retrieval_topk_workspace_bytes", "mh_cox_workspace_bytes",
-                                 "mh_colmean_workspace_bytes", "mh_kmeans_update_workspace_bytes", "mh_kmeans_inertia_workspace_bytes"])
+                                 "mh_colmean_workspace_bytes", "mh_kmeans_update_workspace_bytes", "mh_kmeans_inertia_workspace_bytes",
+                                 "mh_silhouette_workspace_bytes", "mh_kmeanspp_workspace_bytes"])
 
 _lib = None
 
@@ -349,6 +353,13 @@ def load() -> C.CDLL:
     lib.mh_kmeans_update_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int]
     lib.mh_kmeans_inertia_workspace_bytes.restype = C.c_int64
     lib.mh_kmeans_inertia_workspace_bytes.argtypes = [C.c_int64, C.c_int]
+    if not hasattr(lib, "mh_silhouette_workspace_bytes"):
+        raise MirrorHipError(f"{LIB_PATH} lacks mh_silhouette_workspace_bytes: rebuild the library (`make -C mirror_amd/csrc`, or "
+                             "__graft_entry__.build())")
+    lib.mh_silhouette_workspace_bytes.restype = C.c_int64
+    lib.mh_silhouette_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
+    lib.mh_kmeanspp_workspace_bytes.restype = C.c_int64
+    lib.mh_kmeanspp_workspace_bytes.argtypes = [C.c_int64, C.c_int]
     for name, sig in _SIGS.items():
         fn = getattr(lib, name, None)
         if fn is None:      # entry points added within a generation (no argument list changed): an older build lacks them

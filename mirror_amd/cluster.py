@@ -14,11 +14,17 @@ float atomics, the same assignment gives the same centroids bit for bit, so a co
 is harmless), the inertia `mh_kmeans_inertia`, the contingency counts and the three scores `mh_kmeans_tally`.  Nothing waits on the
 host inside an iteration: the per-iteration change counts go to an int32 [max_iter, R] table that is read back every 8 iterations.
 A restart without explicit start begins at K distinct rows drawn by `mh_sample_rows` (the Philox stream of the data feed: the pool is
-one "slide" of n rows, restart r uses draw id offset + r), gathered by `mh_gather_rows`.
+one "slide" of n rows, restart r uses draw id offset + r), gathered by `mh_gather_rows`; with `seeding="kmeans++"` the start is
+`mh_kmeanspp_init` on the prepared rows instead: plain k-means++ (Arthur and Vassilvitskii: D^2 sampling, one draw per centre, NOT
+sklearn's greedy variant with local trials), every restart at once, draw id offset + r of the same stream under kind 2.
 
-Not built: k-means++ seeding on the device (pass `init=` from sklearn's `kmeans_plusplus` on the prepared rows), relocating empty
-clusters (an empty cluster keeps its centroid; `cluster_empty` reports them), bf16 embeddings, a pool gathered over DDP ranks,
-Hungarian-matched accuracy, silhouette.
+Beside NMI, ARI and purity: `evaluate(..., matched=True)` adds the accuracy under the best one-to-one matching of clusters to classes
+(`mh_cluster_match` on the contingency counts: the Hungarian assignment, exact in integers), and `silhouette()` /
+`evaluate(..., silhouette=True)` the one figure that needs no labels (`mh_silhouette`: the same tile product over all pairs of rows
+with an f64 distance-sum epilogue, no [n, n] matrix; `silhouette_score` is the same for labels from elsewhere).
+
+Not built: relocating empty clusters (an empty cluster keeps its centroid; `cluster_empty` reports them), bf16 embeddings, a pool
+gathered over DDP ranks.
 """
 from __future__ import annotations
 
@@ -30,9 +36,10 @@ import torch
 from . import kernels as K
 from ._lib import MirrorHipError
 
-__all__ = ["ClusterProbe"]
+__all__ = ["ClusterProbe", "silhouette_score"]
 
 _CHECK_EVERY = 8          # iterations between two read-backs of the change table
+_SEEDING = ("random", "kmeans++")
 
 
 def _int_in(v, lo: int, hi: int, what: str) -> int:
@@ -57,12 +64,16 @@ class ClusterProbe:
     tensor: the restart of least inertia, ties to the smaller index), `labels_` = `assign_[best_]`, `changed_` (the int32 table) and,
     for a drawn start, `init_rows_` int64 [R, K].  `fit` waits on the host once per 8 iterations, for the change table alone.
 
+    seeding: "random" (K distinct rows drawn uniformly, the default) or "kmeans++" (mh_kmeanspp_init on the prepared rows: Euclidean
+    D^2 sampling in the prepared space for both metrics); either sets `init_rows_`, neither is used when `init=` is given.
+
     init: an f32 [R', K, D] tensor of starting centroids in the prepared space (R' replaces `restarts`), or None for the draw, which
     needs K <= n.  After `evaluate`: `per_restart` f64 [R, 3] (NMI, ARI, purity), `contingency` int32 [R, K, C] ([cluster, label])
-    and `bad` int32 [R] (rows with a label outside [0, C) or without a cluster) stay on the device."""
+    and `bad` int32 [R] (rows with a label outside [0, C) or without a cluster) stay on the device; with `matched=True` also `match_`
+    int32 [R, K] (the class every cluster is matched to, or -1) and `hits_` int64 [R]."""
 
     def __init__(self, num_clusters: int, restarts: int = 16, max_iter: int = 100, metric: str = "cosine", center: bool = True,
-                 seed: int = 0, offset: int = 0, device=None):
+                 seed: int = 0, offset: int = 0, device=None, seeding: str = "random"):
         _int_in(num_clusters, 1, 1024, "num_clusters")
         _int_in(restarts, 1, min(65535, (1 << 20) // num_clusters), f"restarts (restarts x {num_clusters} centroids <= 2^20)")
         _int_in(max_iter, 1, 1 << 16, "max_iter")
@@ -71,6 +82,8 @@ class ClusterProbe:
         if isinstance(seed, bool) or not isinstance(seed, int):
             raise ValueError(f"seed must be an int, got {seed!r}")
         _int_in(offset, 0, (1 << 62), "offset")
+        if seeding not in _SEEDING:
+            raise ValueError(f'seeding must be "random" or "kmeans++", got {seeding!r}')
         d = torch.device("cuda") if device is None else torch.device(device)
         if d.type != "cuda":
             raise MirrorHipError(f"mirror_amd metrics keep their state on a HIP device, got {d}")
@@ -81,6 +94,7 @@ class ClusterProbe:
         self.center = bool(center)
         self.seed = seed
         self.offset = offset
+        self.seeding = seeding
         self.device = d
         self._clear()
 
@@ -88,7 +102,7 @@ class ClusterProbe:
         self.mu_ = self._y = None
         self.centroids_ = self.bias_ = self.assign_ = self.inertia_ = self.counts_ = self.n_iter_ = self.best_ = self.labels_ = None
         self.changed_ = self.init_rows_ = None
-        self.per_restart = self.contingency = self.bad = None
+        self.per_restart = self.contingency = self.bad = self.match_ = self.hits_ = None
 
     # ------------------------------------------------------------------ preparation
     def _rows(self, emb, what: str, D: Optional[int] = None) -> torch.Tensor:
@@ -131,7 +145,10 @@ class ClusterProbe:
         x = emb.detach().to(device=self.device, dtype=torch.float32, non_blocking=True, copy=True).contiguous()
         self.mu_ = K.colmean(x) if self.center else None
         y = self._y = self._prepare(x)
-        if init is None:
+        if init is None and self.seeding == "kmeans++":
+            R = self.restarts
+            self.init_rows_, cent = K.kmeanspp_init(y, R, Kk, self.seed, self.offset)
+        elif init is None:
             R = self.restarts
             slots = torch.zeros((R,), device=self.device, dtype=torch.int64)          # every restart draws from the one "slide"
             lengths = torch.full((1,), n, device=self.device, dtype=torch.int64)
@@ -186,26 +203,52 @@ class ClusterProbe:
         self._fitted()
         return self.assign(emb, self.centroids_.index_select(0, self.best_.view(1)))[0]
 
+    def silhouette(self, restarts: str = "best", samples: bool = False):
+        """The silhouette of the fitted clusters over the prepared rows under the probe's metric, on the device, no host wait:
+        restarts="best" scores `labels_` (a 0-d f64 tensor), "all" every restart (f64 [R]).  samples=True returns (mean, per-row values)
+        instead: f64 [n], or [R, n] for "all"."""
+        self._fitted()
+        if restarts not in ("best", "all"):
+            raise ValueError(f'restarts must be "best" or "all", got {restarts!r}')
+        lab = self.assign_ if restarts == "all" else self.labels_.view(1, -1)
+        mean, _, sil = K.silhouette(self._y, lab, self.num_clusters, self.metric, samples=bool(samples))
+        if restarts == "best":
+            mean, sil = mean[0], (None if sil is None else sil[0])
+        return (mean, sil) if samples else mean
+
     # ------------------------------------------------------------------ scores
-    def evaluate(self, labels: torch.Tensor, num_classes: int):
+    def evaluate(self, labels: torch.Tensor, num_classes: int, matched: bool = False, silhouette: bool = False):
         """The fitted clusters against labels (integer [n], the pool's rows in order): an OrderedDict of `cluster_nmi` (arithmetic
         normalisation, natural log), `cluster_ari`, `cluster_purity` of the best restart, each with `_mean` and `_std` (sample standard
         deviation, 0 for one restart) over the restarts, then `cluster_inertia`, `cluster_empty` (the empty clusters of the best
-        restart), `cluster_k`, `cluster_restarts` and `cluster_n`."""
+        restart), `cluster_k`, `cluster_restarts` and `cluster_n`.  matched=True appends `cluster_acc`, `cluster_acc_mean`,
+        `cluster_acc_std` (per cent of the tallied rows that fall into the class their cluster is matched to, under the best one-to-one
+        matching; NaN when no row is tallied) and `match_` (int32 [R, K], on the device); silhouette=True appends `cluster_silhouette`
+        (the best restart's).  One host copy either way."""
         self._fitted()
         R, n = self.assign_.shape
         if not isinstance(labels, torch.Tensor) or labels.dim() != 1 or labels.numel() != n or labels.dtype not in (torch.int32, torch.int64):
             got = f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, torch.Tensor) else type(labels).__name__
             raise ValueError(f"labels must be an int32 / int64 [{n}] tensor, got {got}")
         _int_in(num_classes, 1, 1024, "num_classes")
+        for v, name in ((matched, "matched"), (silhouette, "silhouette")):
+            if not isinstance(v, bool):
+                raise ValueError(f"{name} must be a bool, got {v!r}")
         if num_classes * self.num_clusters > 65536:
             raise MirrorHipError(f"ClusterProbe: {self.num_clusters} clusters x {num_classes} classes = "
                                  f"{num_classes * self.num_clusters} contingency cells, 65536 at the most")
         labels = labels.detach().to(device=self.device, dtype=torch.int64, non_blocking=True)
         self.contingency, self.bad, self.per_restart = K.kmeans_tally(self.assign_, labels, self.num_clusters, num_classes)
         best = self.best_.view(1)
-        flat = torch.cat([self.per_restart.reshape(-1), best.double(), self.inertia_.index_select(0, best),
-                          (self.counts_.index_select(0, best) == 0).sum().double().view(1)]).cpu()      # the one host wait
+        parts = [self.per_restart.reshape(-1), best.double(), self.inertia_.index_select(0, best),
+                 (self.counts_.index_select(0, best) == 0).sum().double().view(1)]
+        self.match_ = self.hits_ = None
+        if matched:
+            self.match_, self.hits_ = K.cluster_match(self.contingency)
+            parts += [self.hits_.double(), self.bad.double()]                  # counts <= 2^20: exact in f64
+        if silhouette:
+            parts.append(self.silhouette().view(1))
+        flat = torch.cat(parts).cpu()                                         # the one host wait
         table, best = flat[:3 * R].view(R, 3), int(flat[3 * R])
         out: "OrderedDict[str, float]" = OrderedDict()
         for j, name in enumerate(("cluster_nmi", "cluster_ari", "cluster_purity")):
@@ -218,4 +261,41 @@ class ClusterProbe:
         out["cluster_k"] = self.num_clusters
         out["cluster_restarts"] = R
         out["cluster_n"] = n
+        at = 3 * R + 3
+        if matched:
+            acc = 100.0 * flat[at:at + R] / (n - flat[at + R:at + 2 * R])      # 0 / 0 = NaN: no row was tallied
+            out["cluster_acc"] = float(acc[best])
+            out["cluster_acc_mean"] = float(acc.mean())
+            out["cluster_acc_std"] = float(acc.std(unbiased=True)) if R > 1 else 0.0
+            out["match_"] = self.match_
+            at += 2 * R
+        if silhouette:
+            out["cluster_silhouette"] = float(flat[at])
         return out
+
+
+def silhouette_score(emb: torch.Tensor, labels: torch.Tensor, num_clusters: int, metric: str = "cosine", center: bool = False,
+                     samples: bool = False, device=None):
+    """The silhouette of labels that did not come from a probe: emb floating point [n, D], labels integer [n] or [R, n] (cluster ids in
+    [0, num_clusters); a row outside takes no part and has sample NaN).  The rows are prepared as ClusterProbe prepares them
+    (center=False: "euclidean" as they are, "cosine" normalised, which is sklearn's silhouette_score with that metric).  Returns device
+    tensors without a host wait: the mean (0-d f64, or [R]), and with samples=True (mean, per-row values f64 [n] or [R, n])."""
+    if isinstance(num_clusters, bool) or not isinstance(num_clusters, int):
+        raise ValueError(f"num_clusters must be an int in [1, 1024], got {num_clusters!r}")
+    p = ClusterProbe(num_clusters, restarts=1, metric=metric, center=center, device=device)
+    p._rows(emb, "emb")
+    n = emb.shape[0]
+    if (not isinstance(labels, torch.Tensor) or labels.dtype not in (torch.int32, torch.int64) or labels.dim() not in (1, 2)
+            or labels.shape[-1] != n):
+        got = f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, torch.Tensor) else type(labels).__name__
+        raise ValueError(f"labels must be an int32 / int64 [{n}] or [R, {n}] tensor, got {got}")
+    x = emb.detach().to(device=p.device, dtype=torch.float32, non_blocking=True).contiguous()
+    p.mu_ = K.colmean(x) if p.center else None
+    y = p._prepare(x)
+    lab = labels.detach().to(device=p.device, non_blocking=True)
+    if lab.dtype == torch.int64:
+        lab = lab.clamp(-1, num_clusters).to(torch.int32)                     # outside stays outside
+    mean, _, sil = K.silhouette(y, lab.view(-1, n).contiguous(), num_clusters, metric, samples=bool(samples))
+    if labels.dim() == 1:
+        mean, sil = mean[0], (None if sil is None else sil[0])
+    return (mean, sil) if samples else mean

@@ -2884,3 +2884,70 @@ def kmeans_tally(assign: torch.Tensor, labels: torch.Tensor, K: int, C: int):
     summary = torch.empty((R, 3), device=assign.device, dtype=torch.float64)
     _lib.call("mh_kmeans_tally", _p(assign), _p(labels), n, R, K, C, _p(cont), _p(bad), _p(summary), stream=_stream())
     return cont, bad, summary
+
+
+# ----------------------------------------------------------------------------- seeding, silhouette, matched accuracy (csrc/cluster_ext.hip)
+def silhouette(y: torch.Tensor, lab: torch.Tensor, K: int, metric: str, samples: bool = False):
+    """(mean f64 [R], bad int32 [R], sil f64 [R, n] or None) on the device (no sync): the silhouette of every label row lab int32 [R, n]
+    (cluster ids in [0, K); a row outside takes no part, counts in bad and has sil NaN) over the prepared rows y f32 [n, D], distances
+    from the retrieval kernels' exact-f32 tile product in f64 (mh_silhouette: no [n, n] matrix; the product is formed once per label
+    row).  "cosine" is 1 - y_i . y_j: y must hold unit rows."""
+    y = _fs_f32(y, "silhouette: y", device=False)
+    n, D = y.shape
+    if metric not in KMEANS_METRIC:
+        raise ValueError(f'silhouette: metric must be "euclidean" or "cosine", got {metric!r}')
+    if isinstance(K, bool) or not isinstance(K, int) or not (1 <= K <= 1024):
+        raise ValueError(f"silhouette: K must be an int in [1, 1024], got {K!r}")
+    _km_assign(lab, None, n, "silhouette", "lab")
+    R = int(lab.shape[0])
+    _chk(y, lab)
+    if not (1 <= R <= 65535):
+        raise MirrorHipError(f"silhouette: R = {R} label rows (1..65535)")
+    lab = lab.contiguous()
+    mean = torch.empty((R,), device=y.device, dtype=torch.float64)
+    bad = torch.empty((R,), device=y.device, dtype=torch.int32)
+    sil = torch.empty((R, n), device=y.device, dtype=torch.float64) if samples else None
+    ws = torch.empty((int(_lib.load().mh_silhouette_workspace_bytes(n, K, D)) // 8,), device=y.device, dtype=torch.float64)
+    _lib.call("mh_silhouette", _p(y), _p(lab), n, R, K, D, KMEANS_METRIC[metric], _p(sil), _p(mean), _p(bad), _p(ws), stream=_stream())
+    return mean, bad, sil
+
+
+def kmeanspp_init(y: torch.Tensor, R: int, K: int, seed: int, offset: int):
+    """(rows int64 [R, K], cent f32 [R, K, D]) on the device (no sync): k-means++ seeding (D^2 sampling, one draw per centre; not
+    sklearn's greedy variant) of R restarts from the prepared rows y f32 [n, D]; restart r uses draw id offset + r of the data feed's
+    stream under kind 2; cent are bit copies of y[rows] (mh_kmeanspp_init)."""
+    y = _fs_f32(y, "kmeanspp_init: y", device=False)
+    n, D = y.shape
+    for v, name, hi in ((K, "K", 1024), (R, "R", 65535)):
+        if isinstance(v, bool) or not isinstance(v, int) or not (1 <= v <= hi):
+            raise ValueError(f"kmeanspp_init: {name} must be an int in [1, {hi}], got {v!r}")
+    if R * K > (1 << 20):
+        raise MirrorHipError(f"kmeanspp_init: R * K = {R * K} centres, 2^20 at the most")
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"kmeanspp_init: seed must be an int, got {seed!r}")
+    if isinstance(offset, bool) or not isinstance(offset, int) or not (0 <= offset and offset + R < (1 << 63)):
+        raise ValueError(f"kmeanspp_init: draw ids offset .. offset + R must stay in [0, 2^63), got offset = {offset!r}")
+    _chk(y)
+    rows = torch.empty((R, K), device=y.device, dtype=torch.int64)
+    cent = torch.empty((R, K, D), device=y.device, dtype=torch.float32)
+    ws = torch.empty((int(_lib.load().mh_kmeanspp_workspace_bytes(n, R)) // 8,), device=y.device, dtype=torch.float64)
+    _lib.call("mh_kmeanspp_init", _p(y), n, R, K, D, seed & (2 ** 64 - 1), offset, _p(rows), _p(cent), _p(ws), stream=_stream())
+    return rows, cent
+
+
+def cluster_match(cont: torch.Tensor):
+    """(match int32 [R, K], hits int64 [R]) on the device (no sync): per restart the one-to-one assignment of clusters to classes of
+    largest total count in cont int32 [R, K, C] ([cluster, label], as kmeans_tally writes it): match[r, k] the class of cluster k or -1,
+    hits[r] the matched rows: the exact optimum (mh_cluster_match: integer shortest augmenting paths)."""
+    if not isinstance(cont, torch.Tensor) or cont.dim() != 3 or cont.dtype != torch.int32:
+        got = f"{cont.dtype} {tuple(cont.shape)}" if isinstance(cont, torch.Tensor) else type(cont).__name__
+        raise ValueError(f"cluster_match: cont must be int32 [R, K, C], got {got}")
+    R, K, C = (int(v) for v in cont.shape)
+    if not (1 <= K <= 1024) or not (1 <= C <= 1024) or K * C > 65536 or not (1 <= R <= (1 << 20)):
+        raise MirrorHipError(f"cluster_match: K = {K}, C = {C} (1..1024, K * C <= 65536), R = {R} (1..2^20)")
+    _chk(cont)
+    cont = cont.contiguous()
+    match = torch.empty((R, K), device=cont.device, dtype=torch.int32)
+    hits = torch.empty((R,), device=cont.device, dtype=torch.int64)
+    _lib.call("mh_cluster_match", _p(cont), R, K, C, _p(match), _p(hits), stream=_stream())
+    return match, hits
