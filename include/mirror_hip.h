@@ -37,6 +37,11 @@ int mh_version(void);       /* 123 */
 int mh_exp_build(void);      /* 1: built with -DMH_EXP (timing-experiment switches compiled in); the shipped build returns 0 */
 /* number of visible HIP devices whose arch is gfx950; <=0 means the library cannot run here */
 int mh_device_ok(void);
+/* Which of its kernels the calling thread's last elementwise / row-kernel entry point launched: "<entry>:<form>", e.g. "add:quad",
+ * "softmax_fwd:block,scalar", "layernorm_bwd:ws", "colsum:bf16oct", or "<entry>:none" for a call that returned before any launch.
+ * mh_note_form is what the entry points call beside the launch they pick: it keeps the POINTER (string literals only), one store. */
+void mh_note_form(const char* literal);
+const char* mh_last_form(void);
 
 /* ---------------------------------------------------------------- MFMA GEMM (all contractions)
  * C[z] (+)= act(alpha * op(A[z]) x op(B[z]) + diag*I + bias + rcoef*R[z])   z = (b1, b2) two-level batch

@@ -264,7 +264,7 @@ _SIGS = {
     "mh_kmeanspp_init": [P, L, I, I, I, U64, U64, P, P, P],
     "mh_cluster_match": [P, I, I, I, P, P],
 }
-EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "mh_gemm_variant_name", "mh_device_ok", "mh_nys_attn3_ws_floats", "mh_rna_block_workspace_bytes",
+EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "mh_gemm_variant_name", "mh_note_form", "mh_last_form", "mh_device_ok", "mh_nys_attn3_ws_floats", "mh_rna_block_workspace_bytes",
                                  "mh_rna_block_lds_bytes", "mh_rna_block_fits",
                                  "mh_gemm_workspace_bytes", "mh_layernorm_bwd_workspace_bytes", "mh_nys_attn3_workspace_bytes",
                                  "mh_pinv_chain_workspace_bytes", "mh_resconv_bwd_workspace_bytes", "mh_mask_apply_bwd_dbias_ok",
@@ -306,6 +306,8 @@ def load() -> C.CDLL:
     lib.mh_exp_build.restype = C.c_int
     lib.mh_gemm_variant_name.restype = C.c_char_p
     lib.mh_gemm_variant_name.argtypes = []
+    lib.mh_last_form.restype = C.c_char_p
+    lib.mh_last_form.argtypes = []
     lib.mh_device_ok.restype = C.c_int
     lib.mh_nys_attn3_ws_floats.restype = C.c_int64
     lib.mh_nys_attn3_ws_floats.argtypes = [C.c_int, C.c_int, C.c_int]

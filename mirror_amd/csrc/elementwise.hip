@@ -54,11 +54,13 @@ __global__ __launch_bounds__(256) void relu_bwd4_kernel(const TY* y, const TDY* 
     else { MACRO(bf16_t, bf16_t); }
 
 extern "C" int mh_add(const void* a, const void* b, void* y, int64_t n, int dt_a, int dt_b, int dt_y, mh_stream s) {
+    mh_note_form("add:none");
     if (n == 0) return MH_OK;
     if (n % 4 == 0 && mh_quad_ok(a, mh_dt_size(dt_a)) && mh_quad_ok(b, mh_dt_size(dt_b)) && mh_quad_ok(y, mh_dt_size(dt_y))) {
 #define ADD4_(TA, TB)                                                                                                    \
     if (dt_y == MH_F32) hipLaunchKernelGGL((add4_kernel<TA, TB, float>), EW_GRID(n / 4), dim3(256), 0, (hipStream_t)s, (const TA*)a, (const TB*)b, (float*)y, (long)(n / 4)); \
     else hipLaunchKernelGGL((add4_kernel<TA, TB, bf16_t>), EW_GRID(n / 4), dim3(256), 0, (hipStream_t)s, (const TA*)a, (const TB*)b, (bf16_t*)y, (long)(n / 4))
+        mh_note_form("add:quad");
         DISPATCH2(dt_a, dt_b, ADD4_)
 #undef ADD4_
         MH_LAUNCH_CHECK("mh_add");
@@ -67,6 +69,7 @@ extern "C" int mh_add(const void* a, const void* b, void* y, int64_t n, int dt_a
 #define ADD_(TA, TB)                                                                                                     \
     if (dt_y == MH_F32) hipLaunchKernelGGL((add_kernel<TA, TB, float>), EW_GRID(n), dim3(256), 0, (hipStream_t)s, (const TA*)a, (const TB*)b, (float*)y, (long)n); \
     else hipLaunchKernelGGL((add_kernel<TA, TB, bf16_t>), EW_GRID(n), dim3(256), 0, (hipStream_t)s, (const TA*)a, (const TB*)b, (bf16_t*)y, (long)n)
+    mh_note_form("add:scalar");
     DISPATCH2(dt_a, dt_b, ADD_)
 #undef ADD_
     MH_LAUNCH_CHECK("mh_add");
@@ -102,15 +105,18 @@ extern "C" int mh_lm_merge(const float* a, const float* b, void* out, int64_t ro
 }
 
 extern "C" int mh_cast(const void* x, void* y, int64_t n, int dt_x, int dt_y, mh_stream s) {
+    mh_note_form("cast:none");
     if (n == 0) return MH_OK;
     if (n % 4 == 0 && mh_quad_ok(x, mh_dt_size(dt_x)) && mh_quad_ok(y, mh_dt_size(dt_y))) {
 #define CAST4_(TX, TY) hipLaunchKernelGGL((cast4_kernel<TX, TY>), EW_GRID(n / 4), dim3(256), 0, (hipStream_t)s, (const TX*)x, (TY*)y, (long)(n / 4))
+        mh_note_form("cast:quad");
         DISPATCH2(dt_x, dt_y, CAST4_)
 #undef CAST4_
         MH_LAUNCH_CHECK("mh_cast");
         return MH_OK;
     }
 #define CAST_(TX, TY) hipLaunchKernelGGL((cast_kernel<TX, TY>), EW_GRID(n), dim3(256), 0, (hipStream_t)s, (const TX*)x, (TY*)y, (long)n)
+    mh_note_form("cast:scalar");
     DISPATCH2(dt_x, dt_y, CAST_)
 #undef CAST_
     MH_LAUNCH_CHECK("mh_cast");
@@ -118,8 +124,10 @@ extern "C" int mh_cast(const void* x, void* y, int64_t n, int dt_x, int dt_y, mh
 }
 
 extern "C" int mh_gelu_fwd(const void* x, void* y, int64_t n, int dt_x, int dt_y, mh_stream s) {
+    mh_note_form("gelu_fwd:none");
     if (n == 0) return MH_OK;
 #define GELU_(TX, TY) hipLaunchKernelGGL((gelu_fwd_kernel<TX, TY>), EW_GRID(n), dim3(256), 0, (hipStream_t)s, (const TX*)x, (TY*)y, (long)n)
+    mh_note_form("gelu_fwd:scalar");
     DISPATCH2(dt_x, dt_y, GELU_)
 #undef GELU_
     MH_LAUNCH_CHECK("mh_gelu_fwd");
@@ -127,9 +135,11 @@ extern "C" int mh_gelu_fwd(const void* x, void* y, int64_t n, int dt_x, int dt_y
 }
 
 extern "C" int mh_gelu_bwd(const void* x, const void* dy, void* dx, int64_t n, int dt_x, int dt_dy, int dt_dx, mh_stream s) {
+    mh_note_form("gelu_bwd:none");
     MH_REQUIRE(dt_dy == dt_dx, "mh_gelu_bwd: dy/dx dtype mismatch");
     if (n == 0) return MH_OK;
 #define GELUB_(TX, TD) hipLaunchKernelGGL((gelu_bwd_kernel<TX, TD, TD>), EW_GRID(n), dim3(256), 0, (hipStream_t)s, (const TX*)x, (const TD*)dy, (TD*)dx, (long)n)
+    mh_note_form("gelu_bwd:scalar");
     DISPATCH2(dt_x, dt_dy, GELUB_)
 #undef GELUB_
     MH_LAUNCH_CHECK("mh_gelu_bwd");
@@ -138,6 +148,7 @@ extern "C" int mh_gelu_bwd(const void* x, const void* dy, void* dx, int64_t n, i
 
 extern "C" int mh_relu_bwd(const void* y, const void* dy, void* dx, int64_t n_per_batch, int batches, int64_t y_bs,
                            int64_t dy_bs, int64_t dx_bs, int dt_y, int dt_dy, int dt_dx, mh_stream s) {
+    mh_note_form("relu_bwd:none");
     if (n_per_batch == 0 || batches == 0) return MH_OK;
     MH_REQUIRE(batches <= 65535, "mh_relu_bwd: too many batches");
     if (n_per_batch % 4 == 0 && y_bs % 4 == 0 && dy_bs % 4 == 0 && dx_bs % 4 == 0 && mh_quad_ok(y, mh_dt_size(dt_y)) &&
@@ -147,6 +158,7 @@ extern "C" int mh_relu_bwd(const void* y, const void* dy, void* dx, int64_t n_pe
     if (dt_dx == MH_F32) hipLaunchKernelGGL((relu_bwd4_kernel<TY, TDY, float>), g4, dim3(256), 0, (hipStream_t)s, (const TY*)y, (const TDY*)dy, (float*)dx, (long)(n_per_batch / 4), (long)y_bs, (long)dy_bs, (long)dx_bs); \
     else hipLaunchKernelGGL((relu_bwd4_kernel<TY, TDY, bf16_t>), g4, dim3(256), 0, (hipStream_t)s, (const TY*)y, (const TDY*)dy, (bf16_t*)dx, (long)(n_per_batch / 4), (long)y_bs, (long)dy_bs, (long)dx_bs)
 #define RELUB4_(TY, TD) RELUB42_(TY, TD)
+        mh_note_form("relu_bwd:quad");
         DISPATCH2(dt_y, dt_dy, RELUB4_)
 #undef RELUB42_
 #undef RELUB4_
@@ -158,6 +170,7 @@ extern "C" int mh_relu_bwd(const void* y, const void* dy, void* dx, int64_t n_pe
     if (dt_dx == MH_F32) hipLaunchKernelGGL((relu_bwd_kernel<TY, TDY, float>), grid, dim3(256), 0, (hipStream_t)s, (const TY*)y, (const TDY*)dy, (float*)dx, (long)n_per_batch, (long)y_bs, (long)dy_bs, (long)dx_bs); \
     else hipLaunchKernelGGL((relu_bwd_kernel<TY, TDY, bf16_t>), grid, dim3(256), 0, (hipStream_t)s, (const TY*)y, (const TDY*)dy, (bf16_t*)dx, (long)n_per_batch, (long)y_bs, (long)dy_bs, (long)dx_bs)
 #define RELUB_(TY, TD) RELUB2_(TY, TD)
+    mh_note_form("relu_bwd:scalar");
     DISPATCH2(dt_y, dt_dy, RELUB_)
 #undef RELUB2_
 #undef RELUB_
@@ -498,9 +511,11 @@ __global__ __launch_bounds__(256) void colsum_f32_vec_kernel(const float* __rest
 }
 
 extern "C" int mh_colsum(const void* x, float* out, int64_t rows, int cols, int64_t ld, int dt, mh_stream s) {
+    mh_note_form("colsum:none");
     if (rows == 0 || cols == 0) return MH_OK;
     if (dt == MH_F32 && cols % 4 == 0 && ld % 4 == 0 && ((uintptr_t)x & 15) == 0 && rows >= 32) {
         dim3 gv(mh_cdiv(cols / 4, 64), (unsigned)min((long)mh_cdiv(rows, 32), 64L));
+        mh_note_form("colsum:f32quad");
         hipLaunchKernelGGL(colsum_f32_vec_kernel, gv, dim3(256), 0, (hipStream_t)s, (const float*)x, out, (long)rows, cols, (long)ld);
         MH_LAUNCH_CHECK("mh_colsum");
         return MH_OK;
@@ -510,11 +525,13 @@ extern "C" int mh_colsum(const void* x, float* out, int64_t rows, int cols, int6
         long nb = max(1L, 512L / cb);
         long band = (mh_cdiv(rows, nb) + 31) / 32 * 32;
         dim3 gv(cb, mh_cdiv(rows, band));
+        mh_note_form("colsum:bf16oct");
         hipLaunchKernelGGL(colsum_bf16_vec_kernel, gv, dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, out, (long)rows, cols, (long)ld, band);
         MH_LAUNCH_CHECK("mh_colsum");
         return MH_OK;
     }
     dim3 grid(mh_cdiv(cols, 64), mh_cdiv(rows, CS_BAND));
+    mh_note_form("colsum:scalar");
     MH_DISPATCH_DT(dt, T, hipLaunchKernelGGL((colsum_kernel<T>), grid, dim3(256), 0, (hipStream_t)s, (const T*)x, out, (long)rows, cols, (long)ld));
     MH_LAUNCH_CHECK("mh_colsum");
     return MH_OK;
@@ -791,16 +808,19 @@ __global__ __launch_bounds__(256) void mask_apply_bwd_d1_kernel(const T* dy, TDX
 extern "C" int mh_mask_apply_fwd(const void* x, void* y, const float* mask, const float* token, const float* pos, int B, int T, int D,
                                  int first, int token_scalar, int dt_x, int dt_y, mh_stream s) {
     const long total = (long)B * T * D;
+    mh_note_form("mask_apply_fwd:none");
     if (total == 0) return MH_OK;
     if (dt_y == MH_F32 && D % 4 == 0 && !token_scalar && mh_quad_ok(x, mh_dt_size(dt_x)) &&
         (((uintptr_t)y | (uintptr_t)token | (uintptr_t)pos) & 15) == 0) {
         dim3 gv((unsigned)min((long)mh_cdiv((long)B * T, 4), 16384L));
+        mh_note_form("mask_apply_fwd:quad");
         if (dt_x == MH_F32) hipLaunchKernelGGL((mask_apply_fwd_vec_kernel<float>), gv, dim3(256), 0, (hipStream_t)s, (const float*)x, (float*)y, mask, token, pos, B, T, D, first);
         else hipLaunchKernelGGL((mask_apply_fwd_vec_kernel<bf16_t>), gv, dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, (float*)y, mask, token, pos, B, T, D, first);
         MH_LAUNCH_CHECK("mh_mask_apply_fwd");
         return MH_OK;
     }
 #define MAF_(TX, TY) hipLaunchKernelGGL((mask_apply_fwd_kernel<TX, TY>), EW_GRID(total), dim3(256), 0, (hipStream_t)s, (const TX*)x, (TY*)y, mask, token, pos, B, T, D, first, token_scalar)
+    mh_note_form("mask_apply_fwd:scalar");
     DISPATCH2(dt_x, dt_y, MAF_)
 #undef MAF_
     MH_LAUNCH_CHECK("mh_mask_apply_fwd");
@@ -814,11 +834,13 @@ extern "C" int mh_mask_apply_bwd_dbias_ok(const void* dy, const void* dx, const 
 
 extern "C" int mh_mask_apply_bwd(const void* dy, void* dx, const float* mask, float* dtoken, float* dpos, int B, int T, int D,
                                  int first, int token_scalar, int dt_dy, int dt_dx, float* dbias, mh_stream s) {
+    mh_note_form("mask_apply_bwd:none");
     if (T == 0 || D == 0 || B == 0) return MH_OK;
     MH_REQUIRE(!dbias || mh_mask_apply_bwd_dbias_ok(dy, dx, dpos, D, dt_dy, dt_dx),
                "mh_mask_apply_bwd: dbias needs the quad form (f32 dy, D %% 4 == 0, D >= 256, 16-byte aligned operands)");
     if (D == 1) {
 #define MAB1_(TDY, TDX) hipLaunchKernelGGL((mask_apply_bwd_d1_kernel<TDY, TDX>), dim3(mh_cdiv(T, 256)), dim3(256), 0, (hipStream_t)s, (const TDY*)dy, (TDX*)dx, mask, dtoken, dpos, B, T, first)
+        mh_note_form("mask_apply_bwd:d1");
         DISPATCH2(dt_dy, dt_dx, MAB1_)
 #undef MAB1_
         MH_LAUNCH_CHECK("mh_mask_apply_bwd");
@@ -827,6 +849,7 @@ extern "C" int mh_mask_apply_bwd(const void* dy, void* dx, const float* mask, fl
     if (mh_mask_apply_bwd_dbias_ok(dy, dx, dpos, D, dt_dy, dt_dx)) {
         const int band = 16;     // rows of t per block: T / 16 x D / 256 blocks, 4 waves x 8 rows of 1 KiB in flight each
         dim3 gv(mh_cdiv(D, 256), mh_cdiv(T, band));
+        mh_note_form("mask_apply_bwd:quad");
         if (dt_dx == MH_F32) hipLaunchKernelGGL((mask_apply_bwd_vec_kernel<float>), gv, dim3(256), 0, (hipStream_t)s, (const float*)dy, (float*)dx, mask, dtoken, dpos, B, T, D, first, token_scalar, band, dbias);
         else hipLaunchKernelGGL((mask_apply_bwd_vec_kernel<bf16_t>), gv, dim3(256), 0, (hipStream_t)s, (const float*)dy, (bf16_t*)dx, mask, dtoken, dpos, B, T, D, first, token_scalar, band, dbias);
         MH_LAUNCH_CHECK("mh_mask_apply_bwd");
@@ -834,6 +857,7 @@ extern "C" int mh_mask_apply_bwd(const void* dy, void* dx, const float* mask, fl
     }
     dim3 grid(mh_cdiv(D, 64), mh_cdiv(T, MB_BAND));
 #define MAB_(TDY, TDX) hipLaunchKernelGGL((mask_apply_bwd_kernel<TDY, TDX>), grid, dim3(256), 0, (hipStream_t)s, (const TDY*)dy, (TDX*)dx, mask, dtoken, dpos, B, T, D, first, token_scalar)
+    mh_note_form("mask_apply_bwd:scalar");
     DISPATCH2(dt_dy, dt_dx, MAB_)
 #undef MAB_
     MH_LAUNCH_CHECK("mh_mask_apply_bwd");
@@ -957,9 +981,11 @@ __global__ __launch_bounds__(256) void row_scale_kernel(const T* x, const float*
     }
 }
 extern "C" int mh_row_scale(const void* x, const float* scale, void* y, int64_t rows, int D, int dt, mh_stream s) {
+    mh_note_form("row_scale:none");
     if (rows == 0 || D == 0) return MH_OK;
     dim3 grid((unsigned)min((long)mh_cdiv(rows, 4), 16384L));
     const bool vec = D % 4 == 0 && mh_quad_ok(x, mh_dt_size(dt)) && mh_quad_ok(y, mh_dt_size(dt));
+    mh_note_form(vec ? "row_scale:quad" : "row_scale:scalar");
 #define RS_(T)                                                                                                                 \
     if (vec) hipLaunchKernelGGL((row_scale_kernel<T, true>), grid, dim3(256), 0, (hipStream_t)s, (const T*)x, scale, (T*)y, (long)rows, D); \
     else hipLaunchKernelGGL((row_scale_kernel<T, false>), grid, dim3(256), 0, (hipStream_t)s, (const T*)x, scale, (T*)y, (long)rows, D)
@@ -1086,8 +1112,10 @@ __global__ __launch_bounds__(256) void fanout_bwd_kernel(const float* __restrict
 
 extern "C" int mh_fanout_bwd(const float* gfull, const void* x, float alpha, const float* c, float* dE, int B, int T, int D, int dt_x,
                              mh_stream s) {
+    mh_note_form("fanout_bwd:none");
     if (B == 0 || T == 0 || D == 0) return MH_OK;
     const bool vec = D % 4 == 0 && mh_quad_ok(gfull, 4) && mh_quad_ok(x, mh_dt_size(dt_x)) && mh_quad_ok(c, 4) && mh_quad_ok(dE, 4);
+    mh_note_form(vec ? "fanout_bwd:quad" : "fanout_bwd:scalar");
     dim3 grid((unsigned)min((long)mh_cdiv((long)B * T, 4), 16384L));
 #define FAN_(TX)                                                                                                                   \
     if (vec) hipLaunchKernelGGL((fanout_bwd_kernel<TX, true>), grid, dim3(256), 0, (hipStream_t)s, gfull, (const TX*)x, alpha, c, dE, B, T, D); \

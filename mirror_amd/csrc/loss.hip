@@ -282,6 +282,7 @@ static int mse_masked_fwd_launch(const void* pred, const void* tgt, const float*
     MH_REQUIRE(rows_per_batch > 0, "mh_mse_masked_fwd: rows_per_batch must be positive");
     if (D == 1 && tgt_bs == rows_per_batch) {       // contiguous [rows] vectors
         dim3 gf((unsigned)min((long)mh_cdiv(rows, 256), 64L));
+        mh_note_form("mse_masked_fwd:flat");
 #define MSEFL(TP, TT) hipLaunchKernelGGL((mse_masked_fwd_flat_kernel<TP, TT>), gf, dim3(256), 0, (hipStream_t)s, (const TP*)pred, (const TT*)tgt, mask, acc, (long)rows, part)
         if (dt_p == MH_F32 && dt_t == MH_F32) { MSEFL(float, float); }
         else if (dt_p == MH_BF16 && dt_t == MH_BF16) { MSEFL(bf16_t, bf16_t); }
@@ -294,6 +295,7 @@ static int mse_masked_fwd_launch(const void* pred, const void* tgt, const float*
     }
     dim3 grid((unsigned)min((long)mh_cdiv(rows, 16), 1024L));
     const bool vec = D % 4 == 0 && tgt_bs % 4 == 0 && mh_quad_ok(pred, mh_dt_size(dt_p)) && mh_quad_ok(tgt, mh_dt_size(dt_t));
+    mh_note_form(vec ? "mse_masked_fwd:quad" : "mse_masked_fwd:scalar");
 #define MSEF(TP, TT)                                                                                                              \
     if (vec) hipLaunchKernelGGL((mse_masked_fwd_kernel<TP, TT, true>), grid, dim3(256), 0, (hipStream_t)s, (const TP*)pred, (const TT*)tgt, mask, acc, (long)rows, D, (long)rows_per_batch, (long)tgt_bs, part); \
     else hipLaunchKernelGGL((mse_masked_fwd_kernel<TP, TT, false>), grid, dim3(256), 0, (hipStream_t)s, (const TP*)pred, (const TT*)tgt, mask, acc, (long)rows, D, (long)rows_per_batch, (long)tgt_bs, part)
@@ -309,6 +311,7 @@ static int mse_masked_fwd_launch(const void* pred, const void* tgt, const float*
 
 extern "C" int mh_mse_masked_fwd(const void* pred, const void* tgt, const float* mask, float* acc, int64_t rows, int D,
                                  int64_t rows_per_batch, int64_t tgt_bs, int dt_p, int dt_t, mh_stream s) {
+    mh_note_form("mse_masked_fwd:none");
     if (rows == 0) return MH_OK;
     int nb = 0;
     return mse_masked_fwd_launch(pred, tgt, mask, acc, rows, D, rows_per_batch, tgt_bs, dt_p, dt_t, nullptr, &nb, s);
@@ -316,6 +319,7 @@ extern "C" int mh_mse_masked_fwd(const void* pred, const void* tgt, const float*
 
 extern "C" int mh_mse_masked_fwd_ordered(const void* pred, const void* tgt, const float* mask, float* acc, int64_t rows, int D,
                                          int64_t rows_per_batch, int64_t tgt_bs, int dt_p, int dt_t, float* workspace, mh_stream s) {
+    mh_note_form("mse_masked_fwd:none");
     if (rows == 0) return MH_OK;
     MH_REQUIRE(workspace && ((uintptr_t)workspace & 3) == 0, "mh_mse_masked_fwd_ordered: workspace must be a 4-byte aligned pointer");
     int nb = 0;
@@ -331,6 +335,7 @@ extern "C" int mh_mse_masked_fwd_ordered(const void* pred, const void* tgt, cons
 extern "C" int mh_mse_masked_bwd(const void* pred, const void* tgt, const float* mask, const float* acc, const float* g,
                                  float gmul, void* dpred, void* dtgt, int64_t rows, int D, int64_t rows_per_batch, int64_t tgt_bs,
                                  int dt_p, int dt_t, int dt_dp, float* colsum_ws, int cs_blocks, mh_stream s) {
+    mh_note_form("mse_masked_bwd:none");
     if (rows == 0) return MH_OK;
     MH_REQUIRE(rows_per_batch > 0, "mh_mse_masked_bwd: rows_per_batch must be positive");
     const bool vec = D % 4 == 0 && tgt_bs % 4 == 0 && mh_quad_ok(pred, mh_dt_size(dt_p)) && mh_quad_ok(tgt, mh_dt_size(dt_t)) &&
@@ -339,6 +344,7 @@ extern "C" int mh_mse_masked_bwd(const void* pred, const void* tgt, const float*
         MH_REQUIRE(vec && D % 256 == 0 && D <= 1024 && cs_blocks >= 1 && cs_blocks <= 4096 && dt_p == MH_BF16 && dt_t == MH_F32 && dt_dp == MH_BF16 &&
                        (((uintptr_t)colsum_ws) & 15) == 0,
                    "mh_mse_masked_bwd: colsum_ws needs bf16 pred / f32 target / bf16 dpred on quads and D in {256, 512, 768, 1024} (got D=%d, dtypes %d %d %d)", D, dt_p, dt_t, dt_dp);
+        mh_note_form("mse_masked_bwd:colsum");
 #define MSECS(NCH) hipLaunchKernelGGL((mse_masked_bwd_cs_kernel<bf16_t, float, bf16_t, NCH>), dim3(cs_blocks), dim3(256), 0, (hipStream_t)s, (const bf16_t*)pred, (const float*)tgt, mask, acc, g, (bf16_t*)dpred, (float*)dtgt, (long)rows, (long)rows_per_batch, (long)tgt_bs, gmul, colsum_ws)
         if (D == 256) MSECS(1); else if (D == 512) MSECS(2); else if (D == 768) MSECS(3); else MSECS(4);
 #undef MSECS
@@ -346,6 +352,7 @@ extern "C" int mh_mse_masked_bwd(const void* pred, const void* tgt, const float*
         return MH_OK;
     }
     dim3 grid((unsigned)min((long)mh_cdiv(rows * D, 256), 16384L)), gv((unsigned)min((long)mh_cdiv(rows, 4), 16384L));
+    mh_note_form(vec ? "mse_masked_bwd:quad" : "mse_masked_bwd:scalar");
 #define MSEB3(TP, TT, TD)                                                                                                         \
     if (vec) hipLaunchKernelGGL((mse_masked_bwd_vec_kernel<TP, TT, TD>), gv, dim3(256), 0, (hipStream_t)s, (const TP*)pred, (const TT*)tgt, mask, acc, g, (TD*)dpred, (TT*)dtgt, (long)rows, D, (long)rows_per_batch, (long)tgt_bs, gmul); \
     else hipLaunchKernelGGL((mse_masked_bwd_kernel<TP, TT, TD>), grid, dim3(256), 0, (hipStream_t)s, (const TP*)pred, (const TT*)tgt, mask, acc, g, (TD*)dpred, (TT*)dtgt, (long)rows, D, (long)rows_per_batch, (long)tgt_bs, gmul)

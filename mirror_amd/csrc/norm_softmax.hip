@@ -435,6 +435,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const TDY* __res
 extern "C" int mh_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                                 int batches, int rpb, int D, int64_t x_bs, int64_t y_bs, float eps, int dt_x, int dt_y,
                                 mh_stream s) {
+    mh_note_form("layernorm_fwd:none");
     MH_REQUIRE(D >= 1 && D <= 64 * LN_MAXPL, "mh_layernorm_fwd: D=%d unsupported (max %d)", D, 64 * LN_MAXPL);
     const long rows = (long)batches * rpb;
     if (rows == 0) return MH_OK;
@@ -444,6 +445,7 @@ extern "C" int mh_layernorm_fwd(const void* x, const float* gamma, const float* 
 #define LN_FV1(TX, TY, NC) hipLaunchKernelGGL((layernorm_fwd_vec_kernel<TX, TY, NC>), grid, dim3(256), 0, (hipStream_t)s, (const TX*)x, gamma, beta, (TY*)y, mean, rstd, rows, rpb, D, (long)x_bs, (long)y_bs, eps)
 #define LN_FV(TX, TY) do { if (D <= 512) LN_FV1(TX, TY, 2); else if (D <= 1024) LN_FV1(TX, TY, 4); else LN_FV1(TX, TY, 8); } while (0)
     if (vecok) {
+        mh_note_form("layernorm_fwd:quad");
         if (dt_x == MH_F32 && dt_y == MH_F32) LN_FV(float, float);
         else if (dt_x == MH_F32 && dt_y == MH_BF16) LN_FV(float, bf16_t);
         else if (dt_x == MH_BF16 && dt_y == MH_BF16) LN_FV(bf16_t, bf16_t);
@@ -454,6 +456,7 @@ extern "C" int mh_layernorm_fwd(const void* x, const float* gamma, const float* 
 #undef LN_FV
 #undef LN_FV1
 #define LN_F(TX, TY) hipLaunchKernelGGL((layernorm_fwd_kernel<TX, TY>), grid, dim3(256), 0, (hipStream_t)s, (const TX*)x, gamma, beta, (TY*)y, mean, rstd, rows, rpb, D, (long)x_bs, (long)y_bs, eps)
+    mh_note_form("layernorm_fwd:scalar");
     if (dt_x == MH_F32 && dt_y == MH_F32) LN_F(float, float);
     else if (dt_x == MH_F32 && dt_y == MH_BF16) LN_F(float, bf16_t);
     else if (dt_x == MH_BF16 && dt_y == MH_BF16) LN_F(bf16_t, bf16_t);
@@ -803,6 +806,7 @@ static int ln_bwd_impl(const mh_ln_bwd& d, mh_stream s) {
     const bool f32_x = dt_x == MH_F32 && d.dt_dx == MH_F32;
     const bool ws3 = ((uintptr_t)d.workspace & 15) == 0 && d.ws_floats >= 3L * D;
     const bool fan_ok = rpb >= 2 && ((uintptr_t)d.fan_bf16 & 7) == 0 && (!d.fan_cls || ((uintptr_t)d.fan_cls & 15) == 0) && D % 4 == 0;
+    mh_note_form("layernorm_bwd:none");
     // every check runs before the first launch: a refused call has touched nothing
     MH_REQUIRE(D >= 1 && D <= 64 * LN_MAXPL, "mh_layernorm_bwd: D=%d unsupported", D);
     MH_REQUIRE(d.dt_dx == dt_x, "mh_layernorm_bwd: dx dtype must equal x dtype");
@@ -827,6 +831,7 @@ static int ln_bwd_impl(const mh_ln_bwd& d, mh_stream s) {
     if (rows == 0) return MH_OK;
     dim3 grid((unsigned)min((long)mh_cdiv(rows, 4), (long)ln_bwd_blocks()));
     if (ws_form) {          // rows_per_block rows per block (a multiple of 8: two rows per wave per iteration), nb <= ws capacity
+        mh_note_form("layernorm_bwd:ws");
         float* third = d.drop_out ? d.drop_db : d.relu_db;      // the fold's third destination: a bias gradient's column sums
         const int segs = third ? 3 : 2;                         // partial rows per block: dgamma, dbeta (, third)
         const long cap = d.ws_floats / ((long)segs * D);
@@ -868,6 +873,7 @@ static int ln_bwd_impl(const mh_ln_bwd& d, mh_stream s) {
     if (vecok) {
 #define LN_BV1(TX, TDY, NC) hipLaunchKernelGGL((layernorm_bwd_vec_kernel<TX, TDY, NC>), grid, dim3(256), 0, (hipStream_t)s, (const TDY*)d.dy, (const TX*)d.x, d.gamma, d.mean, d.rstd, (TX*)d.dx, d.dgamma, d.dbeta, rows, rpb, D, (long)d.x_bs, (long)d.y_bs, d.accumulate_dx)
 #define LN_BV(TX, TDY) do { if (D <= 512) LN_BV1(TX, TDY, 2); else if (D <= 1024) LN_BV1(TX, TDY, 4); else LN_BV1(TX, TDY, 8); } while (0)
+        mh_note_form("layernorm_bwd:quad");
         if (dt_x == MH_F32 && dt_dy == MH_F32) LN_BV(float, float);
         else if (dt_x == MH_F32 && dt_dy == MH_BF16) LN_BV(float, bf16_t);
         else if (dt_x == MH_BF16 && dt_dy == MH_BF16) LN_BV(bf16_t, bf16_t);
@@ -878,6 +884,7 @@ static int ln_bwd_impl(const mh_ln_bwd& d, mh_stream s) {
         return MH_OK;
     }
 #define LN_B(TX, TDY) hipLaunchKernelGGL((layernorm_bwd_kernel<TX, TDY, TX>), grid, dim3(256), 0, (hipStream_t)s, (const TDY*)d.dy, (const TX*)d.x, d.gamma, d.mean, d.rstd, (TX*)d.dx, d.dgamma, d.dbeta, rows, rpb, D, (long)d.x_bs, (long)d.y_bs, d.accumulate_dx)
+    mh_note_form("layernorm_bwd:scalar");
     if (dt_x == MH_F32 && dt_dy == MH_F32) LN_B(float, float);
     else if (dt_x == MH_F32 && dt_dy == MH_BF16) LN_B(float, bf16_t);
     else if (dt_x == MH_BF16 && dt_dy == MH_BF16) LN_B(bf16_t, bf16_t);
@@ -1080,6 +1087,7 @@ extern "C" int mh_softmax_masked_bwd(const void* y, const void* dy, void* dx, co
 
 extern "C" int mh_softmax_fwd(const void* x, void* y, int64_t rows, int cols, int64_t ldx, int64_t ldy, int dt_x,
                               int dt_y, mh_stream s) {
+    mh_note_form("softmax_fwd:none");
     MH_REQUIRE(cols >= 1, "mh_softmax_fwd: cols=%d", cols);
     if (rows == 0) return MH_OK;
     const bool wave = cols <= 1024;
@@ -1088,6 +1096,7 @@ extern "C" int mh_softmax_fwd(const void* x, void* y, int64_t rows, int cols, in
 #define SM_FV(TX, TY)                                                                                                     \
     if (wave) hipLaunchKernelGGL((softmax_fwd_vec_kernel<TX, TY, true, 4>), grid, dim3(256), 0, (hipStream_t)s, (const TX*)x, (TY*)y, (long)rows, cols, (long)ldx, (long)ldy); \
     else hipLaunchKernelGGL((softmax_fwd_vec_kernel<TX, TY, false, 12>), grid, dim3(256), 0, (hipStream_t)s, (const TX*)x, (TY*)y, (long)rows, cols, (long)ldx, (long)ldy)
+        mh_note_form(wave ? "softmax_fwd:wave,quad" : "softmax_fwd:block,quad");
         if (dt_x == MH_F32 && dt_y == MH_F32) { SM_FV(float, float); }
         else if (dt_x == MH_F32 && dt_y == MH_BF16) { SM_FV(float, bf16_t); }
         else if (dt_x == MH_BF16 && dt_y == MH_BF16) { SM_FV(bf16_t, bf16_t); }
@@ -1099,6 +1108,7 @@ extern "C" int mh_softmax_fwd(const void* x, void* y, int64_t rows, int cols, in
 #define SM_F(TX, TY)                                                                                                   \
     if (wave) hipLaunchKernelGGL((softmax_fwd_kernel<TX, TY, true>), grid, dim3(256), 0, (hipStream_t)s, (const TX*)x, (TY*)y, (long)rows, cols, (long)ldx, (long)ldy); \
     else hipLaunchKernelGGL((softmax_fwd_kernel<TX, TY, false>), grid, dim3(256), 0, (hipStream_t)s, (const TX*)x, (TY*)y, (long)rows, cols, (long)ldx, (long)ldy)
+    mh_note_form(wave ? "softmax_fwd:wave,scalar" : "softmax_fwd:block,scalar");
     if (dt_x == MH_F32 && dt_y == MH_F32) { SM_F(float, float); }
     else if (dt_x == MH_F32 && dt_y == MH_BF16) { SM_F(float, bf16_t); }
     else if (dt_x == MH_BF16 && dt_y == MH_BF16) { SM_F(bf16_t, bf16_t); }
@@ -1110,6 +1120,7 @@ extern "C" int mh_softmax_fwd(const void* x, void* y, int64_t rows, int cols, in
 
 extern "C" int mh_softmax_bwd(const void* y, const void* dy, void* dx, int64_t rows, int cols, int64_t ldy, int64_t lddy,
                               int64_t lddx, int dt_y, int dt_dy, int dt_dx, mh_stream s) {
+    mh_note_form("softmax_bwd:none");
     MH_REQUIRE(cols >= 1, "mh_softmax_bwd: cols=%d", cols);
     MH_REQUIRE(dt_dy == dt_dx, "mh_softmax_bwd: dy and dx dtypes must match");
     if (rows == 0) return MH_OK;
@@ -1120,6 +1131,7 @@ extern "C" int mh_softmax_bwd(const void* y, const void* dy, void* dx, int64_t r
 #define SM_BV(TY, TD)                                                                                                     \
     if (wave) hipLaunchKernelGGL((softmax_bwd_vec_kernel<TY, TD, true, 4>), grid, dim3(256), 0, (hipStream_t)s, (const TY*)y, (const TD*)dy, (TD*)dx, (long)rows, cols, (long)ldy, (long)lddy, (long)lddx); \
     else hipLaunchKernelGGL((softmax_bwd_vec_kernel<TY, TD, false, 12>), grid, dim3(256), 0, (hipStream_t)s, (const TY*)y, (const TD*)dy, (TD*)dx, (long)rows, cols, (long)ldy, (long)lddy, (long)lddx)
+        mh_note_form(wave ? "softmax_bwd:wave,quad" : "softmax_bwd:block,quad");
         if (dt_y == MH_F32 && dt_dy == MH_F32) { SM_BV(float, float); }
         else if (dt_y == MH_F32 && dt_dy == MH_BF16) { SM_BV(float, bf16_t); }
         else if (dt_y == MH_BF16 && dt_dy == MH_BF16) { SM_BV(bf16_t, bf16_t); }
@@ -1131,6 +1143,7 @@ extern "C" int mh_softmax_bwd(const void* y, const void* dy, void* dx, int64_t r
 #define SM_B(TY, TD)                                                                                                   \
     if (wave) hipLaunchKernelGGL((softmax_bwd_kernel<TY, TD, TD, true>), grid, dim3(256), 0, (hipStream_t)s, (const TY*)y, (const TD*)dy, (TD*)dx, (long)rows, cols, (long)ldy, (long)lddy, (long)lddx); \
     else hipLaunchKernelGGL((softmax_bwd_kernel<TY, TD, TD, false>), grid, dim3(256), 0, (hipStream_t)s, (const TY*)y, (const TD*)dy, (TD*)dx, (long)rows, cols, (long)ldy, (long)lddy, (long)lddx)
+    mh_note_form(wave ? "softmax_bwd:wave,scalar" : "softmax_bwd:block,scalar");
     if (dt_y == MH_F32 && dt_dy == MH_F32) { SM_B(float, float); }
     else if (dt_y == MH_F32 && dt_dy == MH_BF16) { SM_B(float, bf16_t); }
     else if (dt_y == MH_BF16 && dt_dy == MH_BF16) { SM_B(bf16_t, bf16_t); }

@@ -1610,28 +1610,47 @@ def cast(x: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None
     return y
 
 
-def gelu_fwd(x: torch.Tensor, out_dtype=None) -> torch.Tensor:
+def last_form() -> str:
+    """"<entry>:<form>" of the kernel the calling thread's last elementwise / row-kernel entry point launched (mh_last_form), e.g.
+    "add:scalar", "softmax_fwd:wave,quad", "layernorm_bwd:ws"; "<entry>:none" when the call returned before any launch."""
+    return (_lib.load().mh_last_form() or b"").decode()
+
+
+def _out_like(out: Optional[torch.Tensor], ref: torch.Tensor, dtype, name: str) -> torch.Tensor:
+    """`out` (contiguous, ref's shape) or a fresh tensor of ref's shape."""
+    if out is None:
+        return torch.empty(ref.shape, device=ref.device, dtype=dtype)
+    _chk(out)
+    if out.shape != ref.shape or (dtype is not None and out.dtype != dtype):
+        raise MirrorHipError(f"{name}: out is {tuple(out.shape)} of {out.dtype}, expected {tuple(ref.shape)} of {dtype}")
+    return _contig(out, f"{name} out")
+
+
+def gelu_fwd(x: torch.Tensor, out_dtype=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _chk(x)
     _contig(x, "gelu input")
-    y = torch.empty_like(x, dtype=out_dtype or x.dtype)
+    y = _out_like(out, x, out_dtype or (x.dtype if out is None else out.dtype), "gelu_fwd")
     _lib.call("mh_gelu_fwd", _p(x), _p(y), x.numel(), dt(x), dt(y), stream=_stream())
     return y
 
 
-def gelu_bwd(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
+def gelu_bwd(x: torch.Tensor, dy: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _chk(x, dy)
     dy = _contig(dy, "gelu dy")
-    dx = torch.empty_like(dy)
+    _contig(x, "gelu x")           # the launch walks x.numel() elements of all three tensors
+    if x.numel() != dy.numel():
+        raise MirrorHipError(f"gelu_bwd: x has {x.numel()} elements, dy {dy.numel()}")
+    dx = _out_like(out, dy, dy.dtype, "gelu_bwd")
     _lib.call("mh_gelu_bwd", _p(x), _p(dy), _p(dx), x.numel(), dt(x), dt(dy), dt(dx), stream=_stream())
     return dx
 
 
-def relu_bwd(y: torch.Tensor, dy: torch.Tensor, out_dtype=None) -> torch.Tensor:
+def relu_bwd(y: torch.Tensor, dy: torch.Tensor, out_dtype=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dx = dy * (y > 0).  y / dy: same shape; either contiguous, or 3-D with a contiguous [R, D] block per batch."""
     _chk(y, dy)
     if y.shape != dy.shape:
         raise MirrorHipError("relu_bwd: shape mismatch")
-    dx = torch.empty(y.shape, device=y.device, dtype=out_dtype or dy.dtype)
+    dx = _out_like(out, y, out_dtype or (dy.dtype if out is None else out.dtype), "relu_bwd")
 
     def blk(t):
         if t.is_contiguous():
@@ -1887,14 +1906,20 @@ def loss_terms_bwd(weights, t: dict) -> None:
     _lib.call("mh_loss_terms_bwd", C.byref(_loss_terms_desc(weights, t)), stream=_stream())
 
 
-def fanout_bwd(gfull, x, alpha: float, c, B: int, T: int, D: int) -> torch.Tensor:
+def fanout_bwd(gfull, x, alpha: float, c, B: int, T: int, D: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dE[b,t] = gfull[b,t] + alpha * x[b,t-1] (t >= 1) + (t == 0 ? c[b] : 0); any of the three may be None."""
     ref = next(t for t in (gfull, x, c) if t is not None)
     _chk(*[t for t in (gfull, x, c) if t is not None])
     assert gfull is None or (gfull.is_contiguous() and gfull.dtype == torch.float32 and gfull.numel() == B * T * D)
     assert x is None or (x.is_contiguous() and x.numel() == B * (T - 1) * D)
     assert c is None or (c.is_contiguous() and c.dtype == torch.float32 and c.numel() == B * D)
-    dE = torch.empty((B, T, D), device=ref.device, dtype=torch.float32)
+    if out is None:
+        dE = torch.empty((B, T, D), device=ref.device, dtype=torch.float32)
+    else:
+        _chk(out)
+        if out.dtype != torch.float32 or tuple(out.shape) != (B, T, D):
+            raise MirrorHipError(f"fanout_bwd: out must be f32 [{B}, {T}, {D}], got {out.dtype} {tuple(out.shape)}")
+        dE = _contig(out, "fanout_bwd out")
     _lib.call("mh_fanout_bwd", _p(gfull), _p(x), float(alpha), _p(c), _p(dE), B, T, D, dt(x) if x is not None else _lib.MH_F32,
               stream=_stream())
     return dE
