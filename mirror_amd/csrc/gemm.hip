@@ -7,7 +7,8 @@ bool gemm_try_tile384(GemmArgs& a, int akc, int bkc, int dtC, int batch, void* c
 const char* gemm_big_epi(GemmArgs& a, int akc, int bkc, int dtC, int batch, hipStream_t s);                     // gemm_big.hip
 const char* gemm_big_window(GemmArgs& a, int akc, int bkc, int batch, hipStream_t s);                            // gemm_big.hip
 
-static int launch_one(const mh_gemm_desc* d, hipStream_t s) {
+// tail: the ragged-K remainder mh_gemm offers to this launch's fold pass (null: none); *tail_added: whether a fold added it
+static int launch_one(const mh_gemm_desc* d, hipStream_t s, const GemmTail* tail = nullptr, bool* tail_added = nullptr) {
     const int split = d->split_k < 1 ? 1 : d->split_k;
     GemmArgs a{};
     a.A = d->A; a.B = d->B; a.C = d->C; a.bias = d->bias;
@@ -64,7 +65,10 @@ static int launch_one(const mh_gemm_desc* d, hipStream_t s) {
     }
     MH_REQUIRE(!want_tile, "mh_gemm: C2 / r_bf16 / k_segments / row_softmax need the 192 x 384 tile kernel (bf16 operands, M %% 192 == 0, N %% 384 == 0, K %% 64 == 0, no bias / split-K)");
     if (d->mma == MH_F32) gemm_launch_f32(a, d->a_kc, d->b_kc, batch, s);
-    else if (d->dtA == MH_BF16 && d->dtB == MH_BF16) gemm_launch_bf16(a, d->a_kc, d->b_kc, d->dtC, batch, s);
+    else if (d->dtA == MH_BF16 && d->dtB == MH_BF16) {
+        const bool added = gemm_launch_bf16(a, d->a_kc, d->b_kc, d->dtC, batch, tail, s);
+        if (tail_added) *tail_added = added;
+    }
     else if (d->dtA == MH_F32 && d->dtB == MH_F32) gemm_launch_mixed_ff(a, d->a_kc, d->b_kc, d->dtC, batch, s);
     else if (d->dtA == MH_F32) gemm_launch_mixed_fb(a, d->a_kc, d->b_kc, d->dtC, batch, s);
     else gemm_launch_mixed_bf(a, d->a_kc, d->b_kc, d->dtC, batch, s);
@@ -111,9 +115,8 @@ static bool rank_update_ok(const mh_gemm_desc* t) {
     if ((t->batch1 != 1 && t->batch2 != 1) || (batch > 1 && (t->sC1 != 0 || t->sC2 != 0)) || t->M > 65535 || batch * t->K > 256) return false;
     return true;
 }
-static bool try_rank_update(const mh_gemm_desc* t, hipStream_t s) {
+static void launch_rank_update(const mh_gemm_desc* t, hipStream_t s) {       // the caller checked rank_update_ok(t)
     const int batch = t->batch1 * t->batch2;
-    if (!rank_update_ok(t)) return false;
     const long sA = t->batch1 > 1 ? t->sA1 : t->sA2, sB = t->batch1 > 1 ? t->sB1 : t->sB2;     // the one batch axis in use
     dim3 grid(mh_cdiv(t->N, 256), t->M);
 #define RU_(TA, TB) hipLaunchKernelGGL((rank_update_kernel<TA, TB>), grid, dim3(256), 0, s, (const TA*)t->A, (long)t->lda, sA, (const TB*)t->B, (long)t->ldb, sB, (float*)t->C, (long)t->ldc, t->M, t->N, t->K, batch, t->alpha)
@@ -122,7 +125,6 @@ static bool try_rank_update(const mh_gemm_desc* t, hipStream_t s) {
     else if (t->dtA == MH_F32) RU_(float, bf16_t);
     else RU_(bf16_t, float);
 #undef RU_
-    return true;
 }
 
 extern "C" int64_t mh_gemm_workspace_bytes(const mh_gemm_desc* d) {
@@ -164,24 +166,20 @@ extern "C" int mh_gemm(const mh_gemm_desc* d, mh_stream stream) {
         t.R = nullptr;
         t.accumulate = 1;
         t.split_k = 1;
-        // offer the remainder to the main launch's fold pass (gemm_big.hip: partial tiles + fold): one launch less when it takes it
-        GemmTail* pt = gemm_pending_tail();
-        pt->KT = 0;
-        constexpr bool merge = true;
-        if (merge && m.accumulate && rank_update_ok(&t)) {
-            const int batch_t = t.batch1 * t.batch2;
-            *pt = GemmTail{t.A, t.B, (long)t.lda, t.batch1 > 1 ? (long)t.sA1 : (long)t.sA2, (long)t.ldb, t.batch1 > 1 ? (long)t.sB1 : (long)t.sB2,
-                           t.K, batch_t, t.dtA == MH_F32, t.dtB == MH_F32, t.alpha};
-        }
-        const int rc = launch_one(&m, s);
-        const bool taken = merge && pt->KT == 0 && m.accumulate && rank_update_ok(&t);
-        pt->KT = 0;
+        // a remainder that fits a rank update is offered to the main launch's fold pass (gemm_big.hip: partial tiles + fold): one
+        // launch less when the fold adds it
+        const bool rank = m.accumulate && rank_update_ok(&t);
+        const GemmTail offer{t.A, t.B, (long)t.lda, t.batch1 > 1 ? (long)t.sA1 : (long)t.sA2, (long)t.ldb, t.batch1 > 1 ? (long)t.sB1 : (long)t.sB2,
+                             t.K, t.batch1 * t.batch2, t.dtA == MH_F32, t.dtB == MH_F32, t.alpha};
+        bool folded = false;
+        const int rc = launch_one(&m, s, rank ? &offer : nullptr, &folded);
         if (rc != MH_OK) return rc;
-        if (taken) {
+        if (folded) {
             MH_LAUNCH_CHECK("mh_gemm(tail in fold)");
             return MH_OK;
         }
-        if (m.accumulate && try_rank_update(&t, s)) {
+        if (rank) {
+            launch_rank_update(&t, s);
             MH_LAUNCH_CHECK("mh_gemm(tail)");
             return MH_OK;
         }

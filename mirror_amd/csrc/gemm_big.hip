@@ -14,12 +14,10 @@
 // bf16 launches come from gemm_launch_bf16 (gemm_try_big_bf16: N a multiple of 256, K of 64, M a multiple of 256 or ragged with
 // K-contiguous A rows — loads clamp to the last row, stores are guarded — 16-byte aligned operands, at least 128 workgroups), from the
 // fused-epilogue launches (gemm_big_epi) and from the row-window launches (gemm_big_window).  Split-K reductions into one f32 C go
-// through bf16 partial tiles and fold_partials_kernel when the caller gave a workspace, through f32 atomics otherwise.
+// through bf16 partial tiles and fold_partials_kernel when the caller gave a workspace, through f32 atomics otherwise.  The ragged-K
+// remainder mh_gemm offers (gemm_kernel.h: GemmTail) comes down to the fold as an argument of gemm_try_big_bf16 -> launch_big ->
+// launch_fold, and whether the fold added it goes back up as their result.
 #include "gemm_kernel.h"
-
-// the tail mh_gemm offers to the next fold launch (gemm_kernel.h: GemmTail); host-side state of the calling thread's launch sequence
-static thread_local GemmTail g_tail = {nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0.f};
-GemmTail* gemm_pending_tail() { return &g_tail; }
 
 namespace {
 
@@ -1215,26 +1213,25 @@ __global__ __launch_bounds__(256) void fold_partials_kernel(const bf16_t* __rest
         }
     }
 }
-static void launch_fold(const float* ws_, int parts, long mn, float* C, long ldc, int N, hipStream_t s) {
+// t: the remainder mh_gemm offers (null: none); true when this pass added it
+static bool launch_fold(const float* ws_, int parts, long mn, float* C, long ldc, int N, const GemmTail* t, hipStream_t s) {
 #ifdef MH_EXP
-    if (getenv("MH_EXP_SKIP_FOLD")) { g_tail.KT = 0; return; }      // timing experiment: what the fold passes cost inside the step
+    if (getenv("MH_EXP_SKIP_FOLD")) return t != nullptr;      // timing experiment: what the fold passes cost inside the step
 #endif
     const bf16_t* ws = reinterpret_cast<const bf16_t*>(ws_);
     const long blocks1 = mh_cdiv(mn / 4, 256);
     // the tail's B rows are read as aligned quads of the output's columns: 4-element alignment of its rows and base
-    const bool tail = g_tail.KT > 0 && (g_tail.ldb % 4) == 0 && (g_tail.sB % 4) == 0 && ((uintptr_t)g_tail.B & (g_tail.b_f32 ? 15 : 7)) == 0;
+    const bool tail = t && (t->ldb % 4) == 0 && (t->sB % 4) == 0 && ((uintptr_t)t->B & (t->b_f32 ? 15 : 7)) == 0;
     // four threads per quad where the tail's dependent loads ride along on a small output (measured: 19.3 -> 13.2 us; the plain
     // fold of the same 33 MB is at HBM rate with one thread per quad, 9.1 us, and 1.3 us slower shared)
     const bool share = tail && blocks1 < 1024;
     const dim3 grid((unsigned)min(share ? mh_cdiv(mn / 4, 64) : blocks1, share ? 4096L : 2048L));
-#define FOLD_(TAIL, PS) hipLaunchKernelGGL((fold_partials_kernel<TAIL, PS>), grid, dim3(256), 0, s, ws, parts, mn, C, ldc, N, g_tail)
-    if (tail) {
-        if (share) FOLD_(true, 4); else FOLD_(true, 1);
-        g_tail.KT = 0;
-    } else {
-        FOLD_(false, 1);
-    }
+#define FOLD_(TAIL, PS, T) hipLaunchKernelGGL((fold_partials_kernel<TAIL, PS>), grid, dim3(256), 0, s, ws, parts, mn, C, ldc, N, T)
+    if (share) FOLD_(true, 4, *t);
+    else if (tail) FOLD_(true, 1, *t);
+    else FOLD_(false, 1, GemmTail{});
 #undef FOLD_
+    return tail;
 }
 
 static int pq_grid(long units) {
@@ -1281,8 +1278,9 @@ static void pp_attr(K kern) {
         }                                                                                            \
     } while (0)
 
+// true when the launch reduced through partial tiles and their fold pass added *tail
 template <typename TC>
-void launch_big(GemmArgs& a, int akc, int bkc, int batch, hipStream_t s) {
+bool launch_big(GemmArgs& a, int akc, int bkc, int batch, const GemmTail* tail, hipStream_t s) {
     a.tiles_m = (a.M + BIG - 1) / BIG;     // a ragged last row tile is allowed when A rows are K-contiguous
     a.tiles_n = a.N / BIG;
     dim3 grid(a.tiles_m * a.tiles_n, a.split_k, batch);
@@ -1301,12 +1299,12 @@ void launch_big(GemmArgs& a, int akc, int bkc, int batch, hipStream_t s) {
     if constexpr (sizeof(TC) == 4) {
         if (partial) {
             PP_DISPATCH_(true);
-            launch_fold((const float*)a.ws, (int)parts, mn, (float*)a.C, (long)a.ldc, a.N, s);
-            return;
+            return launch_fold((const float*)a.ws, (int)parts, mn, (float*)a.C, (long)a.ldc, a.N, tail, s);
         }
     }
     PP_DISPATCH_(false);
 #undef PP_DISPATCH_
+    return false;
 }
 
 }  // namespace
@@ -1375,8 +1373,8 @@ const char* gemm_big_window(GemmArgs& a, int akc, int bkc, int batch, hipStream_
     return nullptr;
 }
 
-// true when the large-tile kernel took the launch
-bool gemm_try_big_bf16(GemmArgs& a, int akc, int bkc, int dtC, int batch, hipStream_t s) {
+// true when the large-tile kernel took the launch; then *tail_added says whether its fold pass added *tail (null: none offered)
+bool gemm_try_big_bf16(GemmArgs& a, int akc, int bkc, int dtC, int batch, const GemmTail* tail, bool* tail_added, hipStream_t s) {
     const bool shape_ok = (a.M % BIG == 0 || (akc && a.M > BIG)) && a.N % BIG == 0 && a.K % 64 == 0 && a.k_per_split % 64 == 0;
     if (!shape_ok || !a.vecA || !a.vecB || !a.vecC || a.R || a.diag != 0.f) return false;
     if (a.atomic && (a.bias || a.act != MH_ACT_NONE || dtC != MH_F32)) return false;
@@ -1385,7 +1383,6 @@ bool gemm_try_big_bf16(GemmArgs& a, int akc, int bkc, int dtC, int batch, hipStr
     if (dtC == MH_BF16 && a.accumulate) return false;
     const long wgs = (long)((a.M + BIG - 1) / BIG) * (a.N / BIG) * a.split_k * batch;
     if (wgs < 128) return false;            // too few workgroups for one per CU: the 128 x 128 kernel spreads better
-    if (dtC == MH_BF16) launch_big<bf16_t>(a, akc, bkc, batch, s);
-    else launch_big<float>(a, akc, bkc, batch, s);
+    *tail_added = dtC == MH_BF16 ? launch_big<bf16_t>(a, akc, bkc, batch, tail, s) : launch_big<float>(a, akc, bkc, batch, tail, s);
     return true;
 }

@@ -25,7 +25,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // The K % 64 remainder of a weight gradient (one row per slide: B x 4097 rows) as a rank-(batch x KT) update: when the main launch
 // reduces through partial tiles + a fold pass, the fold adds it (C[m][n] += alpha sum_{z, k < KT} A_z[k][m] B_z[k][n], both operands
-// with the contraction index as their row) instead of a launch of its own (gemm.hip: try_rank_update).
+// with the contraction index as their row) instead of a launch of its own (gemm.hip: launch_rank_update).  mh_gemm builds it on
+// its stack and hands a pointer down the bf16 launch path (null: nothing offered); whether a fold added it comes back the same way.
 struct GemmTail {
     const void* A; const void* B;
     long lda, sA, ldb, sB;
@@ -35,7 +36,6 @@ struct GemmTail {
 void gemm_note_variant(const char* fmt, ...);      // errors.cpp: names the instance a launch site picked (mh_gemm_variant_name)
 template <typename T> inline const char* gemm_tn() { return sizeof(T) == 4 ? "float" : "bf16"; }
 inline const char* gemm_tf(bool b) { return b ? "true" : "false"; }
-GemmTail* gemm_pending_tail();       // the tail mh_gemm offers to the next fold launch (KT == 0: none); the fold clears it when it takes it
 
 struct GemmArgs {
     const void* A; const void* B; void* C; const float* bias;
@@ -475,7 +475,7 @@ static void launch_l(GemmArgs& a, int akc, int bkc, int batch, hipStream_t s) {
 
 // family entry points (one translation unit each)
 void gemm_launch_f32(GemmArgs& a, int akc, int bkc, int batch, hipStream_t s);                 // MMA f32
-void gemm_launch_bf16(GemmArgs& a, int akc, int bkc, int dtC, int batch, hipStream_t s);       // bf16 operands
+bool gemm_launch_bf16(GemmArgs& a, int akc, int bkc, int dtC, int batch, const GemmTail* tail, hipStream_t s);   // bf16 operands; true: a fold pass added *tail
 void gemm_launch_mixed_ff(GemmArgs& a, int akc, int bkc, int dtC, int batch, hipStream_t s);   // f32 x f32 operands, bf16 MMA
 void gemm_launch_mixed_fb(GemmArgs& a, int akc, int bkc, int dtC, int batch, hipStream_t s);   // f32 A, bf16 B
 void gemm_launch_mixed_bf(GemmArgs& a, int akc, int bkc, int dtC, int batch, hipStream_t s);   // bf16 A, f32 B

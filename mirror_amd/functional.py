@@ -2108,67 +2108,66 @@ class NystromCoreFn(Function):
                     K.pinv_chain_fwd(xt, chain_saved, zfT, iters)
             saved = [(xt, chain_saved, z0 if z0 is not None else st)]      # (no stored f32 z_0 on the one-launch path: a placeholder)
             ctx.z0_stored = z0 is not None
-            K.shared_chip = True         # until the join below: no persistent GEMM kernel beside the half-chip chain
-        tile = (not chain) and pm == MH_BF16 and K.gemm_tile_ok(m_l, m_l, m_l)
-        if tile and _TILE_SIDE:
-            # the template's m = 384: the iteration is 24 dependent one-round launches (~36 us each, half of that fixed cost) that need
-            # attn2 only — they run on the side stream beside sim1 / sim3, their softmax and attn3 v, and meet them at w2 (round 5)
-            side = _side_stream(qkv.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
+        # until the join at the block's end: no persistent GEMM kernel beside the half-chip chain
+        with K.chip_shared() if chain else contextlib.nullcontext():
+            tile = (not chain) and pm == MH_BF16 and K.gemm_tile_ok(m_l, m_l, m_l)
+            if tile and _TILE_SIDE:
+                # the template's m = 384: the iteration is 24 dependent one-round launches (~36 us each, half of that fixed cost) that need
+                # attn2 only — they run on the side stream beside sim1 / sim3, their softmax and attn3 v, and meet them at w2 (round 5)
+                side = _side_stream(qkv.device)
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    zf, saved, st, ctx.a2b = pinv_forward_tile(a2, iters, want_a2b=True)
+            if link is not None:
+                link.core = True
+                link.run("v_cols")       # the v columns of to_qkv: nothing above reads them (landmarks are means of q and k)
+            fused = K.nys_fused_ok(qkv, h, m_l) and lm.dtype == bf16      # nystrom_fused.hip: sim1 / sim3 never reach HBM (mask-aware)
+            lse1 = lse3 = a1 = a3 = None
+            out = torch.empty((Bn, n_p, D), device=qkv.device, dtype=A)
+            rc_in_a3 = fused and _RC_FUSED and A == bf16 and res_w.numel() == h * 33
+            if fused:
+                # res_conv(v) rides on attn3's forward (it stages the v tiles anyway): no launch of its own, no second read of v
+                av, lse3 = K.nys_attn3_fwd(qkv, lm, h, scale, kmask,
+                                           rc=(res_w.detach().reshape(-1).contiguous(), out) if rc_in_a3 else None)   # [B,h,m,dh] f32
+            else:
+                # sim1's rows (length m) fit one 192 x 384 tile at the template's m = 384: the softmax runs in that GEMM's epilogue
+                sm1 = (kmask is None and A == bf16 and mma == MH_BF16 and q.dtype == bf16
+                       and K.gemm_softmax_ok(n_p, lm.shape[1], dh, q.dtype, kl.dtype))
+                if sm1:
+                    a1 = K.gemm(q, kl.transpose(-1, -2), alpha=scale, mma=mma, out_dtype=bf16, softmax=True)   # [B,h,n_p,m]
+                else:
+                    a1 = K.gemm(q, kl.transpose(-1, -2), alpha=scale, mma=mma, out_dtype=f32)
+                a3 = K.gemm(ql, k.transpose(-1, -2), alpha=scale, mma=mma, out_dtype=f32)   # [B,h,m,n_p]
+                if kmask is None:
+                    if not sm1:
+                        a1 = K.softmax_fwd(a1, a1 if A == f32 else None, out_dtype=A)
+                    a3 = K.softmax_fwd(a3, a3 if A == f32 else None, out_dtype=A)
+                else:
+                    a1 = K.softmax_masked_fwd(a1, mrow, mlm, a1 if A == f32 else None, out_dtype=A)
+                    a3 = K.softmax_masked_fwd(a3, mlm, mrow, a3 if A == f32 else None, out_dtype=A)
+            if tile and not _TILE_SIDE:
                 zf, saved, st, ctx.a2b = pinv_forward_tile(a2, iters, want_a2b=True)
-        if link is not None:
-            link.core = True
-            link.run("v_cols")       # the v columns of to_qkv: nothing above reads them (landmarks are means of q and k)
-        fused = K.nys_fused_ok(qkv, h, m_l) and lm.dtype == bf16      # nystrom_fused.hip: sim1 / sim3 never reach HBM (mask-aware)
-        lse1 = lse3 = a1 = a3 = None
-        out = torch.empty((Bn, n_p, D), device=qkv.device, dtype=A)
-        rc_in_a3 = fused and _RC_FUSED and A == bf16 and res_w.numel() == h * 33
-        if fused:
-            # res_conv(v) rides on attn3's forward (it stages the v tiles anyway): no launch of its own, no second read of v
-            av, lse3 = K.nys_attn3_fwd(qkv, lm, h, scale, kmask,
-                                       rc=(res_w.detach().reshape(-1).contiguous(), out) if rc_in_a3 else None)   # [B,h,m,dh] f32
-        else:
-            # sim1's rows (length m) fit one 192 x 384 tile at the template's m = 384: the softmax runs in that GEMM's epilogue
-            sm1 = (kmask is None and A == bf16 and mma == MH_BF16 and q.dtype == bf16
-                   and K.gemm_softmax_ok(n_p, lm.shape[1], dh, q.dtype, kl.dtype))
-            if sm1:
-                a1 = K.gemm(q, kl.transpose(-1, -2), alpha=scale, mma=mma, out_dtype=bf16, softmax=True)   # [B,h,n_p,m]
-            else:
-                a1 = K.gemm(q, kl.transpose(-1, -2), alpha=scale, mma=mma, out_dtype=f32)
-            a3 = K.gemm(ql, k.transpose(-1, -2), alpha=scale, mma=mma, out_dtype=f32)   # [B,h,m,n_p]
-            if kmask is None:
-                if not sm1:
-                    a1 = K.softmax_fwd(a1, a1 if A == f32 else None, out_dtype=A)
-                a3 = K.softmax_fwd(a3, a3 if A == f32 else None, out_dtype=A)
-            else:
-                a1 = K.softmax_masked_fwd(a1, mrow, mlm, a1 if A == f32 else None, out_dtype=A)
-                a3 = K.softmax_masked_fwd(a3, mlm, mrow, a3 if A == f32 else None, out_dtype=A)
-        if tile and not _TILE_SIDE:
-            zf, saved, st, ctx.a2b = pinv_forward_tile(a2, iters, want_a2b=True)
-        elif not chain and not tile:
-            zf, saved, st = pinv_forward(a2, iters, pm, sd)
-        if not fused:
-            av = K.gemm(a3, v, mma=mma, out_dtype=f32)                                   # [B,h,m,dh]
-        # GEMMs that meet activation-dtype tensors cannot use the exact-f32 MFMA unless the activations are f32 too
-        pio = pm if (pm == MH_BF16 or A == f32) else mma
-        w2 = None
-        if side is not None and fused:
-            # w2 = pinv(attn2) (attn3 v) is a [256 x 256] x [256 x 64] product per (b, h): ~11 us of launch that stood alone behind the
-            # join.  av is complete here (the main side of the window is past attn3), the pseudo-inverse when the chain's stream gets to
-            # it: the product goes to the END of the chain's branch, beside res_conv on the main side, and the join covers it
-            # (-0.22 % +- 0.06).
-            w2 = torch.empty((Bn, h, m_l, dh), device=qkv.device, dtype=A)
-            av_ready = torch.cuda.current_stream().record_event()
-            with torch.cuda.stream(side):
-                side.wait_event(av_ready)
-                K.gemm(zf, av, out=w2, mma=pio)
-        if fused and not rc_in_a3:   # res_conv(v) does not need the pseudo-inverse: it runs under the chain, attn1 then adds to it
-            K.resconv(qkv[..., 2 * D:], res_w.detach().contiguous(), out, h, transpose=False, accumulate=False)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-            if chain:
-                K.shared_chip = False
+            elif not chain and not tile:
+                zf, saved, st = pinv_forward(a2, iters, pm, sd)
+            if not fused:
+                av = K.gemm(a3, v, mma=mma, out_dtype=f32)                                   # [B,h,m,dh]
+            # GEMMs that meet activation-dtype tensors cannot use the exact-f32 MFMA unless the activations are f32 too
+            pio = pm if (pm == MH_BF16 or A == f32) else mma
+            w2 = None
+            if side is not None and fused:
+                # w2 = pinv(attn2) (attn3 v) is a [256 x 256] x [256 x 64] product per (b, h): ~11 us of launch that stood alone behind the
+                # join.  av is complete here (the main side of the window is past attn3), the pseudo-inverse when the chain's stream gets to
+                # it: the product goes to the END of the chain's branch, beside res_conv on the main side, and the join covers it
+                # (-0.22 % +- 0.06).
+                w2 = torch.empty((Bn, h, m_l, dh), device=qkv.device, dtype=A)
+                av_ready = torch.cuda.current_stream().record_event()
+                with torch.cuda.stream(side):
+                    side.wait_event(av_ready)
+                    K.gemm(zf, av, out=w2, mma=pio)
+            if fused and not rc_in_a3:   # res_conv(v) does not need the pseudo-inverse: it runs under the chain, attn1 then adds to it
+                K.resconv(qkv[..., 2 * D:], res_w.detach().contiguous(), out, h, transpose=False, accumulate=False)
+            if side is not None:
+                torch.cuda.current_stream().wait_stream(side)
         if w2 is None:
             w2 = K.gemm(zf, av, mma=pio, out_dtype=A)
         o1 = None
@@ -2291,51 +2290,50 @@ class NystromCoreFn(Function):
                 if dlm2 is not None:
                     K.gemm(tr(dS2), ql, out=_heads(dlm2, 1, 2, h), alpha=scale, mma=pio)
                     K.gemm(dS2, kl, out=_heads(dlm2, 0, 2, h), alpha=scale, mma=pio)
-            K.shared_chip = True         # until the join below
-        tile_side = ctx.tile and _TILE_SIDE and not chain
-        if tile_side:      # the 54 launches of the m = 384 iteration's backward beside the attention sides' gradient products
-            dZ_ready = torch.cuda.current_stream().record_event()
-            side = _side_stream(qkv.device)
-            with torch.cuda.stream(side):
-                side.wait_event(dZ_ready)
-                dS2 = pinv_backward_tile(a2, saved, st, dZ, getattr(ctx, "a2b", None))
-                sm_bwd(a2, dS2, mlm if kmask else None, mlm if kmask else None)
-        if ctx.link is not None:
-            ctx.link.run("wgrad")      # to_out's weight gradient (ToOutDropAddFn left it to us): beside the chain when there is one
-        rc_bwd_one = fused and _RC_FUSED and A == bf16      # both res_conv gradients in ONE pass over dout, behind attn3's backward
-        if not rc_bwd_one:
-            K.resconv_wgrad(qkv[..., 2 * D:], dout, dres, h)
-        if dAV is None:
-            dAV = K.gemm(tr(zf), dW2, mma=pio, out_dtype=A)                              # [B,h,m,dh]
-        if fused:
-            K.nys_attn3_bwd(qkv, lm, av, dAV, lse3, dqkv, dlm, h, scale, kmask)          # dk, dv, dq_l
-            if rc_bwd_one:
-                K.resconv_bwd(dout, qkv[..., 2 * D:], rw, dqkv[..., 2 * D:], dres, h)
+        # until the join at the block's end: no persistent GEMM kernel beside the half-chip chain
+        with K.chip_shared() if chain else contextlib.nullcontext():
+            tile_side = ctx.tile and _TILE_SIDE and not chain
+            if tile_side:      # the 54 launches of the m = 384 iteration's backward beside the attention sides' gradient products
+                dZ_ready = torch.cuda.current_stream().record_event()
+                side = _side_stream(qkv.device)
+                with torch.cuda.stream(side):
+                    side.wait_event(dZ_ready)
+                    dS2 = pinv_backward_tile(a2, saved, st, dZ, getattr(ctx, "a2b", None))
+                    sm_bwd(a2, dS2, mlm if kmask else None, mlm if kmask else None)
+            if ctx.link is not None:
+                ctx.link.run("wgrad")      # to_out's weight gradient (ToOutDropAddFn left it to us): beside the chain when there is one
+            rc_bwd_one = fused and _RC_FUSED and A == bf16      # both res_conv gradients in ONE pass over dout, behind attn3's backward
+            if not rc_bwd_one:
+                K.resconv_wgrad(qkv[..., 2 * D:], dout, dres, h)
+            if dAV is None:
+                dAV = K.gemm(tr(zf), dW2, mma=pio, out_dtype=A)                              # [B,h,m,dh]
+            if fused:
+                K.nys_attn3_bwd(qkv, lm, av, dAV, lse3, dqkv, dlm, h, scale, kmask)          # dk, dv, dq_l
+                if rc_bwd_one:
+                    K.resconv_bwd(dout, qkv[..., 2 * D:], rw, dqkv[..., 2 * D:], dres, h)
+                else:
+                    K.resconv(dout, rw, dqkv[..., 2 * D:], h, transpose=True, accumulate=True)
             else:
+                if (kmask is None and A == bf16 and mma == MH_BF16 and a1.dtype == bf16 and a1.is_contiguous()
+                        and K.gemm_softmax_ok(n_p, m, dh, dO.dtype, w2.dtype)):
+                    dS1 = K.gemm(dO, tr(w2), mma=mma, out_dtype=bf16, softmax_bwd_of=a1)    # softmax backward in the epilogue
+                else:
+                    dS1 = K.gemm(dO, tr(w2), mma=mma, out_dtype=A)                           # [B,h,n_p,m]
+                    sm_bwd(a1, dS1, mrow if kmask else None, mlm if kmask else None)
+                dS3 = K.gemm(dAV, tr(v), mma=mma, out_dtype=A)                               # [B,h,m,n_p]
+                K.gemm(tr(a3), dAV, out=dv, mma=mma)
                 K.resconv(dout, rw, dqkv[..., 2 * D:], h, transpose=True, accumulate=True)
-        else:
-            if (kmask is None and A == bf16 and mma == MH_BF16 and a1.dtype == bf16 and a1.is_contiguous()
-                    and K.gemm_softmax_ok(n_p, m, dh, dO.dtype, w2.dtype)):
-                dS1 = K.gemm(dO, tr(w2), mma=mma, out_dtype=bf16, softmax_bwd_of=a1)    # softmax backward in the epilogue
-            else:
-                dS1 = K.gemm(dO, tr(w2), mma=mma, out_dtype=A)                           # [B,h,n_p,m]
-                sm_bwd(a1, dS1, mrow if kmask else None, mlm if kmask else None)
-            dS3 = K.gemm(dAV, tr(v), mma=mma, out_dtype=A)                               # [B,h,m,n_p]
-            K.gemm(tr(a3), dAV, out=dv, mma=mma)
-            K.resconv(dout, rw, dqkv[..., 2 * D:], h, transpose=True, accumulate=True)
-            sm_bwd(a3, dS3, mlm if kmask else None, mrow if kmask else None)
-            # similarities: s1 = scale q kl^T, s2 = scale ql kl^T, s3 = scale ql k^T
-            K.gemm(dS1, kl, out=dq, alpha=scale, mma=mma)
-            K.gemm(tr(dS3), ql, out=dk, alpha=scale, mma=mma)
-            K.gemm(tr(dS1), q, out=dkl, alpha=scale, mma=mma)
-            K.gemm(dS3, k, out=dql, alpha=scale, mma=mma)
-        if tile_side:
-            torch.cuda.current_stream().wait_stream(side)
-        elif side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-            K.shared_chip = False
+                sm_bwd(a3, dS3, mlm if kmask else None, mrow if kmask else None)
+                # similarities: s1 = scale q kl^T, s2 = scale ql kl^T, s3 = scale ql k^T
+                K.gemm(dS1, kl, out=dq, alpha=scale, mma=mma)
+                K.gemm(tr(dS3), ql, out=dk, alpha=scale, mma=mma)
+                K.gemm(tr(dS1), q, out=dkl, alpha=scale, mma=mma)
+                K.gemm(dS3, k, out=dql, alpha=scale, mma=mma)
+            if side is not None:         # the chain's or the tile iteration's side stream
+                torch.cuda.current_stream().wait_stream(side)
+        if chain:
             del work
-        else:
+        elif not tile_side:
             dS2 = pinv_backward_tile(a2, saved, st, dZ, getattr(ctx, "a2b", None)) if ctx.tile else pinv_backward(a2, saved, st, dZ, pm, sd)
             sm_bwd(a2, dS2, mlm if kmask else None, mlm if kmask else None)
         if dlm2 is None:

@@ -5,6 +5,7 @@ node down) and launches on torch's current stream.  There is no CPU / PyTorch fa
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import functools
 import os
@@ -179,9 +180,20 @@ def gemm(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, *
     return out
 
 
-# set (by functional.NystromCoreFn) while the half-chip pinv chain runs on its side stream: launches issued meanwhile must not
-# use the persistent GEMM kernel (mh_gemm_desc.shared_chip)
+# set (by functional.NystromCoreFn, through chip_shared) while the half-chip pinv chain runs on its side stream: launches issued
+# meanwhile must not use the persistent GEMM kernel (mh_gemm_desc.shared_chip)
 shared_chip = False
+
+
+@contextlib.contextmanager
+def chip_shared(on: bool = True):
+    """shared_chip = on inside the block; on every way out of it (an exception included) the value it had before."""
+    global shared_chip
+    prev, shared_chip = shared_chip, on
+    try:
+        yield
+    finally:
+        shared_chip = prev
 
 
 EPI_DROPADD, EPI_MASKPOS, EPI_SQERR = 1, 2, 3

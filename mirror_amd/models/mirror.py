@@ -567,7 +567,6 @@ class MIRROR(nn.Module):
         noise = dict(noise or {})
         if not wsi_emb.is_cuda:
             raise MirrorHipError("mirror_amd models run on MI355X only (no CPU fallback): move the inputs to the GPU")
-        Fn.K.shared_chip = False   # a forward that raised between a chain fork and its join must not leave the hint set
         # the reference draws: rand(B,N) -> rand(B,D) -> eps_wsi -> eps_rna (models/mirror.py:630, :516, :832-833);
         # draw them up front in that order so the two encoders can then run on different streams
         B, dev = wsi_emb.shape[0], wsi_emb.device

@@ -675,11 +675,8 @@ def test_rows_window_product_skips_the_front_pad_rows(B, T, R, Kd, N, kc, beside
         b2, wt = w, w.t().contiguous()
     out = torch.full((B, T, N + 256), 7.0, device="cuda", dtype=bf16)
     o3 = out[..., :N]
-    K.shared_chip = beside_chain            # the one-workgroup-per-tile kernel instead of the persistent one
-    try:
+    with K.chip_shared(beside_chain):       # the one-workgroup-per-tile kernel instead of the persistent one
         Fn._rows_window(a, b2, o3, r0, R, mma=MH_BF16, wt=wt)
-    finally:
-        K.shared_chip = False
     torch.cuda.synchronize()
     ref = (a[:, r0:].float() @ b2.float())
     assert float((o3[:, r0:].float() - ref).abs().max()) <= 1e-2 * float(ref.abs().max())

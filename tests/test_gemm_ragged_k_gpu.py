@@ -86,8 +86,9 @@ def test_fold_with_tail_on_random_bf16_data_against_f64(c, monkeypatch):
 
 
 def test_no_tail_outlives_its_call(monkeypatch):
-    """The offered tail is host state of the calling thread (csrc/gemm_big.hip: g_tail).  Left behind by a call whose main launch
-    did not fold, by one whose fold took it, or by a refused call, it would be added silently to the next folded product."""
+    """The offered tail is an argument of its own call (csrc/gemm.hip: mh_gemm hands a GemmTail on its stack down to launch_fold), not
+    state that a later call could meet.  If one outlived a call whose main launch did not fold, one whose fold took it, or a refused
+    call, it would be added silently to the next folded product."""
     ra, f4 = G.by_id("RA"), G.by_id("F4-t16-a1.0")
     plain = G.Case("F4-t0", f4.M, f4.N, f4.kmain, 0, f4.split_k, 1, "fold", alpha=1.0)
     pd = G.integer_case(f4, seed=7)

@@ -174,6 +174,26 @@ def test_no_cpu_fallback():
         InfoNCE()(torch.randn(4, 3), torch.randn(4, 3))
 
 
+def test_chip_shared_hint_is_scoped():
+    """kernels.chip_shared sets kernels.shared_chip inside its block only: the value from before is back after a body that raised,
+    and after a nested use it is the outer block's value, not False."""
+    assert K.shared_chip is False
+    with pytest.raises(RuntimeError):
+        with K.chip_shared():
+            assert K.shared_chip is True
+            raise RuntimeError("between the fork and the join")
+    assert K.shared_chip is False
+    K.shared_chip = True            # still a plain attribute (tools/bench_gemm_pp.py assigns it)
+    try:
+        with K.chip_shared():
+            with K.chip_shared(False):
+                assert K.shared_chip is False
+            assert K.shared_chip is True
+        assert K.shared_chip is True
+    finally:
+        K.shared_chip = False
+
+
 def test_operand_views_map_to_strides():
     B, n, h, dh = 2, 12, 4, 8
     qkv = torch.zeros(B, n, 3 * h * dh)
