@@ -1245,6 +1245,45 @@ int64_t mh_kmeanspp_workspace_bytes(int64_t n, int R);
  * K C <= 65536, 1 <= R <= 2^20. */
 int mh_cluster_match(const int32_t* cont, int R, int K, int C, int32_t* match, int64_t* hits, mh_stream s);
 
+/* ---------------------------------------------------------------- linear probe of frozen embeddings (csrc/linprobe.hip;
+ * mirror_amd/linprobe.py; the reference's train_subtyping.py --linear_probe over the folds of tools/gen_splits.py, with the frozen
+ * encoder taken out of the loop).  J independent L2-regularised softmax regressions over the SAME prepared rows y [n x D] f32
+ * contiguous (the folds x strengths in the role of the few-shot episodes); per job j
+ *   F_j(W, b) = r_j sum_{i in train_j} CE(softmax(W y_i + b), label_i) + (lambda_j / 2) |W|^2     (the bias is not penalised)
+ *   train_j   = { i : label_i in [0, C), fold_i >= 0, fold_i != heldout_j }                        (heldout_j = -1: every valid row)
+ * and one FISTA iteration is the two launches below.  Layout as mh_fewshot_protos: Cp = the next power of two >= C, weights f32
+ * [J x Cp x D], bias f32 [J x Cp], pad slots c >= C hold weight 0 and bias -inf (the caller sets them; neither entry point writes
+ * them), so that a job's keys never straddle a 128-key tile.  Both are deterministic (fixed summation order, no float atomics),
+ * allocate nothing and never wait on the host.  Shared limits: 2 <= C <= 64, 1 <= D <= 4096, 1 <= n <= 2^20, J Cp <= 2^20,
+ * n J Cp <= 2^28.
+ *
+ * G f32 [n x J Cp], STORED (nothing to zero): G[i, j Cp + c] = r_j (p_c - [c = label_i]) for i in train_j and c < C, p = softmax of
+ * v_c = dot(y_i, Wz[j, c]) + bz[j, c]; 0 for every other row and for pad columns.  The dot product is the k-ordered f32 fmaf chain
+ * from 0 of the retrieval kernels (v_mfma_f32_32x32x2_f32 over the J Cp weight rows as keys), the bias ONE f32 add; then in class
+ * order in f32: m = max_c v_c, lse = m + logf(sum_c expf(v_c - m)), p_c = expf(v_c - lse).  labels int64 [n] (8-byte aligned), fold
+ * int32 [n], heldout int32 [J], rscale f32 [J] (r_j).  loss_part f64 [ceil(n / 128) x J] (8-byte aligned) or NULL:
+ * loss_part[t, j] = r_j sum of CE_i = lse - v_label (f32) over the training rows of row tile t, added in row order in f64; their sum
+ * over t is the data term of F_j at (Wz, bz), without the regulariser.  A NaN in a row makes the G rows and the loss of every job that
+ * trains on it NaN (and, through the step, that job's weights): nothing is filtered.  Grid ceil(n / 128) x ceil(J Cp / 128); the tile
+ * goes through LDS in two halves behind the product and one thread owns each (row, job).
+ * (n + J Cp) D 4 bytes read per tile row / column, n J Cp 4 written. */
+int mh_linprobe_grad(const float* y, int64_t n, int D, const float* Wz, const float* bz, const int64_t* labels, const int32_t* fold,
+                     const int32_t* heldout, const float* rscale, int J, int C, int Cp, float* G, double* loss_part, mh_stream s);
+/* The weight gradient at the look-ahead point and the FISTA update, in place:
+ *   dW[j, c, d] = sum_i G[i, j Cp + c] y[i, d] + lambda_j Wz[j, c, d]          db[j, c] = sum_i G[i, j Cp + c]
+ *   X' = Z - eta_j g,   Z' = X' + beta (X' - X)          over Wx, Wz f32 [J x Cp x D] and bx, bz f32 [J x Cp]
+ * The sums over i are ONE f32 fmaf chain from 0 per element in ascending row order i = 0 .. n - 1 (v_mfma_f32_32x32x2_f32 contracting
+ * over the rows; rows past n enter as fmaf(0, 0, acc) = acc); db is column D of the same product against a column of ones formed in
+ * the load.  Then g = fmaf(lambda_j, Z, sum) (bias: g = sum), X' = fmaf(-eta_j, g, Z), Z' = fmaf(beta, X' - X, X'), each rounded
+ * once.  One workgroup owns a 128 (key) x 128 (column) tile of [J Cp x (D + 1)] and walks all n rows: no split over n, every
+ * element has exactly one owner.  Pad slots are skipped outright: they are neither read nor written.  lam, eta f32 [J];
+ * 0 <= beta <= 1.  gmax_part f32 [ceil((D + 1) / 128) x J], STORED, or NULL: gmax_part[t, j] = max |g| over job j's weights in
+ * column tile t (the bias belongs to the tile of column D); the maximum over t is job j's gradient in the max norm, NaN if any of
+ * its elements is NaN.  Grid ceil(J Cp / 128) x ceil((D + 1) / 128).
+ * n (J Cp + D) 4 bytes read per tile, 4 J C (D + 1) 4 bytes read and written. */
+int mh_linprobe_step(const float* y, int64_t n, int D, const float* G, float* Wx, float* bx, float* Wz, float* bz, const float* lam,
+                     const float* eta, float beta, int J, int C, int Cp, float* gmax_part, mh_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -263,6 +263,8 @@ _SIGS = {
     "mh_silhouette": [P, P, L, I, I, I, I, P, P, P, P],
     "mh_kmeanspp_init": [P, L, I, I, I, U64, U64, P, P, P],
     "mh_cluster_match": [P, I, I, I, P, P],
+    "mh_linprobe_grad": [P, L, I, P, P, P, P, P, P, I, I, I, P, P],
+    "mh_linprobe_step": [P, L, I, P, P, P, P, P, P, P, F, I, I, I, P],
 }
 EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "mh_gemm_variant_name", "mh_note_form", "mh_last_form", "mh_device_ok", "mh_nys_attn3_ws_floats", "mh_rna_block_workspace_bytes",
                                  "mh_rna_block_lds_bytes", "mh_rna_block_fits",

@@ -2789,6 +2789,90 @@ def fewshot_tally(pred: torch.Tensor, labels: torch.Tensor, C: int):
     return conf, bad, summary
 
 
+# ----------------------------------------------------------------------------- linear probe: J softmax regressions at once (csrc/linprobe.hip)
+def _lp_state(y: torch.Tensor, W: torch.Tensor, b: torch.Tensor, C: int, who: str):
+    """(n, D, J, Cp) of prepared rows y f32 [n, D] and padded weights W f32 [J, Cp, D], b f32 [J, Cp], inside the limits the two entry
+    points share."""
+    y = _fs_f32(y, f"{who}: y", device=False)
+    n, D = y.shape
+    if isinstance(C, bool) or not isinstance(C, int) or not (2 <= C <= 64):
+        raise ValueError(f"{who}: C must be an int in [2, 64], got {C!r}")
+    Cp = fewshot_cp(C)
+    if not isinstance(W, torch.Tensor) or W.dtype != torch.float32 or W.dim() != 3 or tuple(W.shape[1:]) != (Cp, D):
+        raise ValueError(f"{who}: the weights must be f32 [J, {Cp}, {D}]")
+    J = W.shape[0]
+    if not isinstance(b, torch.Tensor) or b.dtype != torch.float32 or tuple(b.shape) != (J, Cp):
+        raise ValueError(f"{who}: the bias must be f32 [{J}, {Cp}]")
+    _chk(y, W, b)
+    if not (1 <= J and J * Cp <= (1 << 20)) or n * J * Cp > (1 << 28):
+        raise MirrorHipError(f"{who}: J = {J} jobs of {Cp} keys over n = {n} rows (J * Cp <= 2^20, n * J * Cp <= 2^28)")
+    _contig(W, f"{who}: the weights")
+    _contig(b, f"{who}: the bias")
+    return y, n, D, J, Cp
+
+
+def _lp_vec(t, dtype, J: int, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (J,):
+        raise ValueError(f"{what} must be {dtype} [{J}]")
+    _chk(t)
+    return t.contiguous()
+
+
+def linprobe_grad(y: torch.Tensor, Wz: torch.Tensor, bz: torch.Tensor, labels: torch.Tensor, fold: torch.Tensor, heldout: torch.Tensor,
+                  rscale: torch.Tensor, C: int, G: Optional[torch.Tensor] = None, want_loss: bool = False):
+    """(G f32 [n, J Cp], loss_part f64 [ceil(n / 128), J] or None) on the device (no sync): every job's logit gradient
+    r_j (softmax(Wz y_i + bz) - onehot(label_i)) over its training rows (label in [0, C), fold >= 0, fold != heldout_j), 0 elsewhere
+    and in the pad columns (mh_linprobe_grad).  G may be passed to be overwritten; want_loss asks for the per-row-tile data terms."""
+    y, n, D, J, Cp = _lp_state(y, Wz, bz, C, "linprobe_grad")
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or tuple(labels.shape) != (n,):
+        raise ValueError(f"linprobe_grad: labels must be int64 [{n}]")
+    if not isinstance(fold, torch.Tensor) or fold.dtype != torch.int32 or tuple(fold.shape) != (n,):
+        raise ValueError(f"linprobe_grad: fold must be int32 [{n}]")
+    _chk(labels, fold)
+    heldout = _lp_vec(heldout, torch.int32, J, "linprobe_grad: heldout")
+    rscale = _lp_vec(rscale, torch.float32, J, "linprobe_grad: rscale")
+    tiles = (n + 127) // 128
+    if G is None:
+        G = torch.empty((n, J * Cp), device=y.device, dtype=torch.float32)
+    elif not isinstance(G, torch.Tensor) or G.dtype != torch.float32 or tuple(G.shape) != (n, J * Cp) or not G.is_contiguous():
+        raise ValueError(f"linprobe_grad: G must be a contiguous f32 [{n}, {J * Cp}]")
+    _chk(G)
+    loss_part = torch.empty((tiles, J), device=y.device, dtype=torch.float64) if want_loss else None
+    _lib.call("mh_linprobe_grad", _p(y), n, D, _p(Wz), _p(bz), _p(labels.contiguous()), _p(fold.contiguous()), _p(heldout), _p(rscale),
+              J, C, Cp, _p(G), _p(loss_part), stream=_stream())
+    return G, loss_part
+
+
+def linprobe_step(y: torch.Tensor, G: torch.Tensor, Wx: torch.Tensor, bx: torch.Tensor, Wz: torch.Tensor, bz: torch.Tensor,
+                  lam: torch.Tensor, eta: torch.Tensor, beta: float, C: int, gmax_part: Optional[torch.Tensor] = None,
+                  want_gmax: bool = False):
+    """One FISTA update of every job IN PLACE (no sync): g = G^T [y, 1] + lam_j Wz (the bias unpenalised), X' = Wz - eta_j g,
+    Z' = X' + beta (X' - Wx), stored over Wx / bx and Wz / bz; pad slots untouched (mh_linprobe_step: one row-ordered f32 chain per
+    element).  Returns gmax_part f32 [ceil((D + 1) / 128), J] (max |g| per column tile and job) or None."""
+    y, n, D, J, Cp = _lp_state(y, Wz, bz, C, "linprobe_step")
+    _lp_state(y, Wx, bx, C, "linprobe_step")
+    if Wx.shape[0] != J:
+        raise ValueError(f"linprobe_step: Wx has {Wx.shape[0]} jobs, Wz {J}")
+    if not isinstance(G, torch.Tensor) or G.dtype != torch.float32 or tuple(G.shape) != (n, J * Cp) or not G.is_contiguous():
+        raise ValueError(f"linprobe_step: G must be a contiguous f32 [{n}, {J * Cp}]")
+    _chk(G)
+    lam = _lp_vec(lam, torch.float32, J, "linprobe_step: lam")
+    eta = _lp_vec(eta, torch.float32, J, "linprobe_step: eta")
+    beta = float(beta)
+    if not (0.0 <= beta <= 1.0):
+        raise ValueError(f"linprobe_step: beta must lie in [0, 1], got {beta!r}")
+    tiles = (D + 1 + 127) // 128
+    if gmax_part is None and want_gmax:
+        gmax_part = torch.empty((tiles, J), device=y.device, dtype=torch.float32)
+    elif gmax_part is not None and (not isinstance(gmax_part, torch.Tensor) or gmax_part.dtype != torch.float32
+                                    or tuple(gmax_part.shape) != (tiles, J) or not gmax_part.is_contiguous()):
+        raise ValueError(f"linprobe_step: gmax_part must be a contiguous f32 [{tiles}, {J}]")
+    _chk(gmax_part)
+    _lib.call("mh_linprobe_step", _p(y), n, D, _p(G), _p(Wx), _p(bx), _p(Wz), _p(bz), _p(lam), _p(eta), beta, J, C, Cp, _p(gmax_part),
+              stream=_stream())
+    return gmax_part
+
+
 # ----------------------------------------------------------------------------- k-means and its agreement with labels (csrc/kmeans.hip)
 KMEANS_METRIC = {"euclidean": 0, "cosine": 1}
 
