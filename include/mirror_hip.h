@@ -1284,6 +1284,37 @@ int mh_linprobe_grad(const float* y, int64_t n, int D, const float* Wz, const fl
 int mh_linprobe_step(const float* y, int64_t n, int D, const float* G, float* Wx, float* bx, float* Wz, float* bz, const float* lam,
                      const float* eta, float beta, int J, int C, int Cp, float* gmax_part, mh_stream s);
 
+/* ---------------------------------------------------------------- survival linear probe of frozen embeddings (csrc/survprobe.hip;
+ * mirror_amd/survprobe.py; the reference's train_survival.py --linear_probe: one linear layer of num_bins hazard logits under
+ * NLLSurvLoss, losses/nll_surv.py:17-94, scored by the risk of train_survival.py:1431-1433, with the frozen encoder taken out of the
+ * loop).  J independent L2-regularised hazard regressions over the SAME prepared rows y [n x D] f32 contiguous; per job j, with
+ * v = W y_i + b in R^M, bin T_i and event indicator e_i,
+ *   nll_i     = sum_{t < T_i} softplus(v_t) + softplus(v_T) - e_i v_T                (no term for t > T_i)
+ *   F_j(W, b) = r_j sum_{i in train_j} w_i nll_i + (lambda_j / 2) |W|^2,   w_i = 1 if e_i = 1 else w_cens     (the bias unpenalised)
+ *   train_j   = { i : T_i in [0, M), e_i in {0, 1}, fold_i >= 0, fold_i != heldout_j }
+ * which is NLLSurvLoss(alpha = 1 - w_cens, reduction "mean") without its clamp of the hazards to [eps, 1 - eps]: the two agree
+ * wherever every |v_t| <= log((1 - eps) / eps) (16.1 at eps = 1e-7).  One FISTA iteration is mh_survprobe_grad followed by
+ * mh_linprobe_step with C = M, Cp = Mp.  Layout as mh_linprobe_*: Mp = the next power of two >= M, weights f32 [J x Mp x D], bias f32
+ * [J x Mp]; neither entry point reads what a pad slot t >= M holds.  Both are deterministic (fixed summation order, no float atomics),
+ * allocate nothing and never wait on the host.  Shared limits: 2 <= M <= 64, 1 <= D <= 4096, 1 <= n <= 2^20, J Mp <= 2^20.
+ *
+ * G f32 [n x J Mp] (n J Mp <= 2^28), STORED (nothing to zero): G[i, j Mp + t] = r_j w_i (sigmoid(v_t) - [t = T_i] e_i) for i in
+ * train_j and t <= T_i; exactly 0 for t > T_i, for pad columns and for every other row.  v_t = dot(y_i, Wz[j, t]) + bz[j, t]: the
+ * k-ordered f32 fmaf chain from 0 of the retrieval kernels and ONE f32 add; then e = expf(-|v|), sigmoid(v) = (v >= 0 ? 1 : e) /
+ * (1 + e), softplus(v) = max(v, 0) + log1pf(e), nll_i added in bin order in f32.  bins int64 [n] (8-byte aligned), event uint8 [n],
+ * fold int32 [n], heldout int32 [J], rscale f32 [J] (r_j), 0 <= w_cens <= 1.  loss_part f64 [ceil(n / 128) x J] (8-byte aligned) or
+ * NULL: loss_part[t, j] = r_j sum of w_i nll_i (f32) over the training rows of row tile t, added in row order in f64; their sum over
+ * t is the data term of F_j at (Wz, bz).  A NaN in a row makes the G rows and the loss of every job that trains on it NaN.  Grid
+ * ceil(n / 128) x ceil(J Mp / 128); one thread owns each (row, job). */
+int mh_survprobe_grad(const float* y, int64_t n, int D, const float* Wz, const float* bz, const int64_t* bins, const uint8_t* event,
+                      const int32_t* fold, const int32_t* heldout, const float* rscale, float w_cens, int J, int M, int Mp, float* G,
+                      double* loss_part, mh_stream s);
+/* risk f32 [S x nq], STORED: risk[s, i] = -sum_{t < M} prod_{u <= t} sigmoid(-v_u), v = W[s] q_i + b[s], the product and the sum in
+ * bin order in f32 (mh_surv_risk's definition with 1 - sigmoid(v) formed as sigmoid(-v); no clamp).  The S Mp weight rows of one
+ * fold's jobs are the keys of the same tile product; the [nq x S Mp] logits are never stored.  1 <= nq <= 2^20, S Mp <= 2^20.
+ * Grid ceil(nq / 128) x ceil(S Mp / 128). */
+int mh_survprobe_risk(const float* q, int64_t nq, int D, const float* W, const float* b, int S, int M, int Mp, float* risk, mh_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -265,6 +265,8 @@ _SIGS = {
     "mh_cluster_match": [P, I, I, I, P, P],
     "mh_linprobe_grad": [P, L, I, P, P, P, P, P, P, I, I, I, P, P],
     "mh_linprobe_step": [P, L, I, P, P, P, P, P, P, P, F, I, I, I, P],
+    "mh_survprobe_grad": [P, L, I, P, P, P, P, P, P, P, F, I, I, I, P, P],
+    "mh_survprobe_risk": [P, L, I, P, P, I, I, I, P],
 }
 EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "mh_gemm_variant_name", "mh_note_form", "mh_last_form", "mh_device_ok", "mh_nys_attn3_ws_floats", "mh_rna_block_workspace_bytes",
                                  "mh_rna_block_lds_bytes", "mh_rna_block_fits",

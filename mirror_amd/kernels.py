@@ -2873,6 +2873,54 @@ def linprobe_step(y: torch.Tensor, G: torch.Tensor, Wx: torch.Tensor, bx: torch.
     return gmax_part
 
 
+# ----------------------------------------------------------------------------- survival linear probe: J hazard regressions at once (csrc/survprobe.hip)
+def _sp_bins(M, who: str) -> int:
+    if isinstance(M, bool) or not isinstance(M, int) or not (2 <= M <= 64):
+        raise ValueError(f"{who}: M must be an int in [2, 64], got {M!r}")
+    return M
+
+
+def survprobe_grad(y: torch.Tensor, Wz: torch.Tensor, bz: torch.Tensor, bins: torch.Tensor, event: torch.Tensor, fold: torch.Tensor,
+                   heldout: torch.Tensor, rscale: torch.Tensor, w_cens: float, M: int, G: Optional[torch.Tensor] = None,
+                   want_loss: bool = False):
+    """(G f32 [n, J Mp], loss_part f64 [ceil(n / 128), J] or None) on the device (no sync): every job's hazard logit gradient
+    r_j w_i (sigmoid(Wz y_i + bz) - [t = T_i] e_i) over the bins t <= T_i of its training rows (bin in [0, M), event in {0, 1},
+    fold >= 0, fold != heldout_j; w_i = 1 for an event, w_cens otherwise), exactly 0 elsewhere and in the pad columns
+    (mh_survprobe_grad).  G may be passed to be overwritten; want_loss asks for the per-row-tile data terms."""
+    _sp_bins(M, "survprobe_grad")
+    n = _fs_f32(y, "survprobe_grad: y", device=False).shape[0]          # every type and shape first, the device last
+    for t, dtype, name in ((bins, torch.int64, "bins"), (event, torch.uint8, "event"), (fold, torch.int32, "fold")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (n,):
+            raise ValueError(f"survprobe_grad: {name} must be {dtype} [{n}]")
+    if isinstance(w_cens, bool) or not isinstance(w_cens, (int, float)) or not (0.0 <= float(w_cens) <= 1.0):
+        raise ValueError(f"survprobe_grad: w_cens must lie in [0, 1], got {w_cens!r}")
+    y, n, D, J, Mp = _lp_state(y, Wz, bz, M, "survprobe_grad")
+    _chk(bins, event, fold)
+    heldout = _lp_vec(heldout, torch.int32, J, "survprobe_grad: heldout")
+    rscale = _lp_vec(rscale, torch.float32, J, "survprobe_grad: rscale")
+    tiles = (n + 127) // 128
+    if G is None:
+        G = torch.empty((n, J * Mp), device=y.device, dtype=torch.float32)
+    elif not isinstance(G, torch.Tensor) or G.dtype != torch.float32 or tuple(G.shape) != (n, J * Mp) or not G.is_contiguous():
+        raise ValueError(f"survprobe_grad: G must be a contiguous f32 [{n}, {J * Mp}]")
+    _chk(G)
+    loss_part = torch.empty((tiles, J), device=y.device, dtype=torch.float64) if want_loss else None
+    _lib.call("mh_survprobe_grad", _p(y), n, D, _p(Wz), _p(bz), _p(bins.contiguous()), _p(event.contiguous()), _p(fold.contiguous()),
+              _p(heldout), _p(rscale), float(w_cens), J, M, Mp, _p(G), _p(loss_part), stream=_stream())
+    return G, loss_part
+
+
+def survprobe_risk(q: torch.Tensor, W: torch.Tensor, b: torch.Tensor, M: int) -> torch.Tensor:
+    """f32 [S, nq] on the device (no sync): per job s the risk -sum_t prod_{u <= t} sigmoid(-(W[s] q_i + b[s])_u) of every row of
+    q f32 [nq, D] under padded weights W f32 [S, Mp, D], b f32 [S, Mp] (mh_survprobe_risk: the retrieval kernels' exact-f32 tile
+    product; the [nq, S Mp] logits are never stored)."""
+    _sp_bins(M, "survprobe_risk")
+    q, nq, D, S, Mp = _lp_state(q, W, b, M, "survprobe_risk")
+    risk = torch.empty((S, nq), device=q.device, dtype=torch.float32)
+    _lib.call("mh_survprobe_risk", _p(q), nq, D, _p(W), _p(b), S, M, Mp, _p(risk), stream=_stream())
+    return risk
+
+
 # ----------------------------------------------------------------------------- k-means and its agreement with labels (csrc/kmeans.hip)
 KMEANS_METRIC = {"euclidean": 0, "cosine": 1}
 

@@ -11,7 +11,47 @@ import torch
 
 from . import kernels as K
 
-__all__ = ["concordance_index_censored", "logrank_by_median", "logrank_test", "risk_scores"]
+__all__ = ["concordance_index_censored", "logrank_by_median", "logrank_test", "risk_scores", "survival_bins"]
+
+
+def survival_bins(time, event, num_bins: int = 4, eps: float = 1e-6):
+    """(bins int64 [n], edges f64 [num_bins + 1]) as CPU tensors: the discrete time bins of `datasets/dataset_survival.py:_gen_disc_label`,
+    restated in f64 on the host (numpy; pandas is not a dependency).  The cohort is binned once, as the reference bins it.
+
+    With at least one event (`event == 1`): the edges are the linear-interpolation quantiles of the EVENT times at k / num_bins
+    (`pd.qcut`), the first then overwritten by min(time) - eps and the last by max(time) + eps over ALL rows.  With no event: num_bins
+    equal-width bins over [min, max] with the last edge moved up by 0.1 % of the range (min == max: 0.1 % of |min| to either side, 0.001
+    at 0), as `pd.cut(bins=num_bins, right=False)` forms them.  Either way bin = searchsorted(edges, time, side="right") - 1: the bins
+    are closed on the left.  Raises ValueError where the edges are not strictly increasing (where `pd.qcut` refuses duplicate edges),
+    for an empty or non-finite `time`, and for num_bins < 1."""
+    if isinstance(num_bins, bool) or not isinstance(num_bins, int) or num_bins < 1:
+        raise ValueError(f"num_bins must be a positive int, got {num_bins!r}")
+    t = np.asarray(time.detach().cpu() if isinstance(time, torch.Tensor) else time, dtype=np.float64).reshape(-1)
+    e = np.asarray(event.detach().cpu() if isinstance(event, torch.Tensor) else event).reshape(-1)
+    if t.size == 0 or e.size != t.size:
+        raise ValueError(f"time and event must be non-empty and of one length, got {t.size} and {e.size}")
+    if not np.isfinite(t).all():
+        raise ValueError("survival_bins: time must be finite")
+    te = t[e == 1]
+    if te.size:
+        edges = np.quantile(te, np.linspace(0.0, 1.0, num_bins + 1))
+        if not (np.diff(edges) > 0).all():
+            raise ValueError(f"Bin edges must be unique: the event-time quantiles are {edges.tolist()}")
+        edges[-1] = t.max() + eps
+        edges[0] = t.min() - eps
+    else:
+        mn, mx = float(t.min()), float(t.max())
+        if mn == mx:
+            mn -= 0.001 * abs(mn) if mn != 0 else 0.001
+            mx += 0.001 * abs(mx) if mx != 0 else 0.001
+            edges = np.linspace(mn, mx, num_bins + 1)
+        else:
+            edges = np.linspace(mn, mx, num_bins + 1)
+            edges[-1] += (mx - mn) * 0.001
+    if not (np.diff(edges) > 0).all():
+        raise ValueError(f"Bin edges must increase strictly, got {edges.tolist()}")
+    bins = np.searchsorted(edges, t, side="right") - 1
+    return torch.from_numpy(bins.astype(np.int64)), torch.from_numpy(edges)
 
 
 def risk_scores(logits: torch.Tensor) -> torch.Tensor:
