@@ -39,6 +39,10 @@ int mh_exp_build(void);      /* 1: built with -DMH_EXP (timing-experiment switch
 int mh_device_ok(void);
 /* Which of its kernels the calling thread's last elementwise / row-kernel entry point launched: "<entry>:<form>", e.g. "add:quad",
  * "softmax_fwd:block,scalar", "layernorm_bwd:ws", "colsum:bf16oct", or "<entry>:none" for a call that returned before any launch.
+ * The kernels that walk the token sequence note theirs the same way: "ppeg_fwd:pair" / ":strip", "ppeg_wgrad:strip", "ppeg_bwd:one" /
+ * ":one,drop", "resconv_fwd:mfma" / ":vec" / ":scalar", "resconv_wgrad:mfma" / ":vec8" / ":scalar", "resconv_bwd:mfma" / ":two_pass"
+ * (written after the two entry points it forwards to), "landmark_fwd:quad" / ":scalar", "landmark_bwd:oct" / ":scalar"; a call that
+ * was refused (MH_EINVAL) has noted "<entry>:none" as well.
  * mh_note_form is what the entry points call beside the launch they pick: it keeps the POINTER (string literals only), one store. */
 void mh_note_form(const char* literal);
 const char* mh_last_form(void);

@@ -83,32 +83,38 @@ __global__ __launch_bounds__(256) void landmark_bwd_vec_kernel(const T* __restri
                                                                int D, int l);
 
 extern "C" int mh_landmark_fwd(const void* qkv, void* lm, int B, int n_p, int D, int l, int dt, mh_stream s) {
+    mh_note_form("landmark_fwd:none");
     MH_REQUIRE(l >= 1 && n_p % l == 0, "mh_landmark_fwd: n_p=%d not a multiple of l=%d", n_p, l);
     const long total = (long)B * (n_p / l) * 2 * D;
     if (total == 0) return MH_OK;
     if (D % 4 == 0 && mh_quad_ok(qkv, mh_dt_size(dt)) && mh_quad_ok(lm, mh_dt_size(dt))) {
         dim3 gv((unsigned)min((long)mh_cdiv(total / 4, 256), 16384L));
+        mh_note_form("landmark_fwd:quad");
         MH_DISPATCH_DT(dt, T, hipLaunchKernelGGL((landmark_fwd_vec_kernel<T>), gv, dim3(256), 0, (hipStream_t)s, (const T*)qkv, (T*)lm, B, n_p, D, l));
         MH_LAUNCH_CHECK("mh_landmark_fwd");
         return MH_OK;
     }
     dim3 grid((unsigned)min((long)mh_cdiv(total, 256), 8192L));
+    mh_note_form("landmark_fwd:scalar");
     MH_DISPATCH_DT(dt, T, hipLaunchKernelGGL((landmark_fwd_kernel<T>), grid, dim3(256), 0, (hipStream_t)s, (const T*)qkv, (T*)lm, B, n_p, D, l));
     MH_LAUNCH_CHECK("mh_landmark_fwd");
     return MH_OK;
 }
 
 extern "C" int mh_landmark_bwd(const void* dlm, void* dqkv, int B, int n_p, int D, int l, int dt, mh_stream s) {
+    mh_note_form("landmark_bwd:none");
     MH_REQUIRE(l >= 1 && n_p % l == 0, "mh_landmark_bwd: n_p=%d not a multiple of l=%d", n_p, l);
     const long total = (long)B * n_p * 2 * D;
     if (total == 0) return MH_OK;
     if (D % 8 == 0 && ((uintptr_t)dlm & 15) == 0 && ((uintptr_t)dqkv & 15) == 0) {
         dim3 vgrid((unsigned)min((long)mh_cdiv(total / 8, 256), 8192L));
+        mh_note_form("landmark_bwd:oct");
         MH_DISPATCH_DT(dt, T, hipLaunchKernelGGL((landmark_bwd_vec_kernel<T>), vgrid, dim3(256), 0, (hipStream_t)s, (const T*)dlm, (T*)dqkv, B, n_p, D, l));
         MH_LAUNCH_CHECK("mh_landmark_bwd");
         return MH_OK;
     }
     dim3 grid((unsigned)min((long)mh_cdiv(total, 256), 8192L));
+    mh_note_form("landmark_bwd:scalar");
     MH_DISPATCH_DT(dt, T, hipLaunchKernelGGL((landmark_bwd_kernel<T>), grid, dim3(256), 0, (hipStream_t)s, (const T*)dlm, (T*)dqkv, B, n_p, D, l));
     MH_LAUNCH_CHECK("mh_landmark_bwd");
     return MH_OK;
@@ -271,18 +277,22 @@ __global__ __launch_bounds__(256) void resconv_vec_kernel(const TV* __restrict__
 extern "C" int mh_resconv_fwd(const void* v, int64_t ldv, int64_t v_bs, const float* w, void* out, int64_t ldo,
                               int64_t o_bs, int B, int n_p, int heads, int dh, int taps, int transpose, int accumulate,
                               int dt_v, int dt_o, mh_stream s) {
+    mh_note_form("resconv_fwd:none");
     MH_REQUIRE(taps >= 1 && taps <= RC_MAXTAPS && (taps & 1), "mh_resconv_fwd: taps=%d unsupported", taps);
+    MH_REQUIRE((dt_v == MH_F32 || dt_v == MH_BF16) && (dt_o == MH_F32 || dt_o == MH_BF16), "mh_resconv_fwd: unknown dtype code (dt_v=%d dt_o=%d)", dt_v, dt_o);
     const int C = heads * dh;
     MH_REQUIRE(heads <= 8 || 255 / dh + 2 <= 8, "mh_resconv_fwd: more than 8 heads per 256 columns (heads=%d dh=%d)", heads, dh);
     if (B == 0 || n_p == 0) return MH_OK;
     if (resconv_mfma_on() && resconv_try_mfma(v, ldv, v_bs, w, out, ldo, o_bs, B, n_p, heads, dh, taps, transpose, accumulate, dt_v,
                                               dt_o, (hipStream_t)s)) {   // bf16, dh = 64, 33 taps: banded Toeplitz product on MFMA
+        mh_note_form("resconv_fwd:mfma");
         MH_LAUNCH_CHECK("mh_resconv_fwd");
         return MH_OK;
     }
     if (dh % 8 == 0 && ldv % 8 == 0 && v_bs % 8 == 0 && ldo % 8 == 0 && o_bs % 8 == 0 && ((uintptr_t)v & 15) == 0 &&
         ((uintptr_t)out & 15) == 0 && (heads <= 8 || 511 / dh + 2 <= 8)) {
         dim3 vgrid(mh_cdiv(C, 512), mh_cdiv(n_p, 4 * RV_RT), B);
+        mh_note_form("resconv_fwd:vec");
 #define RCV(TV, TO) hipLaunchKernelGGL((resconv_vec_kernel<TV, TO>), vgrid, dim3(256), 0, (hipStream_t)s, (const TV*)v, (long)ldv, (long)v_bs, w, (TO*)out, (long)ldo, (long)o_bs, n_p, C, dh, taps, transpose, accumulate)
         if (dt_v == MH_F32 && dt_o == MH_F32) RCV(float, float);
         else if (dt_v == MH_BF16 && dt_o == MH_BF16) RCV(bf16_t, bf16_t);
@@ -293,6 +303,7 @@ extern "C" int mh_resconv_fwd(const void* v, int64_t ldv, int64_t v_bs, const fl
         return MH_OK;
     }
     dim3 grid(mh_cdiv(C, 256), mh_cdiv(n_p, RC_RT), B);
+    mh_note_form("resconv_fwd:scalar");
 #define RC(TV, TO) hipLaunchKernelGGL((resconv_kernel<TV, TO>), grid, dim3(256), 0, (hipStream_t)s, (const TV*)v, (long)ldv, (long)v_bs, w, (TO*)out, (long)ldo, (long)o_bs, n_p, C, dh, taps, transpose, accumulate)
     if (dt_v == MH_F32 && dt_o == MH_F32) RC(float, float);
     else if (dt_v == MH_BF16 && dt_o == MH_BF16) RC(bf16_t, bf16_t);
@@ -383,15 +394,19 @@ __global__ __launch_bounds__(256) void resconv_wgrad_kernel(const TV* __restrict
 
 extern "C" int mh_resconv_wgrad(const void* v, int64_t ldv, int64_t v_bs, const void* dout, int64_t ldo, int64_t o_bs,
                                 float* dw, int B, int n_p, int heads, int dh, int taps, int dt_v, int dt_o, mh_stream s) {
+    mh_note_form("resconv_wgrad:none");
     MH_REQUIRE(taps >= 1 && taps <= 63 && (taps & 1), "mh_resconv_wgrad: taps=%d unsupported", taps);
+    MH_REQUIRE((dt_v == MH_F32 || dt_v == MH_BF16) && (dt_o == MH_F32 || dt_o == MH_BF16), "mh_resconv_wgrad: unknown dtype code (dt_v=%d dt_o=%d)", dt_v, dt_o);
     if (B == 0 || n_p == 0) return MH_OK;
     if (resconv_mfma_on() && resconv_wgrad_try_mfma(v, ldv, v_bs, dout, ldo, o_bs, dw, B, n_p, heads, dh, taps, dt_v, dt_o, (hipStream_t)s)) {
+        mh_note_form("resconv_wgrad:mfma");
         MH_LAUNCH_CHECK("mh_resconv_wgrad");
         return MH_OK;
     }
     dim3 grid(heads, mh_cdiv(n_p, RW_ROWS), B);
 #define RW(TV, TO) hipLaunchKernelGGL((resconv_wgrad_kernel<TV, TO>), grid, dim3(256), 0, (hipStream_t)s, (const TV*)v, (long)ldv, (long)v_bs, (const TO*)dout, (long)ldo, (long)o_bs, dw, n_p, dh, taps, vec8)
     const int vec8 = dh % 8 == 0 && ldv % 8 == 0 && v_bs % 8 == 0 && ldo % 8 == 0 && o_bs % 8 == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)dout & 15) == 0;
+    mh_note_form(vec8 ? "resconv_wgrad:vec8" : "resconv_wgrad:scalar");
     if (dt_v == MH_F32 && dt_o == MH_F32) RW(float, float);
     else if (dt_v == MH_BF16 && dt_o == MH_BF16) RW(bf16_t, bf16_t);
     else if (dt_v == MH_BF16 && dt_o == MH_F32) RW(bf16_t, float);
@@ -408,17 +423,24 @@ extern "C" int64_t mh_resconv_bwd_workspace_bytes(int B, int n_p, int heads, int
 extern "C" int mh_resconv_bwd(const void* dout, int64_t ldo, int64_t o_bs, const void* v, int64_t ldv, int64_t v_bs, const float* w, void* dv,
                               int64_t lddv, int64_t dv_bs, float* dw, float* workspace, int64_t ws_floats, int B, int n_p, int heads, int dh,
                               int taps, int dt_v, int dt_o, mh_stream s) {
+    mh_note_form("resconv_bwd:none");
     MH_REQUIRE(taps >= 1 && taps <= 63 && (taps & 1), "mh_resconv_bwd: taps=%d unsupported", taps);
     MH_REQUIRE(dout && v && w && dv && dw, "mh_resconv_bwd: null pointer");
+    // what the second of the two passes would refuse, before the first has added to dw
+    MH_REQUIRE(heads <= 8 || 255 / dh + 2 <= 8, "mh_resconv_bwd: more than 8 heads per 256 columns (heads=%d dh=%d)", heads, dh);
+    MH_REQUIRE((dt_v == MH_F32 || dt_v == MH_BF16) && (dt_o == MH_F32 || dt_o == MH_BF16), "mh_resconv_bwd: unknown dtype code (dt_v=%d dt_o=%d)", dt_v, dt_o);
     if (B == 0 || n_p == 0) return MH_OK;
     if (resconv_mfma_on() && dt_v == dt_o &&
         resconv_bwd_try_mfma(dout, ldo, o_bs, v, ldv, v_bs, w, dv, lddv, dv_bs, dw, workspace, ws_floats, B, n_p, heads, dh, taps, dt_v, (hipStream_t)s)) {
+        mh_note_form("resconv_bwd:mfma");
         MH_LAUNCH_CHECK("mh_resconv_bwd");
         return MH_OK;
     }
     // other dtypes / geometries, or no workspace: the two passes
-    if (int e = mh_resconv_wgrad(v, ldv, v_bs, dout, ldo, o_bs, dw, B, n_p, heads, dh, taps, dt_v, dt_o, s)) return e;
-    return mh_resconv_fwd(dout, ldo, o_bs, w, dv, lddv, dv_bs, B, n_p, heads, dh, taps, 1, 1, dt_o, dt_v, s);
+    int e = mh_resconv_wgrad(v, ldv, v_bs, dout, ldo, o_bs, dw, B, n_p, heads, dh, taps, dt_v, dt_o, s);
+    if (!e) e = mh_resconv_fwd(dout, ldo, o_bs, w, dv, lddv, dv_bs, B, n_p, heads, dh, taps, 1, 1, dt_o, dt_v, s);
+    mh_note_form(e ? "resconv_bwd:none" : "resconv_bwd:two_pass");      // its own note, after the two entry points it forwards to
+    return e;
 }
 
 // ------------------------------------------------------------------ pinv initial scaling

@@ -275,9 +275,12 @@ __global__ __launch_bounds__(256) void ppeg_rows2_kernel(const float* __restrict
 
 extern "C" int mh_ppeg_fwd(const void* x, void* y, const float* merged, const float* bsum, int B, int S, int D, int flip,
                            int dt_x, int dt_y, mh_stream s) {
+    mh_note_form("ppeg_fwd:none");
     MH_REQUIRE(S >= 1 && D >= 1, "mh_ppeg_fwd: bad shape S=%d D=%d", S, D);
+    MH_REQUIRE((dt_x == MH_F32 || dt_x == MH_BF16) && (dt_y == MH_F32 || dt_y == MH_BF16), "mh_ppeg_fwd: unknown dtype code (dt_x=%d dt_y=%d)", dt_x, dt_y);
     if (B == 0) return MH_OK;
     if (dt_x == MH_F32 && dt_y == MH_F32 && D % 2 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)merged | (uintptr_t)bsum) & 7) == 0) {
+        mh_note_form("ppeg_fwd:pair");
 #if P2_FORM
         // rows per strip: two workgroups of ~200 VGPRs fit a CU, so the launch runs in rounds of 512; fewest (rounds x row steps of a
         // strip, 6 of them halo), PR_T rows when that is as good (c2: 2 strips of 32 rows = 512 workgroups; config 4's 91 x 91 grid at B = 8:
@@ -308,6 +311,7 @@ extern "C" int mh_ppeg_fwd(const void* x, void* y, const float* merged, const fl
     // PY_T = 16 rows per strip is not a multiple of the unroll (7): the walk is 7 + 7 + 2 rows with the window slots
     // following the row index, so a strip must start at a slot-0 row -> strips are re-based every PY_T rows
     dim3 grid(mh_cdiv(D, 256), mh_cdiv(S, PY_T) * mh_cdiv(S, PX_T), B);
+    mh_note_form("ppeg_fwd:strip");
 #define PP(TX, TY) hipLaunchKernelGGL((ppeg_strip_kernel<TX, TY>), grid, dim3(256), 0, (hipStream_t)s, (const TX*)x, (TY*)y, merged, bsum, S, D, flip)
     if (dt_x == MH_F32 && dt_y == MH_F32) PP(float, float);
     else if (dt_x == MH_BF16 && dt_y == MH_BF16) PP(bf16_t, bf16_t);
@@ -491,6 +495,8 @@ __global__ __launch_bounds__(256) void ppeg_wgrad_strip_kernel(const TX* __restr
 
 extern "C" int mh_ppeg_wgrad(const void* x, const void* dout, float* dmerged, float* dbsum, int B, int S, int D, int dt_x,
                              int dt_o, mh_stream s) {
+    mh_note_form("ppeg_wgrad:none");
+    MH_REQUIRE((dt_x == MH_F32 || dt_x == MH_BF16) && (dt_o == MH_F32 || dt_o == MH_BF16), "mh_ppeg_wgrad: unknown dtype code (dt_x=%d dt_o=%d)", dt_x, dt_o);
     if (B == 0) return MH_OK;
     const int pr = mh_cdiv(S, mh_cdiv(S, PW_ROWS));       // equal strips of at most PW_ROWS rows
 #if PW_RED
@@ -498,6 +504,7 @@ extern "C" int mh_ppeg_wgrad(const void* x, const void* dout, float* dmerged, fl
 #else
     dim3 grid(mh_cdiv(D, 256), mh_cdiv(S, pr) * mh_cdiv(S, PW_X), B);
 #endif
+    mh_note_form("ppeg_wgrad:strip");
 #define PW(TX, TO) hipLaunchKernelGGL((ppeg_wgrad_strip_kernel<TX, TO>), grid, dim3(256), 0, (hipStream_t)s, (const TX*)x, (const TO*)dout, dmerged, dbsum, S, D, pr)
     if (dt_x == MH_F32 && dt_o == MH_F32) PW(float, float);
     else if (dt_x == MH_BF16 && dt_o == MH_BF16) PW(bf16_t, bf16_t);
@@ -735,6 +742,7 @@ __global__ __launch_bounds__(256, 2) void ppeg_bwd_kernel(const float* __restric
 extern "C" int mh_ppeg_bwd(const float* x, const float* dy, const float* merged, float* dx, float* dmerged, float* dbsum, int B, int S,
                            int D, void* drop_out, float* drop_db, float p, uint64_t seed, uint64_t offset, const uint64_t* dev_base,
                            mh_stream s) {
+    mh_note_form("ppeg_bwd:none");
     MH_REQUIRE(S >= 1 && D >= 1, "mh_ppeg_bwd: bad shape S=%d D=%d", S, D);
     MH_REQUIRE(x && dy && merged && dx && dmerged && dbsum, "mh_ppeg_bwd: null pointer");
     MH_REQUIRE(!drop_out || (drop_db && D % 8 == 0 && (offset & 7) == 0 && p >= 0.f && p < 1.f && ((uintptr_t)drop_out & 1) == 0),
@@ -754,6 +762,7 @@ extern "C" int mh_ppeg_bwd(const float* x, const float* dy, const float* merged,
         }
     }
     const dim3 grid(mh_cdiv(D, 64) * mh_cdiv(S, pr) * mh_cdiv(mh_cdiv(S, PB_X), 4) * B);
+    mh_note_form(drop_out ? "ppeg_bwd:one,drop" : "ppeg_bwd:one");
     if (drop_out)
         hipLaunchKernelGGL(ppeg_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)s, x, dy, merged, dx, dmerged, dbsum, S, D, B, pr,
                            (bf16_t*)drop_out, drop_db, p, seed, offset, dev_base);

@@ -799,12 +799,14 @@ def l2norm_bwd(y, nrm, dy, dx, rows, D, dx_rs, accumulate):
 
 
 # ----------------------------------------------------------------------------- Nystrom pieces
-def landmark_fwd(qkv: torch.Tensor, l: int) -> torch.Tensor:
-    _chk(qkv)
+def landmark_fwd(qkv: torch.Tensor, l: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _chk(qkv, out)
     _contig(qkv, "qkv")
     B, n_p, D3 = qkv.shape
     D = D3 // 3
-    lm = torch.empty((B, n_p // l, 2 * D), device=qkv.device, dtype=qkv.dtype)
+    if out is not None and (tuple(out.shape) != (B, n_p // l, 2 * D) or out.dtype != qkv.dtype or not out.is_contiguous()):
+        raise MirrorHipError("landmark_fwd: out must be a contiguous [B, n_p / l, 2 D] tensor of qkv's dtype")
+    lm = out if out is not None else torch.empty((B, n_p // l, 2 * D), device=qkv.device, dtype=qkv.dtype)
     _lib.call("mh_landmark_fwd", _p(qkv), _p(lm), B, n_p, D, l, dt(qkv), stream=_stream())
     return lm
 
@@ -1272,11 +1274,13 @@ def ppeg_merge(w7, w5, w3, b7, b5, b3):
     return merged, bsum
 
 
-def ppeg(x: torch.Tensor, merged, bsum, S: int, flip: bool, out_dtype=None) -> torch.Tensor:
-    _chk(x, merged, bsum)
+def ppeg(x: torch.Tensor, merged, bsum, S: int, flip: bool, out_dtype=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _chk(x, merged, bsum, out)
     B, n, D = x.shape
     assert n == 1 + S * S and x.is_contiguous()
-    y = torch.empty_like(x, dtype=out_dtype or x.dtype)
+    if out is not None and (out.shape != x.shape or not out.is_contiguous() or out.dtype != (out_dtype or out.dtype)):
+        raise MirrorHipError("ppeg: out must be contiguous, of x's shape and of out_dtype")
+    y = out if out is not None else torch.empty_like(x, dtype=out_dtype or x.dtype)
     _lib.call("mh_ppeg_fwd", _p(x), _p(y), _p(merged), _p(bsum), B, S, D, int(flip), dt(x), dt(y), stream=_stream())
     return y
 
@@ -1624,7 +1628,10 @@ def cast(x: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None
 
 def last_form() -> str:
     """"<entry>:<form>" of the kernel the calling thread's last elementwise / row-kernel entry point launched (mh_last_form), e.g.
-    "add:scalar", "softmax_fwd:wave,quad", "layernorm_bwd:ws"; "<entry>:none" when the call returned before any launch."""
+    "add:scalar", "softmax_fwd:wave,quad", "layernorm_bwd:ws"; "<entry>:none" when the call returned before any launch or was refused.
+    The sequence kernels note theirs too: ppeg_fwd (pair, strip), ppeg_wgrad (strip), ppeg_bwd (one / one,drop), resconv_fwd (mfma, vec,
+    scalar), resconv_wgrad (mfma, vec8, scalar), resconv_bwd (mfma, two_pass: written after the two calls it forwards to), landmark_fwd
+    (quad, scalar) and landmark_bwd (oct, scalar)."""
     return (_lib.load().mh_last_form() or b"").decode()
 
 
