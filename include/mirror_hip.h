@@ -993,6 +993,14 @@ int mh_cls_confusion(const void* input, int64_t ld, int dt_in, const void* label
  * U2_c = 2 #{(i pos, j neg): s_i > s_j} + #{s_i == s_j}, so AUROC_c = U2_c / (2 P_c Q_c); NaN_c = the NaN scores in column c
  * (their pairs add nothing).  labels int64 [N].  O(N^2 C) pairs through LDS; 1 <= N <= 2^20, 2 <= C <= 1024. */
 int mh_auroc_counts(const float* scores, int64_t ld, const int64_t* labels, int N, int C, int64_t* counts, mh_stream s);
+/* The same pair counts for E score tables that share ONE label vector, in one launch (the S strengths of a held-out fold of
+ * LinearProbe.evaluate): table e is scores + e ld_table, its rows ld_row floats apart; counts [E x C x 4] int64, zeroed on s by this
+ * call, and counts[e] is, integer for integer, what mh_auroc_counts(scores + e ld_table, ld_row, ..) answers: the same kernel with
+ * the (table, class) pair e C + c in the grid's z, the negatives staged through LDS and integer atomics as there.  1 <= N <= 2^20,
+ * 2 <= C <= 1024, ld_row >= C, E >= 1, E C <= 65535 (the grid's z extent), ld_table >= N ld_row when E > 1.
+ * O(E N^2 C) pairs; per (table, class) N 4 bytes of scores and N 8 of labels per block row of 256 positives. */
+int mh_auroc_counts_many(const float* scores, int64_t ld_row, int64_t ld_table, const int64_t* labels, int N, int C, int E,
+                         int64_t* counts, mh_stream s);
 
 /* ---------------------------------------------------------------- InfoNCE with explicit negative keys (losses/info_nce.py:126-143;
  * the reference builds these logits and labels and forgets `F.cross_entropy(logits / temperature, labels)`).
@@ -1287,6 +1295,20 @@ int mh_linprobe_grad(const float* y, int64_t n, int D, const float* Wz, const fl
  * n (J Cp + D) 4 bytes read per tile, 4 J C (D + 1) 4 bytes read and written. */
 int mh_linprobe_step(const float* y, int64_t n, int D, const float* G, float* Wx, float* bx, float* Wz, float* bz, const float* lam,
                      const float* eta, float beta, int J, int C, int Cp, float* gmax_part, mh_stream s);
+/* Class probabilities of nq query rows q [nq x D] f32 contiguous under E jobs (weights W f32 [E x Cp x D], bias b f32 [E x Cp], the
+ * layout above; pad slots are never read into P or written): P f32 [E x nq x C] (C columns, not Cp), STORED (nothing to zero):
+ * P[e, i, c] = expf(v_c - lse) with v_c, m and lse formed by the SAME arithmetic sequence as in mh_linprobe_grad (one device function
+ * serves both kernels): the k-ordered f32 fmaf chain of the tile product over the E Cp weight rows as keys, ONE f32 add of the bias,
+ * then in class order in f32 m = max_c v_c, lse = m + logf(sum_c expf(v_c - m)).  So, with rscale = 1, P[e, i, c] equals
+ * G[i, e Cp + c] bit for bit at every c != label_i of a training row.  A NaN query row gives a NaN probability row under every job:
+ * nothing is filtered.  labels int64 [nq] (8-byte aligned) or NULL; nll_part f64 [ceil(nq / 128) x E] (8-byte aligned) or NULL, and it
+ * requires labels: nll_part[t, e] = the sum of lse - v_label (f32) over the rows of row tile t whose label lies in [0, C), added in
+ * row order in f64 as loss_part is (without a scale); rows with any other label add nothing; the sum over t is job e's log-loss over
+ * the labelled rows.  Limits: those above with nq for n and E for J.  Deterministic, allocates nothing, never waits on the host.
+ * Grid ceil(nq / 128) x ceil(E Cp / 128); one thread owns each (row, job); the half tile leaves LDS job by job, 64 C consecutive floats.
+ * (nq + E Cp) D 4 bytes read per tile row / column, E nq C 4 written. */
+int mh_linprobe_proba(const float* q, int64_t nq, int D, const float* W, const float* b, int E, int C, int Cp, const int64_t* labels,
+                      float* P, double* nll_part, mh_stream s);
 
 /* ---------------------------------------------------------------- survival linear probe of frozen embeddings (csrc/survprobe.hip;
  * mirror_amd/survprobe.py; the reference's train_survival.py --linear_probe: one linear layer of num_bins hazard logits under

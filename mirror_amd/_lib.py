@@ -241,6 +241,7 @@ _SIGS = {
     "mh_cls_ce_bwd": [P, L, P, I, I, I, F, L, P, I, P],
     "mh_cls_confusion": [P, L, I, P, I, I, I, P, P],
     "mh_auroc_counts": [P, L, P, I, I, P],
+    "mh_auroc_counts_many": [P, L, L, P, I, I, I, P],
     "mh_infonce_paired_fwd": [P, P, P, P, I, I, I, F, I],
     "mh_infonce_paired_bwd": [P, P, P, P, P, P, P, I, I, I, I, I],
     "mh_infonce_rows_fwd": [P, P, P, L, I, I, I, F, F, P, P, P, P],
@@ -265,6 +266,7 @@ _SIGS = {
     "mh_cluster_match": [P, I, I, I, P, P],
     "mh_linprobe_grad": [P, L, I, P, P, P, P, P, P, I, I, I, P, P],
     "mh_linprobe_step": [P, L, I, P, P, P, P, P, P, P, F, I, I, I, P],
+    "mh_linprobe_proba": [P, L, I, P, P, I, I, I, P, P, P],
     "mh_survprobe_grad": [P, L, I, P, P, P, P, P, P, P, F, I, I, I, P, P],
     "mh_survprobe_risk": [P, L, I, P, P, I, I, I, P],
 }

@@ -201,14 +201,19 @@ __global__ void __launch_bounds__(CL_THREADS) cls_confusion_kernel(const void* _
 // over chunks of AU_CHUNK samples j staged through LDS in tiles of CL_THREADS.  A j that is not a negative of c, and an i that
 // is not a positive, carry NaN, so (s_i > s_j) + (s_i >= s_j) adds 2 per pair ranked right, 1 per tie and 0 otherwise.  Per-lane
 // counts stay below 2 N <= 2^21; waves sum them exactly and add them with integer atomics (order-free).  The blockIdx.y == 0
-// blocks also count P_c, Q_c and the NaN scores of column c.
+// blocks also count P_c, Q_c and the NaN scores of column c.  With several score tables over the same labels (mh_auroc_counts_many)
+// blockIdx.z = e C + c: table e starts ld_table floats behind table e - 1 and owns counts [e C + c][4].
 constexpr int AU_CHUNK = 1024;
 constexpr int AU_MAX_Y = 64;
+constexpr int AU_MAX_Z = 65535;       // the grid's z extent
 
-__global__ void __launch_bounds__(CL_THREADS) auroc_counts_kernel(const float* __restrict__ x, int64_t ld, const int64_t* __restrict__ lab,
-                                                                  int N, unsigned long long* __restrict__ counts) {
+__global__ void __launch_bounds__(CL_THREADS) auroc_counts_kernel(const float* __restrict__ x, int64_t ld, int64_t ld_table,
+                                                                  const int64_t* __restrict__ lab, int N, int C,
+                                                                  unsigned long long* __restrict__ counts) {
     __shared__ float s_s[CL_THREADS];
-    const int c = blockIdx.z;
+    const int e = blockIdx.z / C, c = blockIdx.z - e * C;
+    x += e * ld_table;
+    counts += (int64_t)e * C * 4;
     const int i = blockIdx.x * CL_THREADS + threadIdx.x;
     const bool in = i < N;
     const float xi = in ? x[(int64_t)i * ld + c] : 0.f;
@@ -303,8 +308,29 @@ extern "C" int mh_auroc_counts(const float* scores, int64_t ld, const int64_t* l
     }
     const int nchunks = mh_cdiv(N, AU_CHUNK);
     const dim3 grid(mh_cdiv(N, CL_THREADS), nchunks < AU_MAX_Y ? nchunks : AU_MAX_Y, C);
-    hipLaunchKernelGGL(auroc_counts_kernel, grid, dim3(CL_THREADS), 0, (hipStream_t)s, scores, ld, labels, N,
+    hipLaunchKernelGGL(auroc_counts_kernel, grid, dim3(CL_THREADS), 0, (hipStream_t)s, scores, ld, (int64_t)0, labels, N, C,
                        (unsigned long long*)counts);
     MH_LAUNCH_CHECK("mh_auroc_counts");
+    return MH_OK;
+}
+
+extern "C" int mh_auroc_counts_many(const float* scores, int64_t ld_row, int64_t ld_table, const int64_t* labels, int N, int C, int E,
+                                    int64_t* counts, mh_stream s) {
+    MH_REQUIRE(N >= 1 && N <= (1 << 20), "mh_auroc_counts_many: N = %d outside [1, 2^20]", N);
+    MH_REQUIRE(C >= 2 && C <= 1024 && ld_row >= C, "mh_auroc_counts_many: bad shape C=%d ld_row=%lld", C, (long long)ld_row);
+    MH_REQUIRE(E >= 1 && (int64_t)E * C <= AU_MAX_Z, "mh_auroc_counts_many: E = %d tables of C = %d classes, E C <= %d at the most", E, C,
+               AU_MAX_Z);
+    MH_REQUIRE(E == 1 || ld_table >= (int64_t)N * ld_row, "mh_auroc_counts_many: ld_table = %lld < N ld_row = %d x %lld",
+               (long long)ld_table, N, (long long)ld_row);
+    MH_REQUIRE(scores && labels && counts, "mh_auroc_counts_many: null pointer");
+    if (hipMemsetAsync(counts, 0, (size_t)E * C * 4 * sizeof(int64_t), (hipStream_t)s) != hipSuccess) {
+        mh_set_error("mh_auroc_counts_many: hipMemsetAsync failed");
+        return MH_EHIP;
+    }
+    const int nchunks = mh_cdiv(N, AU_CHUNK);
+    const dim3 grid(mh_cdiv(N, CL_THREADS), nchunks < AU_MAX_Y ? nchunks : AU_MAX_Y, E * C);
+    hipLaunchKernelGGL(auroc_counts_kernel, grid, dim3(CL_THREADS), 0, (hipStream_t)s, scores, ld_row, E == 1 ? (int64_t)0 : ld_table, labels,
+                       N, C, (unsigned long long*)counts);
+    MH_LAUNCH_CHECK("mh_auroc_counts_many");
     return MH_OK;
 }

@@ -24,6 +24,10 @@
 //                      only.  Pad slots are skipped outright (-inf - (-inf) = NaN).  max |g| per key row by integer LDS max on the
 //                      bits of |g| (order-free; a NaN is larger than every number and survives), then per job of the tile.
 //                      No split over n: J Cp = 160, D = 512 is 2 x 5 workgroups.
+//   mh_linprobe_proba  the product and the per-(row, job) softmax of mh_linprobe_grad (lp_spill_half, lp_lse, lp_prob: the same
+//                      device functions, so the same bits) over query rows: p_c = expf(v_c - lse) is what the half tile keeps, and it
+//                      is stored to P [E x nq x C] WITHOUT the pad columns, job by job, 64 C consecutive floats per job of the key
+//                      tile.  lse - v_label of the rows with a label in [0, C) goes through the CE table to nll_part as the loss does.
 #include <math.h>
 
 #include "retrieval_tile.h"
@@ -40,6 +44,35 @@ constexpr int LP_LD = RT_TILE + 32;   // its LDS row stride: the two k of one MF
 constexpr int LP_QUADS = LP_BK * RT_TILE / 4 / RT_THREADS;
 
 // ------------------------------------------------------------------ logits, softmax, logit gradient
+// rows [pass 64, pass 64 + 64) of the 128 x 128 accumulator tile to s_t [64][LP_LDT]: the two waves with wm == pass own them
+__device__ __forceinline__ void lp_spill_half(const f32x16 (&acc)[2][2], float* __restrict__ s_t, int pass, int wm, int wn, int half,
+                                              int lane) {
+    if (wm != pass) return;
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++)
+                s_t[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * LP_LDT + wn * 64 + j * 32 + (lane & 31)] = acc[i][j][r];
+}
+
+// one (row, job): v_c = sc[c] + sb[c] stored back over sc, c < C (pads are never looked at); returns lse = m + logf(sum_c expf(v_c - m)),
+// m = max_c v_c, in class order in f32.  With lp_prob the ONE statement of the softmax that both kernels below use.
+__device__ __forceinline__ float lp_lse(float* __restrict__ sc, const float* __restrict__ sb, int C) {
+    float m = -INFINITY;
+    for (int c = 0; c < C; c++) {
+        const float v = sc[c] + sb[c];
+        sc[c] = v;
+        m = fmaxf(m, v);
+    }
+    float sum = 0.f;
+    for (int c = 0; c < C; c++) sum += expf(sc[c] - m);
+    return m + logf(sum);
+}
+
+__device__ __forceinline__ float lp_prob(float v, float lse) { return expf(v - lse); }
+
 __global__ void __launch_bounds__(RT_THREADS, 3) linprobe_grad_kernel(const float* __restrict__ y, const float* __restrict__ w,
                                                                       const float* __restrict__ bias, const int64_t* __restrict__ labels,
                                                                       const int32_t* __restrict__ fold, const int32_t* __restrict__ heldout,
@@ -68,15 +101,7 @@ __global__ void __launch_bounds__(RT_THREADS, 3) linprobe_grad_kernel(const floa
     double lsum = 0.0;                                    // thread `run` < runs: this row tile's CE of job col0 / Cp + run, in row order
 #pragma unroll
     for (int pass = 0; pass < 2; pass++) {
-        if (wm == pass) {
-#pragma unroll
-            for (int i = 0; i < 2; i++)
-#pragma unroll
-                for (int j = 0; j < 2; j++)
-#pragma unroll
-                    for (int r = 0; r < 16; r++)
-                        s_t[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * LP_LDT + wn * 64 + j * 32 + (lane & 31)] = acc[i][j][r];
-        }
+        lp_spill_half(acc, s_t, pass, wm, wn, half, lane);
         __syncthreads();
         for (int t = tid; t < tasks; t += RT_THREADS) {
             const int rl = t & (LP_HALF - 1), run = t >> 6;
@@ -95,18 +120,9 @@ __global__ void __launch_bounds__(RT_THREADS, 3) linprobe_grad_kernel(const floa
                 r = rscale[job];
             }
             if (train) {
-                const float* sb = s_bias + run * Cp;
-                float m = -INFINITY;
-                for (int c = 0; c < C; c++) {             // pads (c >= C) are never looked at
-                    const float v = sc[c] + sb[c];
-                    sc[c] = v;
-                    m = fmaxf(m, v);
-                }
-                float sum = 0.f;
-                for (int c = 0; c < C; c++) sum += expf(sc[c] - m);
-                const float lse = m + logf(sum);
+                const float lse = lp_lse(sc, s_bias + run * Cp, C);
                 ce = lse - sc[lab];
-                for (int c = 0; c < C; c++) sc[c] = r * (expf(sc[c] - lse) - (c == lab ? 1.f : 0.f));
+                for (int c = 0; c < C; c++) sc[c] = r * (lp_prob(sc[c], lse) - (c == lab ? 1.f : 0.f));
                 for (int c = C; c < Cp; c++) sc[c] = 0.f;
             } else {
                 for (int c = 0; c < Cp; c++) sc[c] = 0.f;
@@ -128,6 +144,67 @@ __global__ void __launch_bounds__(RT_THREADS, 3) linprobe_grad_kernel(const floa
         const int job = (col0 >> cshift) + tid;
         loss_part[(int64_t)blockIdx.x * J + job] = (double)rscale[job] * lsum;
     }
+}
+
+// ------------------------------------------------------------------ class probabilities of query rows, and their log-loss
+__global__ void __launch_bounds__(RT_THREADS, 3) linprobe_proba_kernel(const float* __restrict__ q, const float* __restrict__ w,
+                                                                       const float* __restrict__ bias, const int64_t* __restrict__ labels,
+                                                                       int n, int nk, int D, int C, int cshift, int vec,
+                                                                       float* __restrict__ P, double* __restrict__ nll_part) {
+    __shared__ float s_stage[4][RT_TILE * RT_LD];         // as linprobe_grad_kernel: the stages, then the spilled half tile
+    __shared__ float s_ce[RT_TILE / 2 * LP_LDC];          // lse - v_label of (run, row) of the current half
+    float (&s_a)[2][RT_TILE * RT_LD] = *reinterpret_cast<float (*)[2][RT_TILE * RT_LD]>(&s_stage[0][0]);
+    float (&s_b)[2][RT_TILE * RT_LD] = *reinterpret_cast<float (*)[2][RT_TILE * RT_LD]>(&s_stage[2][0]);
+    float* s_t = &s_stage[0][0];
+    float* s_bias = s_t + LP_HALF * LP_LDT;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, half = lane >> 5;
+    const int row0 = blockIdx.x * RT_TILE, col0 = blockIdx.y * RT_TILE;
+    const int Cp = 1 << cshift, J = nk >> cshift;
+    const int job0 = col0 >> cshift;
+    const int runs = min(RT_TILE >> cshift, J - job0);    // jobs of this key tile: nk = J Cp, a run lies inside the keys or outside
+
+    f32x16 acc[2][2];
+    retr_product(acc, q, w, n, nk, D, row0, col0, vec, s_a, s_b);
+
+    if (tid < RT_TILE) s_bias[tid] = col0 + tid < nk ? bias[col0 + tid] : 0.f;
+    double lsum = 0.0;                                    // thread `run` < runs: this row tile's log-loss under job job0 + run, in row order
+#pragma unroll
+    for (int pass = 0; pass < 2; pass++) {
+        lp_spill_half(acc, s_t, pass, wm, wn, half, lane);
+        __syncthreads();
+        const int rbase = row0 + pass * LP_HALF;
+        const int rows = min(LP_HALF, n - rbase);         // <= 0: this half lies past the last row
+        for (int t = tid; t < LP_HALF * runs; t += RT_THREADS) {
+            const int rl = t & (LP_HALF - 1), run = t >> 6;
+            float* sc = s_t + rl * LP_LDT + run * Cp;
+            float ce = 0.f;
+            if (rl < rows) {
+                const float lse = lp_lse(sc, s_bias + run * Cp, C);
+                if (labels) {
+                    const int64_t l64 = labels[rbase + rl];
+                    if (l64 >= 0 && l64 < C) ce = lse - sc[(int)l64];
+                }
+                for (int c = 0; c < C; c++) sc[c] = lp_prob(sc[c], lse);
+            }
+            s_ce[run * LP_LDC + rl] = ce;
+        }
+        __syncthreads();
+        const int per = rows * C;                         // job by job: rows x C consecutive floats of P [E x n x C]
+        for (int run = 0; run < runs && per > 0; run++) {
+            float* dst = P + ((int64_t)(job0 + run) * n + rbase) * C;
+            for (int t = tid; t < per; t += RT_THREADS) {
+                const int rl = t / C, c = t - rl * C;
+                dst[t] = s_t[rl * LP_LDT + run * Cp + c];
+            }
+        }
+        if (nll_part && tid < runs) {
+            for (int rl = 0; rl < LP_HALF; rl++) lsum += (double)s_ce[tid * LP_LDC + rl];
+        }
+        __syncthreads();                                  // the next pass overwrites the half tile and the CE table
+    }
+    if (nll_part && tid < runs) nll_part[(int64_t)blockIdx.x * J + job0 + tid] = lsum;
 }
 
 // ------------------------------------------------------------------ weight gradient and the FISTA update
@@ -317,5 +394,19 @@ extern "C" int mh_linprobe_step(const float* y, int64_t n, int D, const float* G
     hipLaunchKernelGGL(linprobe_step_kernel, dim3(mh_cdiv(nk, RT_TILE), mh_cdiv(D + 1, RT_TILE)), dim3(RT_THREADS), 0, (hipStream_t)s, y, G,
                        Wx, bx, Wz, bz, lam, eta, beta, (int)n, nk, D, C, lp_shift(Cp), vec_g, vec_y, gmax_part);
     MH_LAUNCH_CHECK("mh_linprobe_step");
+    return MH_OK;
+}
+
+extern "C" int mh_linprobe_proba(const float* q, int64_t nq, int D, const float* W, const float* b, int E, int C, int Cp,
+                                 const int64_t* labels, float* P, double* nll_part, mh_stream s) {
+    if (int rc = linprobe_geometry("mh_linprobe_proba", nq, D, E, C, Cp)) return rc;
+    MH_REQUIRE(labels || !nll_part, "mh_linprobe_proba: nll_part needs labels");
+    MH_REQUIRE(q && W && b && P, "mh_linprobe_proba: null pointer");
+    MH_REQUIRE((((uintptr_t)labels | (uintptr_t)nll_part) & 7) == 0, "mh_linprobe_proba: labels and nll_part must be 8-byte aligned");
+    const int nk = E * Cp;
+    const int vec = D % 4 == 0 && mh_quad_ok(q, 4) && mh_quad_ok(W, 4);
+    hipLaunchKernelGGL(linprobe_proba_kernel, dim3(mh_cdiv(nq, RT_TILE), mh_cdiv(nk, RT_TILE)), dim3(RT_THREADS), 0, (hipStream_t)s, q, W, b,
+                       labels, (int)nq, nk, D, C, lp_shift(Cp), vec, P, nll_part);
+    MH_LAUNCH_CHECK("mh_linprobe_proba");
     return MH_OK;
 }

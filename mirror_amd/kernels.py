@@ -2406,6 +2406,34 @@ def auroc_counts(scores: torch.Tensor, labels_i64: torch.Tensor) -> torch.Tensor
     return counts
 
 
+def auroc_counts_many(scores: torch.Tensor, labels: torch.Tensor, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 [E, C, 4] {U2, P, Q, NaN count} per (table, class) on the device (no sync): mh_auroc_counts of each of the E tables of
+    scores f32 [E, N, C] against the one label vector int64 [N], in one launch (mh_auroc_counts_many).  scores may be a view with unit
+    stride along the classes (row stride >= C, table stride >= N rows); counts may be passed to be overwritten."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 3 or scores.dtype != torch.float32:
+        got = f"{scores.dtype} {tuple(scores.shape)}" if isinstance(scores, torch.Tensor) else type(scores).__name__
+        raise ValueError(f"auroc_counts_many: scores must be f32 [E, N, C], got {got}")
+    E, N, C = scores.shape
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or tuple(labels.shape) != (N,):
+        raise ValueError(f"auroc_counts_many: labels must be int64 [{N}]")
+    if counts is not None and (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or tuple(counts.shape) != (E, C, 4)
+                               or not counts.is_contiguous()):
+        raise ValueError(f"auroc_counts_many: counts must be a contiguous int64 [{E}, {C}, 4]")
+    _chk(scores, labels, counts)
+    if not (1 <= N <= (1 << 20)) or not (2 <= C <= 1024) or not (1 <= E and E * C <= 65535):
+        raise MirrorHipError(f"auroc_counts_many: N = {N} (1..2^20), C = {C} (2..1024), E = {E} tables (E * C <= 65535)")
+    scores = scores.detach()
+    ld_row = scores.stride(1) if N > 1 else C
+    ld_table = scores.stride(0) if E > 1 else N * ld_row
+    if scores.stride(2) != 1 or ld_row < C or ld_table < N * ld_row:
+        scores = scores.contiguous()
+        ld_row, ld_table = C, N * C
+    if counts is None:
+        counts = torch.empty((E, C, 4), device=scores.device, dtype=torch.int64)
+    _lib.call("mh_auroc_counts_many", _p(scores), ld_row, ld_table, _p(labels.contiguous()), N, C, E, _p(counts), stream=_stream())
+    return counts
+
+
 # ----------------------------------------------------------------------------- InfoNCE with explicit negative keys (csrc/infonce.hip)
 def _nce_f32(t: torch.Tensor, shape, name: str) -> torch.Tensor:
     if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
@@ -2878,6 +2906,34 @@ def linprobe_step(y: torch.Tensor, G: torch.Tensor, Wx: torch.Tensor, bx: torch.
     _lib.call("mh_linprobe_step", _p(y), n, D, _p(G), _p(Wx), _p(bx), _p(Wz), _p(bz), _p(lam), _p(eta), beta, J, C, Cp, _p(gmax_part),
               stream=_stream())
     return gmax_part
+
+
+def linprobe_proba(q: torch.Tensor, W: torch.Tensor, b: torch.Tensor, C: int, labels: Optional[torch.Tensor] = None,
+                   P: Optional[torch.Tensor] = None, want_nll: bool = False, nll_part: Optional[torch.Tensor] = None):
+    """(P f32 [E, nq, C], nll_part f64 [ceil(nq / 128), E] or None) on the device (no sync): softmax(W_e q_i + b_e) of the prepared rows
+    q f32 [nq, D] under the E jobs of the padded weights, with the logits, lse and expf(v - lse) of mh_linprobe_grad bit for bit
+    (mh_linprobe_proba).  want_nll (or a passed nll_part) asks for the per-row-tile sums of lse - v_label over the rows with a label in
+    [0, C) and needs labels int64 [nq].  P and nll_part may be passed to be overwritten."""
+    q, nq, D, E, Cp = _lp_state(q, W, b, C, "linprobe_proba")
+    if labels is not None and (not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or tuple(labels.shape) != (nq,)):
+        raise ValueError(f"linprobe_proba: labels must be int64 [{nq}]")
+    want_nll = want_nll or nll_part is not None
+    if want_nll and labels is None:
+        raise ValueError("linprobe_proba: the log-loss needs labels")
+    tiles = (nq + 127) // 128
+    if P is None:
+        P = torch.empty((E, nq, C), device=q.device, dtype=torch.float32)
+    elif not isinstance(P, torch.Tensor) or P.dtype != torch.float32 or tuple(P.shape) != (E, nq, C) or not P.is_contiguous():
+        raise ValueError(f"linprobe_proba: P must be a contiguous f32 [{E}, {nq}, {C}]")
+    if nll_part is None and want_nll:
+        nll_part = torch.empty((tiles, E), device=q.device, dtype=torch.float64)
+    elif nll_part is not None and (not isinstance(nll_part, torch.Tensor) or nll_part.dtype != torch.float64
+                                   or tuple(nll_part.shape) != (tiles, E) or not nll_part.is_contiguous()):
+        raise ValueError(f"linprobe_proba: nll_part must be a contiguous f64 [{tiles}, {E}]")
+    _chk(labels, P, nll_part)
+    _lib.call("mh_linprobe_proba", _p(q), nq, D, _p(W), _p(b), E, C, Cp, _p(None if labels is None else labels.contiguous()), _p(P),
+              _p(nll_part), stream=_stream())
+    return P, nll_part
 
 
 # ----------------------------------------------------------------------------- survival linear probe: J hazard regressions at once (csrc/survprobe.hip)

@@ -22,8 +22,16 @@ exact-f32 tile product) and `mh_linprobe_step` (every weight gradient as one pro
 place).  Both are deterministic: no float atomics, two fits agree bit for bit.  Scoring the held-out folds reuses
 `mh_fewshot_predict` / `mh_fewshot_tally` with a fold's S jobs in the role of the episodes.
 
-Not built: AUROC or class probabilities, class weights, momentum restart or line search, bf16 embeddings, a pool gathered over DDP
-ranks, a split of the step kernel over n (at J Cp = 160, D = 512 it runs on a handful of workgroups).
+The figures that need a score (the reference's validation pass prints Acc, AUC and F1: train_subtyping.py:1355-1432) come from two
+more launches per fold: `mh_linprobe_proba` (the tile product and the softmax of `mh_linprobe_grad`, bit for bit, with the
+probabilities [S, n_f, C] and the held-out log-loss as its outputs) and `mh_auroc_counts_many` (the exact integer pair counts of
+`mh_auroc_counts` for the S tables at once).  `evaluate(auroc=True)` forms the one-vs-rest AUROC in f64 from those counts, ON THE
+SOFTMAX PROBABILITIES as sklearn's `roc_auc_score(multi_class="ovr")` does on `predict_proba`; the reference feeds raw logits to
+torcheval's MulticlassAUROC, which ranks the same for C = 2 and differently for C > 2.  `predict_proba` / `oof_proba` hand the
+probabilities out.
+
+Not built: class weights, calibration figures (ECE, Brier score), momentum restart or line search, bf16 embeddings, a pool gathered
+over DDP ranks, a split of the step kernel over n (at J Cp = 160, D = 512 it runs on a handful of workgroups).
 """
 from __future__ import annotations
 
@@ -45,6 +53,11 @@ def _int_in(v, lo: int, hi: int, what: str) -> int:
     return v
 
 
+def _floats(t: torch.Tensor):
+    """A host tensor as floats: a float for a scalar, nested tuples otherwise."""
+    return tuple(_floats(x) for x in t) if t.dim() else float(t)
+
+
 def fista_betas(steps: int) -> list:
     """beta_0 .. beta_{steps - 1} of the iteration above, in f64 on the host (beta_0 = 0)."""
     out, t = [], 1.0
@@ -56,8 +69,9 @@ def fista_betas(steps: int) -> list:
 
 
 class LinearProbe:
-    """`fit(emb, labels, fold=None)` trains every job; `evaluate()` scores the held-out folds; `predict(emb, strength=None)` classifies
-    new rows under the all-rows job of the best (or the given) strength.
+    """`fit(emb, labels, fold=None)` trains every job; `evaluate()` scores the held-out folds (`auroc=True`: with AUROC and log-loss);
+    `predict(emb, strength=None)` classifies new rows under the all-rows job of the best (or the given) strength and `predict_proba`
+    gives their class probabilities; `oof_proba(strength=None)` gives every pool row's under the job that held its fold out.
 
     The rows are prepared as FewShotProbe / ClusterProbe prepare them: center=True, y = (x - mu) / max(|x - mu|, 1e-12) with mu the
     pool's column mean (mh_colmean, mh_center_l2norm); center=False, normalised only.  Later queries use the POOL's mean.
@@ -104,7 +118,7 @@ class LinearProbe:
         self.coef_ = self.intercept_ = self.loss_ = self.grad_inf_ = self.n_train_ = None
         self.n_iter_ = 0
         self.n_folds_ = 0
-        self.per_job = self.best_strength_ = None
+        self.per_job = self.per_job_auc = self.per_job_nll = self.best_strength_ = None
 
     # ------------------------------------------------------------------ preparation
     @staticmethod
@@ -195,27 +209,82 @@ class LinearProbe:
             raise ValueError("LinearProbe: nothing is fitted (call fit() first)")
 
     # ------------------------------------------------------------------ scores of the held-out folds
-    def evaluate(self):
+    def evaluate(self, auroc: bool = False, average: Optional[str] = "macro", select: str = "acc"):
         """Every fold's rows under the S jobs that held it out: an OrderedDict of `linprobe_acc` (per cent), `linprobe_bacc` (balanced
         accuracy, per cent) and `linprobe_f1` (macro F1) at the best strength, each the mean over the folds, with `_mean` and `_std`
         (sample standard deviation over the folds, 0 for one fold) as tuples over the strengths in the constructor's order; then
         `linprobe_best_strength` (the highest mean accuracy, ties to the larger lambda), `linprobe_strengths`, `linprobe_folds`,
-        `linprobe_n` (the rows that lie in a fold) and `per_job` f64 [F, S, 3] on the device.  One host copy."""
+        `linprobe_n` (the rows that lie in a fold) and `per_job` f64 [F, S, 3] on the device.  One host copy.
+
+        auroc=True adds the two figures that need a score, per fold from one `mh_linprobe_proba` over the fold's rows under its S
+        jobs and one `mh_auroc_counts_many` on the result: `linprobe_auc` and `linprobe_nll` with `_mean` / `_std` as above,
+        `per_job_auc` f64 [F, S, C] and `per_job_nll` f64 [F, S] on the device; still one host copy.  The AUROC is one-vs-rest ON THE
+        SOFTMAX PROBABILITIES, class c's column against the rows of every other label, U2_c / (2 P_c Q_c) in f64 from the exact
+        integer pair counts: sklearn's `roc_auc_score(predict_proba, multi_class="ovr")`.  The reference hands torcheval's
+        MulticlassAUROC the raw logits (train_subtyping.py:1391); the two rankings agree for C = 2 and differ for C > 2, where a row's
+        lse moves its probability of c but not its logit.  A class without a positive or without a negative in the fold (P_c Q_c = 0)
+        is NaN in `per_job_auc` and left out of the average; a NaN probability in a column makes that job's AUROC NaN; a fold where no
+        class has both gives NaN.  average: "macro" (the mean over the classes with P_c Q_c > 0), "weighted" (weights P_c) or None
+        (per class only: `linprobe_auc` is a tuple over the classes, `_mean` / `_std` tuples over the strengths of such tuples).
+        `linprobe_nll` is the mean held-out log-loss: the sum of lse - v_label over the fold's rows with a label in [0, C), divided by
+        their number.  select: "acc", "auc" (the highest mean AUROC; needs an average) or "nll" (the lowest mean log-loss) chooses
+        `linprobe_best_strength`, ties to the larger lambda; "auc" and "nll" need auroc=True."""
+        if not isinstance(auroc, bool):
+            raise ValueError(f"auroc must be a bool, got {auroc!r}")
+        if average is not None and average not in ("macro", "weighted"):
+            raise ValueError(f"average must be 'macro', 'weighted' or None, got {average!r}")
+        if select not in ("acc", "auc", "nll"):
+            raise ValueError(f"select must be 'acc', 'auc' or 'nll', got {select!r}")
+        if select != "acc" and not auroc:
+            raise ValueError(f"select={select!r} needs auroc=True")
+        if select == "auc" and average is None:
+            raise ValueError("select='auc' needs average='macro' or 'weighted'")
         self._fitted()
         F, S, C = self.n_folds_, len(self.strengths), self.num_classes
         if F < 1:
             raise ValueError("LinearProbe: evaluate() needs folds (fit(emb, labels, fold=...))")
-        tables = []
+        tables, aucs, pos, nlls = [], [], [], []
         for f, rows in enumerate(self._fold_rows):
             q = self._y.index_select(0, rows)
-            pred = K.fewshot_predict(q, self._Wx[f * S:(f + 1) * S], self._bx[f * S:(f + 1) * S], C)
-            tables.append(K.fewshot_tally(pred, self._labels.index_select(0, rows), C)[2])
+            lab = self._labels.index_select(0, rows)
+            W, b = self._Wx[f * S:(f + 1) * S], self._bx[f * S:(f + 1) * S]
+            pred = K.fewshot_predict(q, W, b, C)
+            tables.append(K.fewshot_tally(pred, lab, C)[2])
+            if auroc:
+                P, part = K.linprobe_proba(q, W, b, C, labels=lab, want_nll=True)
+                cnt = K.auroc_counts_many(P, lab).double()                    # [S, C, 4]: every count is below 2^53, exact in f64
+                a = cnt[:, :, 0] / (2.0 * cnt[:, :, 1] * cnt[:, :, 2])        # 0 / 0 = NaN where P_c Q_c = 0
+                aucs.append(torch.where(cnt[:, :, 3] > 0, math.nan, a))
+                pos.append(cnt[0, :, 1] * (cnt[0, :, 2] > 0))                 # P_c of the classes that count, 0 for the others
+                nlls.append(part.sum(0) / ((lab >= 0) & (lab < C)).sum())
         self.per_job = torch.stack(tables)
-        t = self.per_job.cpu()                                                # the one host wait
+        if auroc:
+            self.per_job_auc, self.per_job_nll = torch.stack(aucs), torch.stack(nlls)
+            packed = torch.cat([self.per_job.reshape(-1), self.per_job_auc.reshape(-1), self.per_job_nll.reshape(-1),
+                                torch.stack(pos).reshape(-1)]).cpu()          # the one host wait
+            t, auc_t, nll_t, w = (x.reshape(sh) for x, sh in zip(packed.split([F * S * 3, F * S * C, F * S, F * C]),
+                                                                  ((F, S, 3), (F, S, C), (F, S), (F, C))))
+        else:
+            self.per_job_auc = self.per_job_nll = None
+            t = self.per_job.cpu()                                            # the one host wait
         mean = t.mean(0)
         std = t.std(0, unbiased=True) if F > 1 else torch.zeros_like(mean)
-        acc = [float(a) if a == a else -math.inf for a in mean[:, 0]]
-        best = max(range(S), key=lambda s: (acc[s], self.strengths[s]))
+        score = [float(a) for a in mean[:, 0]]
+        if auroc:
+            if average is None:
+                job_auc = auc_t                                               # [F, S, C]
+            else:
+                wt = (w > 0).double() if average == "macro" else w            # [F, C]
+                job_auc = torch.where(wt[:, None, :] > 0, auc_t, 0.0).mul(wt[:, None, :]).sum(2) / wt.sum(1)[:, None]
+            auc_mean, nll_mean = job_auc.mean(0), nll_t.mean(0)
+            auc_std = job_auc.std(0, unbiased=True) if F > 1 else torch.zeros_like(auc_mean)
+            nll_std = nll_t.std(0, unbiased=True) if F > 1 else torch.zeros_like(nll_mean)
+            if select == "auc":
+                score = [float(a) for a in auc_mean]
+            elif select == "nll":
+                score = [-float(a) for a in nll_mean]
+        score = [a if a == a else -math.inf for a in score]
+        best = max(range(S), key=lambda s: (score[s], self.strengths[s]))
         self.best_strength_ = self.strengths[best]
         out: "OrderedDict[str, object]" = OrderedDict()
         for k, name in enumerate(("linprobe_acc", "linprobe_bacc", "linprobe_f1")):
@@ -227,16 +296,16 @@ class LinearProbe:
         out["linprobe_folds"] = F
         out["linprobe_n"] = int(sum(r.numel() for r in self._fold_rows))
         out["per_job"] = self.per_job
+        if auroc:
+            for name, m, sd in (("linprobe_auc", auc_mean, auc_std), ("linprobe_nll", nll_mean, nll_std)):
+                out[name], out[name + "_mean"], out[name + "_std"] = _floats(m[best]), _floats(m), _floats(sd)
+            out["per_job_auc"], out["per_job_nll"] = self.per_job_auc, self.per_job_nll
         return out
 
-    # ------------------------------------------------------------------ new rows
-    def predict(self, emb: torch.Tensor, strength: Optional[float] = None) -> torch.Tensor:
-        """int32 [n'] on the device: the classes of emb's rows, prepared with the pool's mean, under the all-rows job of `strength`
-        (one of the constructor's) or, for None, of `linprobe_best_strength` (evaluate() is run when it has not been; without folds
-        and with more than one strength, name the strength)."""
-        self._fitted()
-        S, C = len(self.strengths), self.num_classes
-        self._rows(emb, "emb", self._Wx.shape[2])
+    def _strength_index(self, strength: Optional[float]) -> int:
+        """The position of `strength` among the constructor's, or for None of `linprobe_best_strength` (evaluate() is run when it has
+        not been; without folds and with more than one strength, name the strength)."""
+        S = len(self.strengths)
         if strength is None:
             if S == 1:
                 strength = self.strengths[0]
@@ -248,6 +317,39 @@ class LinearProbe:
                 strength = self.best_strength_
         if isinstance(strength, bool) or not isinstance(strength, (int, float)) or float(strength) not in self.strengths:
             raise ValueError(f"strength must be one of {self.strengths}, got {strength!r}")
-        j = self.n_folds_ * S + self.strengths.index(float(strength))
-        q = self._prepare(emb.detach().to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous())
-        return K.fewshot_predict(q, self._Wx[j:j + 1], self._bx[j:j + 1], C)[0]
+        return self.strengths.index(float(strength))
+
+    def oof_proba(self, strength: Optional[float] = None) -> torch.Tensor:
+        """f32 [n, C] on the device: every pool row's class probabilities under the job that held its fold out at `strength` (None: as
+        predict), NaN for the rows that lie in no fold."""
+        self._fitted()
+        if self.n_folds_ < 1:
+            raise ValueError("LinearProbe: oof_proba() needs folds (fit(emb, labels, fold=...))")
+        S, s, C = len(self.strengths), self._strength_index(strength), self.num_classes
+        out = torch.full((self._y.shape[0], C), math.nan, device=self.device, dtype=torch.float32)
+        for f, rows in enumerate(self._fold_rows):
+            j = f * S + s
+            out.index_copy_(0, rows, K.linprobe_proba(self._y.index_select(0, rows), self._Wx[j:j + 1], self._bx[j:j + 1], C)[0][0])
+        return out
+
+    # ------------------------------------------------------------------ new rows
+    def predict(self, emb: torch.Tensor, strength: Optional[float] = None) -> torch.Tensor:
+        """int32 [n'] on the device: the classes of emb's rows, prepared with the pool's mean, under the all-rows job of `strength`
+        (one of the constructor's) or, for None, of `linprobe_best_strength` (evaluate() is run when it has not been; without folds
+        and with more than one strength, name the strength)."""
+        j, q = self._all_rows_job(emb, strength)
+        return K.fewshot_predict(q, self._Wx[j:j + 1], self._bx[j:j + 1], self.num_classes)[0]
+
+    def predict_proba(self, emb: torch.Tensor, strength: Optional[float] = None) -> torch.Tensor:
+        """f32 [n', C] on the device: the class probabilities of emb's rows under the same job and the same preparation as `predict`
+        (mh_linprobe_proba).  Its argmax is `predict`'s class wherever the two largest probabilities differ; where they are equal,
+        `predict` answers the smaller class."""
+        j, q = self._all_rows_job(emb, strength)
+        return K.linprobe_proba(q, self._Wx[j:j + 1], self._bx[j:j + 1], self.num_classes)[0][0]
+
+    def _all_rows_job(self, emb: torch.Tensor, strength: Optional[float]):
+        """(the all-rows job of `strength`, emb's rows prepared with the pool's mean)."""
+        self._fitted()
+        self._rows(emb, "emb", self._Wx.shape[2])
+        j = self.n_folds_ * len(self.strengths) + self._strength_index(strength)
+        return j, self._prepare(emb.detach().to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous())
