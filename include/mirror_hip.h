@@ -1341,6 +1341,80 @@ int mh_survprobe_grad(const float* y, int64_t n, int D, const float* Wz, const f
  * Grid ceil(nq / 128) x ceil(S Mp / 128). */
 int mh_survprobe_risk(const float* q, int64_t nq, int D, const float* W, const float* b, int S, int M, int Mp, float* risk, mh_stream s);
 
+/* ---------------------------------------------------------------- cross-validated recursive gene elimination (csrc/geneselect.hip,
+ * the step in csrc/linprobe.hip; mirror_amd/geneselect.py; the reference's tools/distill_rna_feature.py:121-132:
+ * RFECV(LinearSVC(), step=0.05, cv=StratifiedKFold(5), scoring="accuracy") over the cohort's transcripts).  J = folds + 1 jobs over the
+ * SAME prepared rows y [n x D] f32 contiguous, each C one-vs-rest squared-hinge machines (also for C = 2) with a per-job mask
+ * uint8 [J x D] of the features still in play; per job j
+ *   F_j(W, b) = r_j sum_{i in train_j} sum_{c < C} max(0, 1 - t_ic v_ic)^2 + (lambda_j / 2) |W o mask_j|^2      (the bias is not penalised)
+ *   t_ic = +1 if label_i = c else -1,   v = W y_i + b,   train_j = { i : label_i in [0, C), fold_i >= 0, fold_i != heldout_j }
+ * With lambda_j = 1 / (svm_c n_train_j) this has the minimiser of LinearSVC(C = svm_c) up to the bias: liblinear penalises it, and
+ * fit_intercept = 0 (the bias pinned to 0) is the setting under which the two agree exactly.  One FISTA iteration is mh_gsel_grad then
+ * mh_gsel_step; a round ends with mh_gsel_eliminate.  Layout as mh_linprobe_*: Cp = the next power of two >= C, weights f32
+ * [J x Cp x D], bias f32 [J x Cp]; no entry point reads what a pad slot c >= C holds, and the weights of an eliminated feature are
+ * exactly 0 and stay 0.  Every entry point is deterministic (fixed summation order, no float atomics), allocates nothing and never
+ * waits on the host.  Shared limits: 2 <= C <= 64, 1 <= D <= 2^18, 1 <= n <= 2^20, J Cp <= 2^20, n J Cp <= 2^28.
+ *
+ * mu, rstd f32 [D] of x [n x D] f32 contiguous: the column sums as mh_colmean forms them (up to 128 strips of at least 64 rows, each
+ * summed in row order in f64, the strips added in strip order), mu = sum / n rounded to f32 once; then a second pass in the same
+ * order over the squares of the centred values (double)x - (double)mu: var = sum / n (population, ddof = 0), rstd = 1 / sqrt(var) rounded
+ * to f32 once, and 0 where var is not positive (a constant column: mu is exact and var is exactly 0).  Four launches, grids
+ * ceil(D / 256) x strips and ceil(D / 256).  workspace: mh_colstats_workspace_bytes(n, D) bytes (8 D per strip), 8-byte aligned, nothing
+ * to zero.  2 n D 4 bytes read. */
+int mh_colstats(const float* x, int64_t n, int D, float* mu, float* rstd, void* workspace, mh_stream s);
+int64_t mh_colstats_workspace_bytes(int64_t n, int D);
+/* y[i, d] = (x[i, d] - mu[d]) * rstd[d], a subtraction and a multiplication in f32; y may be x.  Grid ceil(D / 256) x min(n, 4096);
+ * n D 4 bytes read and written. */
+int mh_standardize(const float* x, const float* mu, const float* rstd, float* y, int64_t n, int D, mh_stream s);
+/* out f32 [J x n], STORED: out[j, i] = the sum of y[i, d]^2 over the d with mask[j, d] != 0.  One wave per row: a lane adds the squares
+ * of its active columns d = lane, lane + 64, .. in that order (fmaf from 0), the lanes are added by the fixed butterfly of
+ * mh_center_l2norm.  J <= 2^19, n J <= 2^28.  Grid ceil(n / 4) x min(J, 1024); J n D 4 bytes read (a row's later jobs from cache). */
+int mh_gsel_rowsq(const float* y, int64_t n, int D, const uint8_t* mask, int J, float* out, mh_stream s);
+/* G f32 [n x J Cp], STORED (nothing to zero): G[i, j Cp + c] = -2 r_j t_ic max(0, 1 - t_ic v_ic) for i in train_j and c < C; exactly 0
+ * for every other row, for pad columns and where the hinge is inactive.  v_ic = dot(y_i, Wz[j, c]) + bz[j, c], formed in two
+ * launches.  First: the J Cp weight rows are the keys of the retrieval kernels' exact-f32 128 x 128 tile product
+ * (v_mfma_f32_32x32x2_f32) with the contraction cut into Z = mh_gsel_slices(n, J Cp, D) slices of ks columns; slice z is ONE k-ordered
+ * f32 fmaf chain from 0 over the columns [z ks, min(D, (z + 1) ks)) and is stored to workspace [Z x n x J Cp]; grid ceil(n / 128) x
+ * ceil(J Cp / 128) x Z.  The slicing depends on the shape alone, never on the device: with T = ceil(n / 128) ceil(J Cp / 128) tiles,
+ * z0 = min(ceil(D / 256), clamp(floor(768 / T), 1, 128)), ks = ceil(D / z0) rounded up to a multiple of 16, Z = ceil(D / ks)
+ * (768 = 256 CUs x 3 resident workgroups of 35 KB of LDS; a slice is at least 16 stages of the product; Z = 1 for D <= 256).
+ * Second: one thread per (row, job) adds the slices in slice order from slice 0 (f32), then ONE f32 add of the bias; m = 1 - v for the
+ * row's class and 1 + v for the others, exact roundings of 1 - t v; the hinge h = m where m > 0 or m is NaN, else 0;
+ * G = -(2 r_j h) / +(2 r_j h), one rounding.  labels int64 [n] (8-byte aligned), fold int32 [n], heldout int32 [J], rscale f32 [J] (r_j).
+ * loss_part f64 [ceil(n / 128) x J] (8-byte aligned) or NULL: loss_part[t, j] = r_j sum over the training rows of row tile t, added
+ * in row order in f64, of sum_c h^2 (an f32 fmaf chain from 0 in class order); the sum over t is the data term of F_j at (Wz, bz).
+ * pred int32 [J x n] or NULL, STORED for EVERY row, in train or not: the class of the largest v_c under mh_fewshot_predict's rule (a
+ * NaN is not eligible, equal values go to the smaller class, -1 when none is eligible).  A NaN in a row makes pred -1 and the G rows
+ * and the loss NaN for exactly the jobs that train on it.  workspace: mh_gsel_grad_workspace_bytes(n, J, Cp, D) bytes, 4-byte aligned,
+ * nothing to zero.  Second grid ceil(n / 128) x ceil(J / 16).
+ * Z (n + J Cp) ks 4 bytes read per tile row / column, Z n J Cp 4 written and read back, n J Cp 4 written. */
+int mh_gsel_grad(const float* y, int64_t n, int D, const float* Wz, const float* bz, const int64_t* labels, const int32_t* fold,
+                 const int32_t* heldout, const float* rscale, int J, int C, int Cp, float* G, double* loss_part, int32_t* pred,
+                 void* workspace, mh_stream s);
+int64_t mh_gsel_grad_workspace_bytes(int64_t n, int J, int Cp, int D);
+/* Z above for nk = J Cp keys; 0 outside the limits.  No stream, nothing launched. */
+int mh_gsel_slices(int64_t n, int nk, int D);
+/* mh_linprobe_step (the same kernel, the mask a template parameter: with a mask of ones and fit_intercept = 1 the two agree bit for
+ * bit) with mask uint8 [J x D], shared by a job's classes, and fit_intercept in {0, 1}.  A (job, column) with mask = 0 is neither read
+ * for the update nor written (Wx, Wz keep what they hold) and takes no part in gmax_part; with fit_intercept = 0 the same holds for bx /
+ * bz and the bias gradient.  The contraction over the rows still walks every column tile: the active columns are not compacted.
+ * D up to 2^18.  gmax_part f32 [ceil((D + 1) / 128) x J], STORED, or NULL.  Grid ceil(J Cp / 128) x ceil((D + 1) / 128).
+ * n (J Cp + D) 4 bytes read per tile, 4 J C (D + 1) 4 bytes read and written at the most, J D mask bytes read. */
+int mh_gsel_step(const float* y, int64_t n, int D, const float* G, float* Wx, float* bx, float* Wz, float* bz, const float* lam,
+                 const float* eta, float beta, const uint8_t* mask, int fit_intercept, int J, int C, int Cp, float* gmax_part,
+                 mh_stream s);
+/* Drop the k least important active features of every job.  imp[j, d] = the f32 fmaf chain from 0 of Wx[j, c, d]^2 in class order
+ * c < C, over the d with mask[j, d] != 0.  The k active features with the smallest key (bits of imp as uint32, then d) are removed:
+ * equal importances go by the smaller index first, +inf sorts above every number and a NaN above +inf.  For a removed feature
+ * mask[j, d] = 0, elim_round[j, d] = round (int32 [J x D]; the caller starts it at -1; round >= 0) and Wx, Wz[j, c < C, d] = 0; nothing
+ * else is written.  k = 0 removes nothing; k >= the job's active count removes every active feature.  importance f32 [J x D] or NULL,
+ * STORED: imp as formed, 0 for inactive features (the state BEFORE the removal).  Integer decisions only: one workgroup of 1024
+ * threads per job finds the k-th smallest key by a radix select over the key bits (four passes of 8 bits, LDS histograms with integer
+ * atomics) and then walks the features in index order, breaking the tie at the threshold by prefix counts (ballots, wave counts in
+ * LDS); no sort, no workspace.  Grid J; 6 J C D 4 bytes read at the most (imp is formed again in every pass), J D 9 written at the most. */
+int mh_gsel_eliminate(float* Wx, float* Wz, uint8_t* mask, int32_t* elim_round, int J, int C, int Cp, int D, int k, int round,
+                      float* importance, mh_stream s);
+
 #ifdef __cplusplus
 }
 #endif

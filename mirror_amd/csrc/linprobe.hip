@@ -240,12 +240,16 @@ __device__ __forceinline__ void lp_store(const f4_t (&r)[LP_QUADS], float* __res
     }
 }
 
+// MASKED (mh_gsel_step): a (job, column) with mask[job, column] = 0 is neither read for the update nor written and takes no part in the
+// maximum; fit_intercept = 0 does the same to the bias column.  MASKED = false is mh_linprobe_step: both arguments are unused.
+template <bool MASKED>
 __global__ void __launch_bounds__(RT_THREADS, 2) linprobe_step_kernel(const float* __restrict__ y, const float* __restrict__ G,
                                                                       float* __restrict__ Wx, float* __restrict__ bx,
                                                                       float* __restrict__ Wz, float* __restrict__ bz,
                                                                       const float* __restrict__ lam, const float* __restrict__ eta,
                                                                       float beta, int n, int nk, int D, int C, int cshift, int vec_g,
-                                                                      int vec_y, float* __restrict__ gmax_part) {
+                                                                      int vec_y, float* __restrict__ gmax_part,
+                                                                      const uint8_t* __restrict__ mask, int fit_intercept) {
     __shared__ __attribute__((aligned(16))) float s_g[2][LP_BK * LP_LD];
     __shared__ __attribute__((aligned(16))) float s_y[2][LP_BK * LP_LD];
     __shared__ unsigned s_max[RT_TILE];                   // bits of max |g| per key row of the tile
@@ -322,6 +326,7 @@ __global__ void __launch_bounds__(RT_THREADS, 2) linprobe_step_kernel(const floa
                 const int col = col0 + wn * 64 + j * 32 + (lane & 31);
                 if (col > D) continue;
                 const bool isb = col == D;
+                if (MASKED && (isb ? !fit_intercept : !mask[(int64_t)job * D + col])) continue;
                 float* px = isb ? bx + key : Wx + (int64_t)key * D + col;
                 float* pz = isb ? bz + key : Wz + (int64_t)key * D + col;
                 const float z = *pz, x = *px;
@@ -350,11 +355,11 @@ __global__ void __launch_bounds__(RT_THREADS, 2) linprobe_step_kernel(const floa
 }
 
 // the limits both entry points share; 0: fine
-int linprobe_geometry(const char* who, int64_t n, int D, int J, int C, int Cp) {
+int linprobe_geometry(const char* who, int64_t n, int D, int J, int C, int Cp, int maxd = LP_MAXD) {
     MH_REQUIRE(C >= 2 && C <= LP_MAXC, "%s: C = %d outside [2, %d]", who, C, LP_MAXC);
     MH_REQUIRE(Cp >= C && Cp <= LP_MAXC && (Cp & (Cp - 1)) == 0 && Cp < 2 * C, "%s: Cp = %d is not the next power of two >= C = %d", who,
                Cp, C);
-    MH_REQUIRE(D >= 1 && D <= LP_MAXD, "%s: D = %d outside [1, %d]", who, D, LP_MAXD);
+    MH_REQUIRE(D >= 1 && D <= maxd, "%s: D = %d outside [1, %d]", who, D, maxd);
     MH_REQUIRE(n >= 1 && n <= (1 << 20), "%s: n = %lld outside [1, 2^20]", who, (long long)n);
     MH_REQUIRE(J >= 1 && (int64_t)J * Cp <= (1 << 20), "%s: J = %d jobs of Cp = %d keys outside [1, 2^20] keys", who, J, Cp);
     MH_REQUIRE(n * J * Cp <= (1ll << 28), "%s: n J Cp = %lld x %d x %d logit gradients, 2^28 at the most", who, (long long)n, J, Cp);
@@ -391,9 +396,27 @@ extern "C" int mh_linprobe_step(const float* y, int64_t n, int D, const float* G
     const int nk = J * Cp;
     const int vec_g = nk % 4 == 0 && mh_quad_ok(G, 4);
     const int vec_y = D % 4 == 0 && mh_quad_ok(y, 4);
-    hipLaunchKernelGGL(linprobe_step_kernel, dim3(mh_cdiv(nk, RT_TILE), mh_cdiv(D + 1, RT_TILE)), dim3(RT_THREADS), 0, (hipStream_t)s, y, G,
-                       Wx, bx, Wz, bz, lam, eta, beta, (int)n, nk, D, C, lp_shift(Cp), vec_g, vec_y, gmax_part);
+    hipLaunchKernelGGL(linprobe_step_kernel<false>, dim3(mh_cdiv(nk, RT_TILE), mh_cdiv(D + 1, RT_TILE)), dim3(RT_THREADS), 0, (hipStream_t)s,
+                       y, G, Wx, bx, Wz, bz, lam, eta, beta, (int)n, nk, D, C, lp_shift(Cp), vec_g, vec_y, gmax_part,
+                       (const uint8_t*)nullptr, 1);
     MH_LAUNCH_CHECK("mh_linprobe_step");
+    return MH_OK;
+}
+
+// geneselect.hip's step: the kernel above with the mask, at that file's limits (D up to 2^18)
+extern "C" int mh_gsel_step(const float* y, int64_t n, int D, const float* G, float* Wx, float* bx, float* Wz, float* bz, const float* lam,
+                            const float* eta, float beta, const uint8_t* mask, int fit_intercept, int J, int C, int Cp, float* gmax_part,
+                            mh_stream s) {
+    if (int rc = linprobe_geometry("mh_gsel_step", n, D, J, C, Cp, 1 << 18)) return rc;
+    MH_REQUIRE(beta >= 0.f && beta <= 1.f, "mh_gsel_step: beta = %g outside [0, 1]", (double)beta);
+    MH_REQUIRE(fit_intercept == 0 || fit_intercept == 1, "mh_gsel_step: fit_intercept = %d is neither 0 nor 1", fit_intercept);
+    MH_REQUIRE(y && G && Wx && bx && Wz && bz && lam && eta && mask, "mh_gsel_step: null pointer");
+    const int nk = J * Cp;
+    const int vec_g = nk % 4 == 0 && mh_quad_ok(G, 4);
+    const int vec_y = D % 4 == 0 && mh_quad_ok(y, 4);
+    hipLaunchKernelGGL(linprobe_step_kernel<true>, dim3(mh_cdiv(nk, RT_TILE), mh_cdiv(D + 1, RT_TILE)), dim3(RT_THREADS), 0, (hipStream_t)s,
+                       y, G, Wx, bx, Wz, bz, lam, eta, beta, (int)n, nk, D, C, lp_shift(Cp), vec_g, vec_y, gmax_part, mask, fit_intercept);
+    MH_LAUNCH_CHECK("mh_gsel_step");
     return MH_OK;
 }
 

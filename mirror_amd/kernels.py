@@ -3183,3 +3183,192 @@ def cluster_match(cont: torch.Tensor):
     hits = torch.empty((R,), device=cont.device, dtype=torch.int64)
     _lib.call("mh_cluster_match", _p(cont), R, K, C, _p(match), _p(hits), stream=_stream())
     return match, hits
+
+
+# ----------------------------------------------------------------------------- recursive gene elimination: J squared-hinge jobs at once (csrc/geneselect.hip)
+def _gs_f32(t: torch.Tensor, what: str, device: bool = True) -> torch.Tensor:
+    """_fs_f32 at the limits of the gsel entry points (D up to 2^18)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+        got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{what} must be f32 [n, D], got {got}")
+    if device:
+        _chk(t)
+    n, D = t.shape
+    if not (1 <= n <= (1 << 20)) or not (1 <= D <= (1 << 18)):
+        raise MirrorHipError(f"{what}: n = {n} (1..2^20), D = {D} (1..2^18)")
+    return t.detach().contiguous()
+
+
+def _gs_state(y: torch.Tensor, W: torch.Tensor, b: torch.Tensor, C: int, who: str):
+    """_lp_state at the limits of the gsel entry points."""
+    y = _gs_f32(y, f"{who}: y", device=False)
+    n, D = y.shape
+    if isinstance(C, bool) or not isinstance(C, int) or not (2 <= C <= 64):
+        raise ValueError(f"{who}: C must be an int in [2, 64], got {C!r}")
+    Cp = fewshot_cp(C)
+    if not isinstance(W, torch.Tensor) or W.dtype != torch.float32 or W.dim() != 3 or tuple(W.shape[1:]) != (Cp, D):
+        raise ValueError(f"{who}: the weights must be f32 [J, {Cp}, {D}]")
+    J = W.shape[0]
+    if not isinstance(b, torch.Tensor) or b.dtype != torch.float32 or tuple(b.shape) != (J, Cp):
+        raise ValueError(f"{who}: the bias must be f32 [{J}, {Cp}]")
+    _chk(y, W, b)
+    if not (1 <= J and J * Cp <= (1 << 20)) or n * J * Cp > (1 << 28):
+        raise MirrorHipError(f"{who}: J = {J} jobs of {Cp} keys over n = {n} rows (J * Cp <= 2^20, n * J * Cp <= 2^28)")
+    _contig(W, f"{who}: the weights")
+    _contig(b, f"{who}: the bias")
+    return y, n, D, J, Cp
+
+
+def _gs_mask(mask, J: int, D: int, who: str) -> torch.Tensor:
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != (J, D) or not mask.is_contiguous():
+        raise ValueError(f"{who}: mask must be a contiguous uint8 [{J}, {D}]")
+    return mask
+
+
+def colstats(x: torch.Tensor):
+    """(mu f32 [D], rstd f32 [D]) on the device (no sync): the column means and reciprocal population standard deviations of x f32 [n, D],
+    summed in a fixed order in f64, rstd = 0 for a constant column (mh_colstats)."""
+    x = _gs_f32(x, "colstats: x")
+    n, D = x.shape
+    mu = torch.empty((D,), device=x.device, dtype=torch.float32)
+    rstd = torch.empty((D,), device=x.device, dtype=torch.float32)
+    ws = torch.empty((int(_lib.load().mh_colstats_workspace_bytes(n, D)) // 8,), device=x.device, dtype=torch.float64)
+    _lib.call("mh_colstats", _p(x), n, D, _p(mu), _p(rstd), _p(ws), stream=_stream())
+    return mu, rstd
+
+
+def standardize(x: torch.Tensor, mu: torch.Tensor, rstd: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """f32 [n, D]: (x - mu) * rstd (mh_standardize).  out may be x itself (in place)."""
+    x = _gs_f32(x, "standardize: x", device=False)
+    n, D = x.shape
+    for t, name in ((mu, "mu"), (rstd, "rstd")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (D,):
+            raise ValueError(f"standardize: {name} must be f32 [{D}]")
+    if out is None:
+        out = torch.empty_like(x)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (n, D) or not out.is_contiguous():
+        raise ValueError(f"standardize: out must be a contiguous f32 [{n}, {D}]")
+    _chk(x, mu, rstd, out)
+    _lib.call("mh_standardize", _p(x), _p(mu.contiguous()), _p(rstd.contiguous()), _p(out), n, D, stream=_stream())
+    return out
+
+
+def gsel_rowsq(y: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """f32 [J, n] on the device (no sync): every row's sum of squares over the columns with mask[j, d] != 0 (mh_gsel_rowsq)."""
+    y = _gs_f32(y, "gsel_rowsq: y", device=False)
+    n, D = y.shape
+    if not isinstance(mask, torch.Tensor) or mask.dim() != 2:
+        raise ValueError(f"gsel_rowsq: mask must be a contiguous uint8 [J, {D}]")
+    J = mask.shape[0]
+    _gs_mask(mask, J, D, "gsel_rowsq")
+    _chk(y, mask)
+    if not (1 <= J <= (1 << 19)) or n * J > (1 << 28):
+        raise MirrorHipError(f"gsel_rowsq: J = {J} jobs over n = {n} rows (J <= 2^19, n * J <= 2^28)")
+    out = torch.empty((J, n), device=y.device, dtype=torch.float32)
+    _lib.call("mh_gsel_rowsq", _p(y), n, D, _p(mask), J, _p(out), stream=_stream())
+    return out
+
+
+def gsel_slices(n: int, nk: int, D: int) -> int:
+    """The slices mh_gsel_grad cuts the contraction over D into for n rows and nk = J Cp keys (mh_gsel_slices; 0 outside the limits)."""
+    return int(_lib.load().mh_gsel_slices(int(n), int(nk), int(D)))
+
+
+def gsel_workspace(n: int, J: int, Cp: int, D: int, device) -> torch.Tensor:
+    """The f32 workspace of mh_gsel_grad for this shape (mh_gsel_grad_workspace_bytes); nothing to zero."""
+    nbytes = int(_lib.load().mh_gsel_grad_workspace_bytes(int(n), int(J), int(Cp), int(D)))
+    if nbytes <= 0:
+        raise MirrorHipError(f"gsel_workspace: n = {n}, J = {J}, Cp = {Cp}, D = {D} outside the limits of mh_gsel_grad")
+    return torch.empty((nbytes // 4,), device=device, dtype=torch.float32)
+
+
+def gsel_grad(y: torch.Tensor, Wz: torch.Tensor, bz: torch.Tensor, labels: torch.Tensor, fold: torch.Tensor, heldout: torch.Tensor,
+              rscale: torch.Tensor, C: int, G: Optional[torch.Tensor] = None, want_loss: bool = False, want_pred: bool = False,
+              workspace: Optional[torch.Tensor] = None):
+    """(G f32 [n, J Cp], loss_part f64 [ceil(n / 128), J] or None, pred int32 [J, n] or None) on the device (no sync): every job's
+    squared-hinge logit gradient -2 r_j t max(0, 1 - t v) over its training rows, 0 elsewhere and in the pad columns; the per-row-tile
+    data terms; the class of the largest v_c of EVERY row (mh_gsel_grad).  G and the workspace (gsel_workspace) may be passed."""
+    y, n, D, J, Cp = _gs_state(y, Wz, bz, C, "gsel_grad")
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or tuple(labels.shape) != (n,):
+        raise ValueError(f"gsel_grad: labels must be int64 [{n}]")
+    if not isinstance(fold, torch.Tensor) or fold.dtype != torch.int32 or tuple(fold.shape) != (n,):
+        raise ValueError(f"gsel_grad: fold must be int32 [{n}]")
+    _chk(labels, fold)
+    heldout = _lp_vec(heldout, torch.int32, J, "gsel_grad: heldout")
+    rscale = _lp_vec(rscale, torch.float32, J, "gsel_grad: rscale")
+    if G is None:
+        G = torch.empty((n, J * Cp), device=y.device, dtype=torch.float32)
+    elif not isinstance(G, torch.Tensor) or G.dtype != torch.float32 or tuple(G.shape) != (n, J * Cp) or not G.is_contiguous():
+        raise ValueError(f"gsel_grad: G must be a contiguous f32 [{n}, {J * Cp}]")
+    need = int(_lib.load().mh_gsel_grad_workspace_bytes(n, J, Cp, D)) // 4
+    if workspace is None:
+        workspace = torch.empty((need,), device=y.device, dtype=torch.float32)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32 or workspace.dim() != 1
+          or workspace.numel() < need or not workspace.is_contiguous()):
+        raise ValueError(f"gsel_grad: workspace must be a contiguous f32 [{need}] at the least")
+    _chk(G, workspace)
+    loss_part = torch.empty(((n + 127) // 128, J), device=y.device, dtype=torch.float64) if want_loss else None
+    pred = torch.empty((J, n), device=y.device, dtype=torch.int32) if want_pred else None
+    _lib.call("mh_gsel_grad", _p(y), n, D, _p(Wz), _p(bz), _p(labels.contiguous()), _p(fold.contiguous()), _p(heldout), _p(rscale),
+              J, C, Cp, _p(G), _p(loss_part), _p(pred), _p(workspace), stream=_stream())
+    return G, loss_part, pred
+
+
+def gsel_step(y: torch.Tensor, G: torch.Tensor, Wx: torch.Tensor, bx: torch.Tensor, Wz: torch.Tensor, bz: torch.Tensor,
+              lam: torch.Tensor, eta: torch.Tensor, beta: float, mask: torch.Tensor, fit_intercept: bool, C: int,
+              gmax_part: Optional[torch.Tensor] = None, want_gmax: bool = False):
+    """linprobe_step under a feature mask uint8 [J, D] IN PLACE (no sync): a masked (job, column) is neither read nor written and takes
+    no part in gmax_part; fit_intercept=False does the same to the bias (mh_gsel_step).  Returns gmax_part or None."""
+    y, n, D, J, Cp = _gs_state(y, Wz, bz, C, "gsel_step")
+    _gs_state(y, Wx, bx, C, "gsel_step")
+    if Wx.shape[0] != J:
+        raise ValueError(f"gsel_step: Wx has {Wx.shape[0]} jobs, Wz {J}")
+    if not isinstance(G, torch.Tensor) or G.dtype != torch.float32 or tuple(G.shape) != (n, J * Cp) or not G.is_contiguous():
+        raise ValueError(f"gsel_step: G must be a contiguous f32 [{n}, {J * Cp}]")
+    _chk(G)
+    lam = _lp_vec(lam, torch.float32, J, "gsel_step: lam")
+    eta = _lp_vec(eta, torch.float32, J, "gsel_step: eta")
+    beta = float(beta)
+    if not (0.0 <= beta <= 1.0):
+        raise ValueError(f"gsel_step: beta must lie in [0, 1], got {beta!r}")
+    _gs_mask(mask, J, D, "gsel_step")
+    if not isinstance(fit_intercept, bool):
+        raise ValueError(f"gsel_step: fit_intercept must be a bool, got {fit_intercept!r}")
+    tiles = (D + 1 + 127) // 128
+    if gmax_part is None and want_gmax:
+        gmax_part = torch.empty((tiles, J), device=y.device, dtype=torch.float32)
+    elif gmax_part is not None and (not isinstance(gmax_part, torch.Tensor) or gmax_part.dtype != torch.float32
+                                    or tuple(gmax_part.shape) != (tiles, J) or not gmax_part.is_contiguous()):
+        raise ValueError(f"gsel_step: gmax_part must be a contiguous f32 [{tiles}, {J}]")
+    _chk(mask, gmax_part)
+    _lib.call("mh_gsel_step", _p(y), n, D, _p(G), _p(Wx), _p(bx), _p(Wz), _p(bz), _p(lam), _p(eta), beta, _p(mask), int(fit_intercept),
+              J, C, Cp, _p(gmax_part), stream=_stream())
+    return gmax_part
+
+
+def gsel_eliminate(Wx: torch.Tensor, Wz: torch.Tensor, mask: torch.Tensor, elim_round: torch.Tensor, k: int, round: int, C: int,
+                   want_importance: bool = False):
+    """Drop every job's k least important active features IN PLACE (no sync): mask 0, elim_round = round, Wx / Wz columns 0
+    (mh_gsel_eliminate: importance = sum_c Wx[j, c, d]^2, ties to the smaller index, integer decisions only).  Returns importance f32
+    [J, D] (before the removal, 0 for inactive features) or None."""
+    if isinstance(C, bool) or not isinstance(C, int) or not (2 <= C <= 64):
+        raise ValueError(f"gsel_eliminate: C must be an int in [2, 64], got {C!r}")
+    Cp = fewshot_cp(C)
+    if not isinstance(Wx, torch.Tensor) or Wx.dtype != torch.float32 or Wx.dim() != 3 or Wx.shape[1] != Cp or not Wx.is_contiguous():
+        raise ValueError(f"gsel_eliminate: Wx must be a contiguous f32 [J, {Cp}, D]")
+    J, _, D = Wx.shape
+    if not isinstance(Wz, torch.Tensor) or Wz.dtype != torch.float32 or tuple(Wz.shape) != (J, Cp, D) or not Wz.is_contiguous():
+        raise ValueError(f"gsel_eliminate: Wz must be a contiguous f32 [{J}, {Cp}, {D}]")
+    _gs_mask(mask, J, D, "gsel_eliminate")
+    if (not isinstance(elim_round, torch.Tensor) or elim_round.dtype != torch.int32 or tuple(elim_round.shape) != (J, D)
+            or not elim_round.is_contiguous()):
+        raise ValueError(f"gsel_eliminate: elim_round must be a contiguous int32 [{J}, {D}]")
+    for v, name in ((k, "k"), (round, "round")):
+        if isinstance(v, bool) or not isinstance(v, int) or not (0 <= v < (1 << 31)):
+            raise ValueError(f"gsel_eliminate: {name} must be a non-negative int, got {v!r}")
+    _chk(Wx, Wz, mask, elim_round)
+    if not (1 <= D <= (1 << 18)) or not (1 <= J and J * Cp <= (1 << 20)):
+        raise MirrorHipError(f"gsel_eliminate: J = {J} jobs of {Cp} keys, D = {D} (J * Cp <= 2^20, D in 1..2^18)")
+    imp = torch.empty((J, D), device=Wx.device, dtype=torch.float32) if want_importance else None
+    _lib.call("mh_gsel_eliminate", _p(Wx), _p(Wz), _p(mask), _p(elim_round), J, C, Cp, D, k, round, _p(imp), stream=_stream())
+    return imp
