@@ -1341,6 +1341,49 @@ int mh_survprobe_grad(const float* y, int64_t n, int D, const float* Wz, const f
  * Grid ceil(nq / 128) x ceil(S Mp / 128). */
 int mh_survprobe_risk(const float* q, int64_t nq, int D, const float* W, const float* b, int S, int M, int Mp, float* risk, mh_stream s);
 
+/* ---------------------------------------------------------------- ridge Cox probe of frozen embeddings (csrc/coxprobe.hip, the step in
+ * csrc/linprobe.hip; mirror_amd/coxprobe.py: the L2-penalised Cox proportional-hazards model on the frozen slide embedding that
+ * slide-encoder benchmarks report, strength chosen over folds, scored by the c-index).  J independent regressions over the SAME prepared
+ * rows y [n x D] f32 contiguous, SORTED by time, non-increasing (NaN times last); job j has one weight row w_j in R^D and no intercept
+ * (the partial likelihood does not see one).  With scores v_i = dot(y_i, w_j), the definitions are those of the Cox block above
+ * restricted to the job's training rows train_j = { i : event_i in {0, 1}, time_i not NaN, fold_i >= 0, fold_i != heldout_j }
+ * (a_ij = [i in train_j], e_i = [event_i = 1]):
+ *   m_j = max_{train_j} v,   w_k = a_kj exp(v_k - m_j) in f64
+ *   S_i = sum_{t_k >= t_i} w_k     D_i = sum_k [t_k = t_i] a_kj e_k w_k     d_i = sum_k [t_k = t_i] a_kj e_k
+ *   l_i = sum_{k < i} [t_k = t_i] a_kj e_k     f_i = 0 (MH_COX_BRESLOW), l_i / d_i (MH_COX_EFRON)     den_i = S_i - f_i D_i
+ *   F_j(w) = r_j sum_i a_ij e_i (log den_i + m_j - v_i) + (lambda_j / 2) |w|^2
+ *   g_k = dF_j / dv_k = r_j a_kj [ w_k sum_i q_i ([t_k > t_i] + [t_k = t_i](1 - e_k f_i)) - e_k ],   q_i = a_ij e_i / den_i
+ * With r_j = 1 / |train_j| this has the minimiser of sksurv's CoxPHSurvivalAnalysis(alpha = lambda_j |train_j|).  One FISTA iteration
+ * is mh_coxprobe_scores, mh_coxprobe_grad, mh_coxprobe_step.  All three are deterministic (fixed summation order, no float atomics),
+ * allocate nothing and never wait on the host.
+ *
+ * V f32 [J x nq], job-major, STORED: V[j, i] = dot(q_i, W[j]), the k-ordered f32 fmaf chain from 0 of the retrieval kernels' exact-f32
+ * 128 x 128 tile product with the J weight rows W f32 [J x D] as the keys (no pad slots).  1 <= D <= 4096, 1 <= nq <= 2^20,
+ * 1 <= J <= 2^20, nq J <= 2^28.  Grid ceil(nq / 128) x ceil(J / 128); (nq + J) D 4 bytes read per tile row / column, nq J 4 written. */
+int mh_coxprobe_scores(const float* q, int64_t nq, int D, const float* W, int J, float* V, mh_stream s);
+/* G f32 [n x J] row-major (the layout mh_coxprobe_step reads), STORED: G[k, j] = g_k of job j; exactly 0 on every row outside train_j,
+ * whatever V holds there; NaN on the rows of train_j when a score of train_j is NaN (no other job is touched).  loss f64 [J], STORED:
+ * the data term r_j sum_i ..., 0 for a job without training events.  V f32 [J x n] as mh_coxprobe_scores leaves it.  Input contract:
+ * the rows are in non-increasing time order and rows with a NaN time come last; time f64 [n], tie groups are runs of equal times (a
+ * NaN time is a group of its own and trains nowhere); event uint8 [n] (0 censored, 1 event, anything else: the row trains nowhere);
+ * fold int32 [n]; heldout int32 [J]; rscale f32 [J] (r_j); ties MH_COX_BRESLOW / MH_COX_EFRON.  On sorted rows S_i is a prefix sum
+ * read at the last row of i's tie group and sum_{t_i <= t_k} q_i a suffix sum read at the first row of k's: one workgroup of 256
+ * threads per job walks its column of V in three fixed-order block scans (thread t owns the contiguous rows [t c, (t + 1) c),
+ * c = ceil(n / 256); the 256 chunk summaries are folded in thread order by one thread).  Every sum, exp and log is f64, only the
+ * stores to G round to f32.  Limits: 1 <= n <= 65536, n J <= 2^24, max - min of a job's training scores <= 700 (the Cox block's
+ * domain).  time, loss and workspace 8-byte aligned; workspace: mh_coxprobe_workspace_bytes(n, J) bytes (28 per score: w, two scan
+ * rows and the event counts), nothing to zero; -1 outside the limits.  Grid J. */
+int mh_coxprobe_grad(const float* V, int64_t n, int J, const double* time, const uint8_t* event, const int32_t* fold,
+                     const int32_t* heldout, const float* rscale, int ties, float* G, double* loss, void* workspace, mh_stream s);
+int64_t mh_coxprobe_workspace_bytes(int64_t n, int J);
+/* mh_linprobe_step's kernel with one key per job (C = Cp = 1) and no bias column: g = G^T y + lambda_j Wz (ONE row-ordered f32 fmaf
+ * chain from 0 per element, then fmaf(lambda_j, Wz, .)), X' = fmaf(-eta_j, g, Wz), Z' = fmaf(beta, X' - X, X'), stored over Wx / Wz
+ * f32 [J x D] in place.  With a second, zero key per job, a mask of ones and fit_intercept = 0, mh_gsel_step at C = 2 forms the same
+ * bits.  gmax_part f32 [ceil((D + 1) / 128) x J], STORED, or NULL: max |g| per column tile and job (0 from a tile that holds the
+ * unused bias column alone).  1 <= D <= 4096, 1 <= n <= 65536, n J <= 2^24, 0 <= beta <= 1.  Grid ceil(J / 128) x ceil((D + 1) / 128). */
+int mh_coxprobe_step(const float* y, int64_t n, int D, const float* G, float* Wx, float* Wz, const float* lam, const float* eta,
+                     float beta, int J, float* gmax_part, mh_stream s);
+
 /* ---------------------------------------------------------------- cross-validated recursive gene elimination (csrc/geneselect.hip,
  * the step in csrc/linprobe.hip; mirror_amd/geneselect.py; the reference's tools/distill_rna_feature.py:121-132:
  * RFECV(LinearSVC(), step=0.05, cv=StratifiedKFold(5), scoring="accuracy") over the cohort's transcripts).  J = folds + 1 jobs over the

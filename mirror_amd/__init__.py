@@ -7,15 +7,15 @@ and metrics of train_subtyping.py in `losses` and `metrics`; the zero-shot retri
 neighbours of the alignment heads in `retrieval`; the kNN probe of frozen embeddings in `knn`, the few-shot prototype probe in
 `fewshot`, the label-free cluster probe (k-means scored with NMI, ARI and purity) in `cluster`, the cross-validated linear
 probe (softmax regression over folds and L2 strengths) in `linprobe` and its survival counterpart (hazard regression scored with the
-censored concordance index) in `survprobe`; the upstream choice of transcripts, cross-validated recursive gene elimination
-(RFECV over squared-hinge machines), in `geneselect`);
+censored concordance index) in `survprobe`, with the cross-validated ridge Cox probe on the follow-up time itself in `coxprobe`;
+the upstream choice of transcripts, cross-validated recursive gene elimination (RFECV over squared-hinge machines), in `geneselect`);
 all arithmetic runs in hand-written HIP kernels behind the C ABI of `include/mirror_hip.h` (`mirror_amd/lib/libmirror_hip.so`).  There is no CPU fallback.
 """
 from ._lib import MirrorHipError, LIB_PATH  # noqa: F401
 
 __version__ = "0.1.0"
 
-__all__ = ["MirrorHipError", "LIB_PATH", "FewShotProbe", "ClusterProbe", "LinearProbe", "SurvivalProbe", "GeneSelect", "install_aliases"]
+__all__ = ["MirrorHipError", "LIB_PATH", "FewShotProbe", "ClusterProbe", "LinearProbe", "SurvivalProbe", "CoxProbe", "GeneSelect", "install_aliases"]
 
 
 def __getattr__(name: str):
@@ -32,6 +32,9 @@ def __getattr__(name: str):
     if name == "SurvivalProbe":
         from .survprobe import SurvivalProbe
         return SurvivalProbe
+    if name == "CoxProbe":
+        from .coxprobe import CoxProbe
+        return CoxProbe
     if name == "GeneSelect":
         from .geneselect import GeneSelect
         return GeneSelect

@@ -269,6 +269,9 @@ _SIGS = {
     "mh_linprobe_proba": [P, L, I, P, P, I, I, I, P, P, P],
     "mh_survprobe_grad": [P, L, I, P, P, P, P, P, P, P, F, I, I, I, P, P],
     "mh_survprobe_risk": [P, L, I, P, P, I, I, I, P],
+    "mh_coxprobe_scores": [P, L, I, P, I, P],
+    "mh_coxprobe_grad": [P, L, I, P, P, P, P, P, I, P, P, P],
+    "mh_coxprobe_step": [P, L, I, P, P, P, P, P, F, I, P],
     "mh_colstats": [P, L, I, P, P, P],
     "mh_standardize": [P, P, P, P, L, I],
     "mh_gsel_rowsq": [P, L, I, P, I, P],
@@ -283,7 +286,7 @@ EXPORTS = sorted(list(_SIGS) + ["mh_last_error", "mh_version", "mh_exp_build", "
                                  "mh_retrieval_workspace_bytes", "mh_retrieval_topk_workspace_bytes", "mh_cox_workspace_bytes",
                                  "mh_colmean_workspace_bytes", "mh_kmeans_update_workspace_bytes", "mh_kmeans_inertia_workspace_bytes",
                                  "mh_silhouette_workspace_bytes", "mh_kmeanspp_workspace_bytes", "mh_colstats_workspace_bytes",
-                                 "mh_gsel_grad_workspace_bytes", "mh_gsel_slices"])
+                                 "mh_gsel_grad_workspace_bytes", "mh_gsel_slices", "mh_coxprobe_workspace_bytes"])
 
 _lib = None
 
@@ -384,6 +387,11 @@ def load() -> C.CDLL:
     lib.mh_gsel_grad_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int]
     lib.mh_gsel_slices.restype = C.c_int
     lib.mh_gsel_slices.argtypes = [C.c_int64, C.c_int, C.c_int]
+    if not hasattr(lib, "mh_coxprobe_workspace_bytes"):
+        raise MirrorHipError(f"{LIB_PATH} lacks mh_coxprobe_workspace_bytes: rebuild the library (`make -C mirror_amd/csrc`, or "
+                             "__graft_entry__.build())")
+    lib.mh_coxprobe_workspace_bytes.restype = C.c_int64
+    lib.mh_coxprobe_workspace_bytes.argtypes = [C.c_int64, C.c_int]
     for name, sig in _SIGS.items():
         fn = getattr(lib, name, None)
         if fn is None:      # entry points added within a generation (no argument list changed): an older build lacks them

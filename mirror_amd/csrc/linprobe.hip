@@ -242,7 +242,9 @@ __device__ __forceinline__ void lp_store(const f4_t (&r)[LP_QUADS], float* __res
 
 // MASKED (mh_gsel_step): a (job, column) with mask[job, column] = 0 is neither read for the update nor written and takes no part in the
 // maximum; fit_intercept = 0 does the same to the bias column.  MASKED = false is mh_linprobe_step: both arguments are unused.
-template <bool MASKED>
+// BIAS = false (mh_coxprobe_step: the partial likelihood has no intercept) leaves the bias column alone outright: bx and bz are never
+// dereferenced and may be null.
+template <bool MASKED, bool BIAS = true>
 __global__ void __launch_bounds__(RT_THREADS, 2) linprobe_step_kernel(const float* __restrict__ y, const float* __restrict__ G,
                                                                       float* __restrict__ Wx, float* __restrict__ bx,
                                                                       float* __restrict__ Wz, float* __restrict__ bz,
@@ -326,6 +328,7 @@ __global__ void __launch_bounds__(RT_THREADS, 2) linprobe_step_kernel(const floa
                 const int col = col0 + wn * 64 + j * 32 + (lane & 31);
                 if (col > D) continue;
                 const bool isb = col == D;
+                if (!BIAS && isb) continue;
                 if (MASKED && (isb ? !fit_intercept : !mask[(int64_t)job * D + col])) continue;
                 float* px = isb ? bx + key : Wx + (int64_t)key * D + col;
                 float* pz = isb ? bz + key : Wz + (int64_t)key * D + col;
@@ -417,6 +420,24 @@ extern "C" int mh_gsel_step(const float* y, int64_t n, int D, const float* G, fl
     hipLaunchKernelGGL(linprobe_step_kernel<true>, dim3(mh_cdiv(nk, RT_TILE), mh_cdiv(D + 1, RT_TILE)), dim3(RT_THREADS), 0, (hipStream_t)s,
                        y, G, Wx, bx, Wz, bz, lam, eta, beta, (int)n, nk, D, C, lp_shift(Cp), vec_g, vec_y, gmax_part, mask, fit_intercept);
     MH_LAUNCH_CHECK("mh_gsel_step");
+    return MH_OK;
+}
+
+// coxprobe.hip's step: the kernel above with one key per job (C = Cp = 1: `key & (Cp - 1)` is 0, the per-job maximum runs over one key)
+// and no bias column, at that file's limits
+extern "C" int mh_coxprobe_step(const float* y, int64_t n, int D, const float* G, float* Wx, float* Wz, const float* lam, const float* eta,
+                                float beta, int J, float* gmax_part, mh_stream s) {
+    MH_REQUIRE(D >= 1 && D <= LP_MAXD, "mh_coxprobe_step: D = %d outside [1, %d]", D, LP_MAXD);
+    MH_REQUIRE(n >= 1 && n <= 65536, "mh_coxprobe_step: n = %lld outside [1, 65536]", (long long)n);
+    MH_REQUIRE(J >= 1 && n * J <= (1ll << 24), "mh_coxprobe_step: n J = %lld x %d score gradients outside [1, 2^24]", (long long)n, J);
+    MH_REQUIRE(beta >= 0.f && beta <= 1.f, "mh_coxprobe_step: beta = %g outside [0, 1]", (double)beta);
+    MH_REQUIRE(y && G && Wx && Wz && lam && eta, "mh_coxprobe_step: null pointer");
+    const int vec_g = J % 4 == 0 && mh_quad_ok(G, 4);
+    const int vec_y = D % 4 == 0 && mh_quad_ok(y, 4);
+    hipLaunchKernelGGL((linprobe_step_kernel<false, false>), dim3(mh_cdiv(J, RT_TILE), mh_cdiv(D + 1, RT_TILE)), dim3(RT_THREADS), 0,
+                       (hipStream_t)s, y, G, Wx, (float*)nullptr, Wz, (float*)nullptr, lam, eta, beta, (int)n, J, D, 1, 0, vec_g, vec_y,
+                       gmax_part, (const uint8_t*)nullptr, 0);
+    MH_LAUNCH_CHECK("mh_coxprobe_step");
     return MH_OK;
 }
 

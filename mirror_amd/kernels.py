@@ -2984,6 +2984,121 @@ def survprobe_risk(q: torch.Tensor, W: torch.Tensor, b: torch.Tensor, M: int) ->
     return risk
 
 
+# ----------------------------------------------------------------------------- ridge Cox probe: J partial-likelihood regressions at once (csrc/coxprobe.hip)
+COXPROBE_MAX_N = 65536
+
+
+def _cp_weights(W, D: int, what: str) -> int:
+    if not isinstance(W, torch.Tensor) or W.dtype != torch.float32 or W.dim() != 2 or W.shape[1] != D:
+        got = f"{W.dtype} {tuple(W.shape)}" if isinstance(W, torch.Tensor) else type(W).__name__
+        raise ValueError(f"{what} must be f32 [J, {D}], got {got}")
+    return int(W.shape[0])
+
+
+def _cp_out(t, dtype, shape, what: str) -> None:
+    if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
+        raise ValueError(f"{what} must be a contiguous {dtype} {list(shape)}")
+
+
+def coxprobe_workspace(n: int, J: int, device) -> torch.Tensor:
+    """The f64 workspace of coxprobe_grad for n rows and J jobs (mh_coxprobe_workspace_bytes: 28 bytes per score), nothing to zero."""
+    nbytes = int(_lib.load().mh_coxprobe_workspace_bytes(n, J))
+    if nbytes < 0:
+        raise MirrorHipError(f"coxprobe_grad: J = {J} jobs over n = {n} rows (1 <= n <= {COXPROBE_MAX_N}, n * J <= 2^24)")
+    return torch.empty((nbytes // 8,), device=device, dtype=torch.float64)
+
+
+def coxprobe_scores(q: torch.Tensor, W: torch.Tensor, V: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """f32 [J, nq], job-major, on the device (no sync): V[j, i] = q_i . W[j] of the prepared rows q f32 [nq, D] under the weight rows
+    W f32 [J, D] (mh_coxprobe_scores: the retrieval kernels' exact-f32 tile product, one key per job).  V may be passed to be
+    overwritten."""
+    q = _fs_f32(q, "coxprobe_scores: q", device=False)                    # every type and shape first, the device last
+    nq, D = q.shape
+    J = _cp_weights(W, D, "coxprobe_scores: the weights")
+    _cp_out(V, torch.float32, (J, nq), "coxprobe_scores: V")
+    _chk(q, W, V)
+    if not (1 <= J <= (1 << 20)) or nq * J > (1 << 28):
+        raise MirrorHipError(f"coxprobe_scores: J = {J} jobs over nq = {nq} rows (1 <= J <= 2^20, nq * J <= 2^28)")
+    _contig(W, "coxprobe_scores: the weights")
+    if V is None:
+        V = torch.empty((J, nq), device=q.device, dtype=torch.float32)
+    _lib.call("mh_coxprobe_scores", _p(q), nq, D, _p(W), J, _p(V), stream=_stream())
+    return V
+
+
+def coxprobe_grad(V: torch.Tensor, time: torch.Tensor, event: torch.Tensor, fold: torch.Tensor, heldout: torch.Tensor,
+                  rscale: torch.Tensor, ties: str, G: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None):
+    """(G f32 [n, J], loss f64 [J]) on the device (no sync): every job's partial-likelihood score gradient
+    r_j (w_k sum_i q_i ([t_k > t_i] + [t_k = t_i](1 - e_k f_i)) - e_k) over its training rows (event in {0, 1}, time not NaN, fold >= 0,
+    fold != heldout_j), exactly 0 elsewhere, and the data term of its objective (mh_coxprobe_grad: f64 scans over the scores
+    V f32 [J, n] of rows in NON-INCREASING time order, NaN times last; ties "breslow" / "efron").  G, loss and the workspace
+    (coxprobe_workspace) may be passed to be overwritten."""
+    if not isinstance(V, torch.Tensor) or V.dtype != torch.float32 or V.dim() != 2 or not V.is_contiguous():
+        got = f"{V.dtype} {tuple(V.shape)}" if isinstance(V, torch.Tensor) else type(V).__name__
+        raise ValueError(f"coxprobe_grad: V must be a contiguous f32 [J, n], got {got}")
+    J, n = V.shape
+    for t, dtype, name in ((time, torch.float64, "time"), (event, torch.uint8, "event"), (fold, torch.int32, "fold")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (n,):
+            raise ValueError(f"coxprobe_grad: {name} must be {dtype} [{n}]")
+    for t, dtype, name in ((heldout, torch.int32, "heldout"), (rscale, torch.float32, "rscale")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (J,):
+            raise ValueError(f"coxprobe_grad: {name} must be {dtype} [{J}]")
+    if ties not in COX_TIES:
+        raise ValueError(f'coxprobe_grad: ties must be "breslow" or "efron", got {ties!r}')
+    _cp_out(G, torch.float32, (n, J), "coxprobe_grad: G")
+    _cp_out(loss, torch.float64, (J,), "coxprobe_grad: loss")
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float64 or workspace.dim() != 1
+                                  or not workspace.is_contiguous()):
+        raise ValueError("coxprobe_grad: workspace must be a contiguous 1-D f64 tensor (coxprobe_workspace)")
+    _chk(V, time, event, fold, heldout, rscale, G, loss, workspace)
+    if not (1 <= n <= COXPROBE_MAX_N) or not (1 <= J) or n * J > (1 << 24):
+        raise MirrorHipError(f"coxprobe_grad: J = {J} jobs over n = {n} rows (1 <= n <= {COXPROBE_MAX_N}, n * J <= 2^24)")
+    need = int(_lib.load().mh_coxprobe_workspace_bytes(n, J)) // 8
+    if workspace is None:
+        workspace = torch.empty((need,), device=V.device, dtype=torch.float64)
+    elif workspace.numel() < need:
+        raise ValueError(f"coxprobe_grad: workspace holds {workspace.numel()} f64, {need} are needed")
+    if G is None:
+        G = torch.empty((n, J), device=V.device, dtype=torch.float32)
+    if loss is None:
+        loss = torch.empty((J,), device=V.device, dtype=torch.float64)
+    _lib.call("mh_coxprobe_grad", _p(V), n, J, _p(time.contiguous()), _p(event.contiguous()), _p(fold.contiguous()),
+              _p(heldout.contiguous()), _p(rscale.contiguous()), COX_TIES[ties], _p(G), _p(loss), _p(workspace), stream=_stream())
+    return G, loss
+
+
+def coxprobe_step(y: torch.Tensor, G: torch.Tensor, Wx: torch.Tensor, Wz: torch.Tensor, lam: torch.Tensor, eta: torch.Tensor,
+                  beta: float, gmax_part: Optional[torch.Tensor] = None, want_gmax: bool = False):
+    """One FISTA update of every job IN PLACE (no sync): g = G^T y + lam_j Wz, X' = Wz - eta_j g, Z' = X' + beta (X' - Wx), stored over
+    Wx / Wz f32 [J, D]; no intercept (mh_coxprobe_step: mh_linprobe_step's kernel with one key per job, one row-ordered f32 chain per
+    element).  Returns gmax_part f32 [ceil((D + 1) / 128), J] (max |g| per column tile and job) or None."""
+    y = _fs_f32(y, "coxprobe_step: y", device=False)
+    n, D = y.shape
+    J = _cp_weights(Wz, D, "coxprobe_step: Wz")
+    if _cp_weights(Wx, D, "coxprobe_step: Wx") != J:
+        raise ValueError(f"coxprobe_step: Wx has {Wx.shape[0]} jobs, Wz {J}")
+    if not isinstance(G, torch.Tensor) or G.dtype != torch.float32 or tuple(G.shape) != (n, J) or not G.is_contiguous():
+        raise ValueError(f"coxprobe_step: G must be a contiguous f32 [{n}, {J}]")
+    for t, name in ((lam, "lam"), (eta, "eta")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (J,):
+            raise ValueError(f"coxprobe_step: {name} must be {torch.float32} [{J}]")
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not (0.0 <= float(beta) <= 1.0):
+        raise ValueError(f"coxprobe_step: beta must lie in [0, 1], got {beta!r}")
+    tiles = (D + 1 + 127) // 128
+    _cp_out(gmax_part, torch.float32, (tiles, J), "coxprobe_step: gmax_part")
+    _chk(y, G, Wx, Wz, lam, eta, gmax_part)
+    if not (1 <= n <= COXPROBE_MAX_N) or not (1 <= J) or n * J > (1 << 24):
+        raise MirrorHipError(f"coxprobe_step: J = {J} jobs over n = {n} rows (1 <= n <= {COXPROBE_MAX_N}, n * J <= 2^24)")
+    _contig(Wx, "coxprobe_step: Wx")
+    _contig(Wz, "coxprobe_step: Wz")
+    if gmax_part is None and want_gmax:
+        gmax_part = torch.empty((tiles, J), device=y.device, dtype=torch.float32)
+    _lib.call("mh_coxprobe_step", _p(y), n, D, _p(G), _p(Wx), _p(Wz), _p(lam.contiguous()), _p(eta.contiguous()), float(beta), J,
+              _p(gmax_part), stream=_stream())
+    return gmax_part
+
+
 # ----------------------------------------------------------------------------- k-means and its agreement with labels (csrc/kmeans.hip)
 KMEANS_METRIC = {"euclidean": 0, "cosine": 1}
 

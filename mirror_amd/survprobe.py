@@ -27,8 +27,8 @@ logits, hazard NLL and logit gradient: the J Mp weight rows are the keys of the 
 held-out fold is scored by `mh_survprobe_risk` (its S jobs as keys, the logits never stored) and `mh_cindex_counts` once per strength;
 all counts are stacked on the device and read back in one copy.
 
-Not built: time-dependent AUC, the Brier score, a Cox objective inside the probe (`CoxSurvLoss` trains one), a pool gathered over DDP
-ranks, a batched concordance kernel (a fold is a few hundred rows).
+Not built: time-dependent AUC, the Brier score, a pool gathered over DDP ranks, a batched concordance kernel (a fold is a few hundred
+rows).  A Cox objective inside a probe, on the follow-up time itself, is `coxprobe.py`'s `CoxProbe`.
 """
 from __future__ import annotations
 
