@@ -43,6 +43,9 @@ int mh_device_ok(void);
  * ":one,drop", "resconv_fwd:mfma" / ":vec" / ":scalar", "resconv_wgrad:mfma" / ":vec8" / ":scalar", "resconv_bwd:mfma" / ":two_pass"
  * (written after the two entry points it forwards to), "landmark_fwd:quad" / ":scalar", "landmark_bwd:oct" / ":scalar"; a call that
  * was refused (MH_EINVAL) has noted "<entry>:none" as well.
+ * The fused loss notes the branches its kernels take: "loss_terms_fwd:<align>,<cluster>" with <align> = "ext" (no rank-local alignment
+ * term), "quad" (D % 4 == 0) or "scalar" staging of the embeddings and <cluster> = "regs" (P <= 4096: the score row in registers) or
+ * "global"; "loss_terms_bwd:<align>,<cluster>" with <align> = "ext", "bm16" (B <= 16) or "bm32"; ":none" when the call was refused.
  * mh_note_form is what the entry points call beside the launch they pick: it keeps the POINTER (string literals only), one store. */
 void mh_note_form(const char* literal);
 const char* mh_last_form(void);
@@ -567,6 +570,9 @@ int64_t mh_rna_block_workspace_bytes(int B, int D, int Hh);
 int64_t mh_rna_block_lds_bytes(int B, int D, int Hh);
 int mh_rna_block_fits(int B, int D, int Hh, int H);
 
+/* Attention over the heads axis of qkv [B, 3 H hd] (f32 or bf16): out [B, H hd], attn [B, H, H] f32.  Both directions admit the same
+ * shapes, H <= 64 and H hd <= 4096, and opt in to the backward's dynamic LDS (16 H hd + 8 H^2 bytes, up to 96 KiB; the forward asks
+ * for 12 H hd + 4 H^2): where the device declines that, the forward refuses too, so no forward succeeds whose backward cannot run. */
 int mh_headattn_fwd(const void* qkv, void* out, float* attn, int B, int H, int hd, int dt, mh_stream s);
 int mh_headattn_bwd(const void* qkv, const float* attn, const void* dout, void* dqkv, int B, int H, int hd,
                     int dt, mh_stream s);
@@ -775,6 +781,8 @@ int mh_loss_terms_bwd(const mh_loss_terms* d, mh_stream s);
 /* w[r] /= max(||w[r]||, eps) in place (the prototype renormalisation, train_mirror.py:1133-1136); shadow_bf16 (nullable, [rows, D]
  * contiguous) receives the bf16 copy of the result in the same pass */
 int mh_rownorm_(float* w, void* shadow_bf16, int rows, int D, float eps, mh_stream s);
+/* x = min(max(x, lo), hi) in place as torch.clamp_ has it: the bounds apply to +-inf, a NaN stays a NaN (the optimizers' clamped
+ * element below follows the same rule) */
 int mh_clamp_(float* x, int64_t n, float lo, float hi, mh_stream s);
 /* torch.optim.Adam (wd=0): flat f32 params/grads/moments; optional bf16 shadow copy of the params.  This is mh_optim_step's rule
  * MH_OPT_ADAM without a group map behind an older argument list: one device body (optim.hip) serves both, bit for bit.

@@ -94,6 +94,17 @@ __device__ __forceinline__ float block_max256(float v, float* red) {
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
+// a * b rounded to f32 on its own.  Written `s * g - m`, the compiler fuses product and difference into one fma, which keeps the
+// product exact: against an m that IS the rounded product the result is the rounding residue of s g (up to 4e-6 at a logit of 100)
+// where 0 is meant, so a logit differs between the pass that reduces it and the pass that subtracts the reduction.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+// torch.clamp: the bounds apply to +-inf, a NaN stays a NaN (fminf / fmaxf alone return their other operand, i.e. lo)
+__device__ __forceinline__ float clamp_keep_nan(float x, float lo, float hi) { return x != x ? x : fminf(fmaxf(x, lo), hi); }
+
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_grad_f(float x) {
     const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752f));

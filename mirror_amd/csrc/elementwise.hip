@@ -1259,8 +1259,24 @@ __global__ __launch_bounds__(256) void headattn_bwd_kernel(const T* __restrict__
     }
 }
 
+// One admission rule for the pair: the forward takes exactly what the backward can run.  Dynamic LDS: forward 12 D + 4 H^2 bytes,
+// backward 16 D + 8 H^2, which passes the 64 KiB a kernel gets without asking from D > 4096 - H^2 / 2 on; both directions opt in to
+// the backward's largest request (H = 64, D = 4096: 96 KiB of the CU's 160 KiB) and refuse every shape when the device declines.
+constexpr size_t HA_LDS_MAX = (4 * (size_t)4096 + 2 * (size_t)64 * 64) * sizeof(float);
+static_assert(HA_LDS_MAX <= 160 * 1024, "headattn: the backward's largest LDS request must fit a CU");
+static int headattn_admit(const char* who, int H, int hd) {
+    MH_REQUIRE(H >= 1 && H <= 64 && (long)H * hd <= 4096, "%s: H=%d hd=%d unsupported", who, H, hd);
+    static const bool big = [] {
+#define HA_ATTR(KERN) (hipFuncSetAttribute(reinterpret_cast<const void*>(&KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)HA_LDS_MAX) == hipSuccess)
+        return HA_ATTR(headattn_fwd_kernel<float>) && HA_ATTR(headattn_fwd_kernel<bf16_t>) && HA_ATTR(headattn_bwd_kernel<float>) && HA_ATTR(headattn_bwd_kernel<bf16_t>);
+#undef HA_ATTR
+    }();
+    MH_REQUIRE(big, "%s: the device refused %d bytes of dynamic LDS", who, (int)HA_LDS_MAX);
+    return MH_OK;
+}
+
 extern "C" int mh_headattn_fwd(const void* qkv, void* out, float* attn, int B, int H, int hd, int dt, mh_stream s) {
-    MH_REQUIRE(H >= 1 && H <= 64 && (long)H * hd <= 4096, "mh_headattn_fwd: H=%d hd=%d unsupported", H, hd);
+    if (const int rc = headattn_admit("mh_headattn_fwd", H, hd)) return rc;
     if (B == 0) return MH_OK;
     const size_t lds = (3 * (size_t)H * hd + (size_t)H * H) * sizeof(float);
     MH_DISPATCH_DT(dt, T, hipLaunchKernelGGL((headattn_fwd_kernel<T>), dim3(B), dim3(256), lds, (hipStream_t)s, (const T*)qkv, (T*)out, attn, H, hd));
@@ -1270,7 +1286,7 @@ extern "C" int mh_headattn_fwd(const void* qkv, void* out, float* attn, int B, i
 
 extern "C" int mh_headattn_bwd(const void* qkv, const float* attn, const void* dout, void* dqkv, int B, int H, int hd, int dt,
                                mh_stream s) {
-    MH_REQUIRE(H >= 1 && H <= 64 && (long)H * hd <= 4096, "mh_headattn_bwd: H=%d hd=%d unsupported", H, hd);
+    if (const int rc = headattn_admit("mh_headattn_bwd", H, hd)) return rc;
     if (B == 0) return MH_OK;
     const size_t lds = (4 * (size_t)H * hd + 2 * (size_t)H * H) * sizeof(float);
     MH_DISPATCH_DT(dt, T, hipLaunchKernelGGL((headattn_bwd_kernel<T>), dim3(B), dim3(256), lds, (hipStream_t)s, (const T*)qkv, attn, (const T*)dout, (T*)dqkv, H, hd));

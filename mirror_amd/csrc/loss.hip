@@ -15,15 +15,17 @@ __global__ __launch_bounds__(256) void ce_rows_fwd_kernel(const float* __restric
     if (r >= R) return;
     const float s = (scale ? scale[0] : 1.f) * scale_mul;
     const float* g = G + (long)r * ldg;
+    // every logit is the ROUNDED product (mul_rn), here and in the backward: a single logit then costs exactly 0 and a saturated row
+    // leaves exactly the gradient its softmax has
     float m = -INFINITY;
-    for (int c = lane; c < C; c += 64) m = fmaxf(m, s * g[c]);
+    for (int c = lane; c < C; c += 64) m = fmaxf(m, mul_rn(s, g[c]));
     m = wave_max(m);
     float sum = 0.f;
-    for (int c = lane; c < C; c += 64) sum += __expf(s * g[c] - m);
+    for (int c = lane; c < C; c += 64) sum += __expf(mul_rn(s, g[c]) - m);
     sum = wave_sum(sum);
     if (lane == 0) {
         const float l = m + __logf(sum);
-        const float loss = l - s * g[label_off + r];
+        const float loss = l - mul_rn(s, g[label_off + r]);
         lse[r] = l;
         if (loss_rows) loss_rows[r] = coef * loss;
         if (out) atomicAdd(out, coef * loss);
@@ -46,7 +48,7 @@ __global__ __launch_bounds__(256) void ce_rows_bwd_kernel(const float* __restric
     const float l = lse[r];
     float ds = 0.f;
     for (int c = lane; c < C; c += 64) {
-        const float p = __expf(s * gr[c] - l) - (c == label_off + r ? 1.f : 0.f);
+        const float p = __expf(mul_rn(s, gr[c]) - l) - (c == label_off + r ? 1.f : 0.f);
         dG[(long)r * C + c] = w * s * p;
         ds += w * p * gr[c];
     }
@@ -520,7 +522,7 @@ extern "C" int mh_rownorm_(float* w, void* shadow_bf16, int rows, int D, float e
 }
 
 __global__ void clamp_kernel(float* x, long n, float lo, float hi) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) x[i] = fminf(fmaxf(x[i], lo), hi);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) x[i] = clamp_keep_nan(x[i], lo, hi);
 }
 extern "C" int mh_clamp_(float* x, int64_t n, float lo, float hi, mh_stream s) {
     if (n == 0) return MH_OK;

@@ -140,15 +140,16 @@ __global__ __launch_bounds__(256) void loss_terms_fwd_kernel(mh_loss_terms d) {
             float loss = 0.f;        // lane 0 of each wave carries its rows' sums
             for (int r = wave; r < B; r += 4) {
                 // image -> rna direction: row r of s G; rna -> image: column r
-                const float vr = lane < B ? s * Gs[r * ldg + lane] : -INFINITY;
-                const float vc = lane < B ? s * Gs[lane * ldg + r] : -INFINITY;
+                // (the logits are the ROUNDED products, here and in the backward: see mul_rn)
+                const float vr = lane < B ? mul_rn(s, Gs[r * ldg + lane]) : -INFINITY;
+                const float vc = lane < B ? mul_rn(s, Gs[lane * ldg + r]) : -INFINITY;
                 const float mr = wave_max(vr), mc = wave_max(vc);
                 const float sr = wave_sum(lane < B ? __expf(vr - mr) : 0.f), sc = wave_sum(lane < B ? __expf(vc - mc) : 0.f);
                 const float lr = mr + __logf(sr), lc = mc + __logf(sc);
                 if (lane == 0) {
                     d.save[B * B + r] = lr;
                     d.save[B * B + B + r] = lc;
-                    loss += (lr + lc) - 2.f * s * Gs[r * ldg + r];
+                    loss += (lr + lc) - 2.f * mul_rn(s, Gs[r * ldg + r]);
                 }
             }
             loss = block_sum256(lane == 0 ? loss : 0.f, red);
@@ -235,7 +236,8 @@ __device__ __forceinline__ void align_bwd(const mh_loss_terms& d, float* Ps, flo
         float pv = 0.f;
         if (r < B && c < B) {
             const float g = d.save[r * B + c], eye = r == c ? 2.f : 0.f;
-            const float p = __expf(s * g - d.save[B * B + r]) + __expf(s * g - d.save[B * B + B + c]) - eye;
+            const float v = mul_rn(s, g);
+            const float p = __expf(v - d.save[B * B + r]) + __expf(v - d.save[B * B + B + c]) - eye;
             pv = w * s * p;
             ds += w * p * g;
         }
@@ -373,23 +375,34 @@ int check(const mh_loss_terms* d, const char* who) {
 }  // namespace
 
 extern "C" int mh_loss_terms_fwd(const mh_loss_terms* d, mh_stream s) {
+    mh_note_form("loss_terms_fwd:none");
     const int rc = check(d, "mh_loss_terms_fwd");
     if (rc != MH_OK) return rc;
     const size_t lds = align_lds_bytes(d);
     static bool once = [] { return hipFuncSetAttribute((const void*)loss_terms_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess; }();
     MH_REQUIRE(once, "mh_loss_terms_fwd: cannot raise the dynamic LDS limit");
+    // the branches the kernel takes on these operands: how the alignment block stages its embeddings, where a cluster block holds its row
+    const bool regs = d->P <= 256 * SK_E;
+    if (!d->has_align) mh_note_form(regs ? "loss_terms_fwd:ext,regs" : "loss_terms_fwd:ext,global");
+    else if ((d->D & 3) == 0) mh_note_form(regs ? "loss_terms_fwd:quad,regs" : "loss_terms_fwd:quad,global");
+    else mh_note_form(regs ? "loss_terms_fwd:scalar,regs" : "loss_terms_fwd:scalar,global");
     hipLaunchKernelGGL(loss_terms_fwd_kernel, dim3(d->Bc + 3 + NMSE), dim3(256), lds, (hipStream_t)s, *d);
     MH_LAUNCH_CHECK("mh_loss_terms_fwd");
     return MH_OK;
 }
 
 extern "C" int mh_loss_terms_bwd(const mh_loss_terms* d, mh_stream s) {
+    mh_note_form("loss_terms_bwd:none");
     const int rc = check(d, "mh_loss_terms_bwd");
     if (rc != MH_OK) return rc;
     MH_REQUIRE(d->d_w_score && d->d_r_score && d->d_w_mu && d->d_w_logstd && d->d_r_mu && d->d_r_logstd && d->d_rna_pred,
                "mh_loss_terms_bwd: null gradient pointer");
     MH_REQUIRE(!d->has_align || (d->d_wsi_emb && d->d_rna_emb), "mh_loss_terms_bwd: null embedding gradient pointer");
     const size_t lds = sizeof(float) * BMAX * BMAX;
+    const bool regs = d->P <= 256 * SK_E;
+    if (!d->has_align) mh_note_form(regs ? "loss_terms_bwd:ext,regs" : "loss_terms_bwd:ext,global");
+    else if (d->B <= 16) mh_note_form(regs ? "loss_terms_bwd:bm16,regs" : "loss_terms_bwd:bm16,global");
+    else mh_note_form(regs ? "loss_terms_bwd:bm32,regs" : "loss_terms_bwd:bm32,global");
     hipLaunchKernelGGL(loss_terms_bwd_kernel, dim3(d->Bc + NALIGN + 2 + NMSE), dim3(256), lds, (hipStream_t)s, *d);
     MH_LAUNCH_CHECK("mh_loss_terms_bwd");
     return MH_OK;

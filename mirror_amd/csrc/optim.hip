@@ -104,7 +104,7 @@ __device__ __forceinline__ void optim_body(OPTIM_PARAMS_) {
 #pragma unroll
         for (int e = 0; e < 4; e++) optim_elem<RULE, MOM>(pa[e], ga[e], ma[e], va[e], wd, c);
         // one element (logit_scale, train_mirror.py:1255) is clamped right behind its update: master, shadow and EMA get the clamped value
-        if ((clamp_i >> 2) == q && clamp_i >= 0) pa[clamp_i & 3] = fminf(fmaxf(pa[clamp_i & 3], clamp_lo), clamp_hi);
+        if ((clamp_i >> 2) == q && clamp_i >= 0) pa[clamp_i & 3] = clamp_keep_nan(pa[clamp_i & 3], clamp_lo, clamp_hi);
         reinterpret_cast<float4*>(p)[q] = pp;
         if constexpr (MOM) reinterpret_cast<float4*>(m)[q] = mm;
         if constexpr (RULE != MH_OPT_SGD) reinterpret_cast<float4*>(v)[q] = vv;
@@ -136,7 +136,7 @@ __device__ __forceinline__ void optim_body(OPTIM_PARAMS_) {
         if constexpr (MOM) mi = m[i];
         if constexpr (RULE != MH_OPT_SGD) vi = v[i];
         optim_elem<RULE, MOM, true>(pn, g[i], mi, vi, wd, c);
-        if (i == clamp_i) pn = fminf(fmaxf(pn, clamp_lo), clamp_hi);
+        if (i == clamp_i) pn = clamp_keep_nan(pn, clamp_lo, clamp_hi);
         p[i] = pn;
         if constexpr (MOM) m[i] = mi;
         if constexpr (RULE != MH_OPT_SGD) v[i] = vi;

@@ -1631,7 +1631,8 @@ def last_form() -> str:
     "add:scalar", "softmax_fwd:wave,quad", "layernorm_bwd:ws"; "<entry>:none" when the call returned before any launch or was refused.
     The sequence kernels note theirs too: ppeg_fwd (pair, strip), ppeg_wgrad (strip), ppeg_bwd (one / one,drop), resconv_fwd (mfma, vec,
     scalar), resconv_wgrad (mfma, vec8, scalar), resconv_bwd (mfma, two_pass: written after the two calls it forwards to), landmark_fwd
-    (quad, scalar) and landmark_bwd (oct, scalar)."""
+    (quad, scalar) and landmark_bwd (oct, scalar).  The fused loss notes "loss_terms_fwd:<align>,<cluster>" (align: ext, quad, scalar;
+    cluster: regs, global) and "loss_terms_bwd:<align>,<cluster>" (align: ext, bm16, bm32)."""
     return (_lib.load().mh_last_form() or b"").decode()
 
 
